@@ -255,6 +255,67 @@ def cpu_baseline_wide(gen, L, D, R, per_gpu, mu, records, snp_every):
             "reference_python": REFERENCE_PYTHON}
 
 
+DUMP_BUDGET_BYTES = 64 << 20                    # --dump-outputs: all files of all ranks together
+DUMP_HEADER_BYTES = 64 << 10                    # (per rank: kept apart for the .npy headers and counts.npy)
+DUMP_SEED = 20240601                            # the fixed row sample of an output larger than its share of the budget
+
+
+def _u64_to_f64(a):
+    """uint64 [n] -> float64 [n, 2] (high, low 32-bit halves): exact, which a plain float64 cast of a 56-bit key is not"""
+    import numpy as np
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(eng, out_dir, prefix, wide, ids, nrec, budget, with_cands=True):
+    """--dump-outputs: what the last timed step left for its caller, as float64 .npy files in `out_dir`, at most
+    `budget` bytes in all (this rank's share of DUMP_BUDGET_BYTES).  u64 fields become exact high / low 32-bit halves, u32 fields are exact as they are; rows
+    are put in a canonical order.  Narrow path: the candidates (prefix, in_mask, out_mask), the collected records (key,
+    genome, count) and the sorted keys of every genome; wide path: the hits (cand, genome, pos, strand), the groups'
+    composite keys and the per-genome record counts.  `with_cands` = False leaves out the candidate list (at world > 1
+every rank holds the one rank 0 writes).  Every output gets an equal share of the budget; one larger than
+    its share (the sorted keys: hundreds of MB per genome) is written as a fixed, seeded sample of its rows.
+    `<prefix>counts.npy` holds the full row count of every output, in the order of the returned `files`."""
+    import numpy as np
+    from krisp_amd import _native
+
+    def fields(*names):
+        """structured rows -> float64 [n, columns]: u64 fields as two columns, u32 fields as one"""
+        return lambda a: np.concatenate([_u64_to_f64(a[f]) if a.dtype[f].itemsize == 8 else a[f].astype(np.float64)[:, None]
+                                         for f in names], axis=-1)
+    outs = {}                       # name -> (row count, float64 columns, fetch() -> rows in canonical order, rows -> float64)
+    if wide:
+        outs["wide_hits"] = (eng.wide_count(_native.WIDE_HITS), 4,
+                             lambda: np.sort(eng.wide_fetch(_native.WIDE_HITS), order=["cand", "genome", "pos", "strand"]),
+                             fields("cand", "genome", "pos", "strand"))
+        outs["wide_groups"] = (eng.wide_count(_native.WIDE_GROUPS), 2, lambda: np.sort(eng.wide_fetch(_native.WIDE_GROUPS)),
+                               _u64_to_f64)
+        outs["wide_counts"] = (eng.wide_count(_native.WIDE_COUNTS), 1, lambda: eng.wide_fetch(_native.WIDE_COUNTS),
+                               lambda a: a.astype(np.float64))
+    else:
+        if with_cands:
+            c = eng.cands()
+            outs["cands"] = (len(c), 6, lambda: c, fields("prefix", "in_mask", "out_mask"))
+        outs["records"] = (nrec, 4, lambda: np.sort(eng.fetch_records(nrec), order=["key", "genome"]),
+                           fields("key", "genome", "count"))
+        for g in ids:
+            outs[f"keys_genome{g}"] = (eng.count(g), 2, lambda g=g: eng.keys(g), _u64_to_f64)
+    os.makedirs(out_dir, exist_ok=True)
+    share = (budget - DUMP_HEADER_BYTES) // len(outs)
+    files = {}
+    for i, (name, (n, cols, fetch, to_f64)) in enumerate(outs.items()):
+        a = fetch()
+        cap = share // (8 * cols)
+        if len(a) > cap:
+            a = a[np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED + i)).choice(len(a), cap, replace=False))]
+        a = np.ascontiguousarray(to_f64(a), dtype=np.float64)
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+        files[f"{prefix}{name}.npy"] = {"rows": int(len(a)), "of": int(n)}
+        del a
+    np.save(os.path.join(out_dir, f"{prefix}counts.npy"), np.asarray([o[0] for o in outs.values()], dtype=np.float64))
+    return {"dir": out_dir, "files": files, "counts": f"{prefix}counts.npy"}
+
+
 def self_launch(n, timeout_s):
     """`bench.py --gpus N` without a launcher: this process -- which has not touched the GPU and never will -- starts N
     fresh copies of itself, one rank each (RANK / LOCAL_RANK / WORLD_SIZE as torch.distributed.run sets them, a private
@@ -354,9 +415,18 @@ def main():
                     help="at --gpus 8 without --config: leave out the second block that times BASELINE configs[3]'s load")
     ap.add_argument("--force-configs3", action="store_true", help="time the configs[3] block at any world size (tests)")
     ap.add_argument("--configs3-length", type=int, default=0, help="genome length of that block (tests; default: configs[3]'s 100 Mbp)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, at most "
+                         "64 MB in all, shared by the ranks; with more than one rank the names start with rank<r>_ and "
+                         "rank 0 alone writes the candidates): the same arguments give the same inputs, so two builds can "
+                         "be compared output for output")
     ap.add_argument("--launch-timeout", type=int, default=1500,
                     help="self-launched ranks (--gpus N without a launcher) are ended after this many seconds")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     # RCCL writes its version banner (NCCL_DEBUG=VERSION, what these boxes export) and its warnings to STDOUT, in front of
     # the ONE JSON line: errors only, unless the caller asked for more than the banner
@@ -485,6 +555,16 @@ def main():
     comm1 = eng.debug_comm() if comm else None      # (before the closing barrier: that is bench.py's, not the step's)
     barrier()
     dt = time.perf_counter() - t0                   # (the K steps and their closing barrier, nothing else: ADVICE r5)
+    stages = eng.stage_times() if not args.no_stage_timers else {}
+    dumped, lazy_dump = None, {}
+    if args.dump_outputs:
+        # (untimed, before the self-exchange and the configs[3] block change the step's results.  Fetching a genome's keys
+        # makes the in-bucket order KR_OPT_LAZY_ORDER left out: LDS sorts that the stage table -- read above -- and the
+        # lazy-order counters would count; the dump's share of those counters is taken off where the line reads them)
+        lazy0 = eng.debug_lazy()
+        dumped = dump_outputs(eng, args.dump_outputs, f"rank{rank}_" if world > 1 else "", wide, ids, nrec[0],
+                              DUMP_BUDGET_BYTES // world, with_cands=rank == 0)
+        lazy_dump = {key: v - lazy0[key] for key, v in eng.debug_lazy().items()}
     if comm and args.transport == "rccl" and not wide and world == 1:
         # --force-comm at N = 1: one round of the tree with the rank as its own partner, on the real transport -- the step's
         # candidate list + header through ncclSend / ncclRecv, merged as a received list is (kr_debug_cands_selfexchange)
@@ -495,7 +575,6 @@ def main():
         except _native.KrispHipError as e:
             selfx = {"error": str(e)}
         barrier()
-    stages = eng.stage_times() if not args.no_stage_timers else {}
     kmers_local = int(sum(eng.wide_fetch(_native.WIDE_COUNTS))) if wide else sum(eng.count(g) for g in ids)
     # measured streaming-copy rate of this box: the best of every copy form x grid the library times (kr_debug_copy_gbps),
     # over 1 GiB and over 800 MB arrays (the size of a genome's key array)
@@ -643,7 +722,7 @@ def main():
             # (`basis` says which).  `kernel` = the dominant kernel BY ITSELF (one sort lane, calibration
             # steps of this run: what `rocprofv3 --stats` of `bench.py --lanes 1` shows), `live` = the same kernel inside
             # the timed region, where its launches share the device with other genomes' kernels.
-            lazy = eng.debug_lazy()
+            lazy = {key: v - lazy_dump.get(key, 0) for key, v in eng.debug_lazy().items()}
             alg_bpk = None
             if not wide:
                 sb = stage_bytes
@@ -729,6 +808,7 @@ def main():
                                       f" + tree-reduce of candidates ({args.transport})")},
             "roofline": roof,
             "configs3": configs3,
+            "dumped_outputs": dumped,
         }
         if world == 1 and not args.no_cpu_baseline and wide:
             out["cpu_baseline"] = cpu_baseline_wide(config, L, Dg, R, per_gpu, args.mu, args.records, args.snp_every)
