@@ -306,6 +306,21 @@ int64_t kr_read_file(const char* path, uint8_t** text, int64_t* stats);
  * stands (the reference: kstream.py:458-479, gzip.open).  stats[8]: [0..3] as kr_genome_upload_text, [4] members,
  * [5] first bad member, [6] its status, [7] microseconds of the inflate + CRC kernels. */
 int64_t kr_genome_upload_bgzf(kr_ctx*, int id, const uint8_t* file, size_t n, int one_shot, int64_t* stats);
+/* A `.gz` file of ONE plain gzip member (what `gzip` writes; csrc/k_gunzip.inc) inflated ON THE DEVICE, then parsed there as
+ * kr_genome_upload_bgzf parses its text: `file` = the bytes as they lie on disk (header with any of FEXTRA / FNAME /
+ * FCOMMENT / FHCRC, deflate data, trailer, zero padding behind it).  The deflate data is cut into chunks of `chunk`
+ * compressed bytes (0: the library's choice); every chunk after the first finds a block start by trial, the chunks decode
+ * side by side into 16-bit symbols (a byte, or a place in the unknown 32 KB in front of the chunk), the windows are handed
+ * down the line, CRC-32 and ISIZE checked against the trailer.  Returns the number of bases; KR_ERR_HOST -- nothing
+ * uploaded -- for a BGZF file, a second member or other data behind the trailer, a file or text of >= 2^32 - 64 bytes, a
+ * CRC or ISIZE that differs, anything that does not decode, or scratch (about 2 bytes per byte of text + the file) that
+ * does not fit: the caller then reads the file through kr_read_file, whose verdict stands.  The scratch is given back
+ * before the call returns.  stats[8]: [0..3] as kr_genome_upload_text, [4] chunks, [5] chunks joined (their block start
+ * was real), [6] the longest run of windows resolved one after the other, [7] microseconds of the inflate's wall time (the
+ * kernels, the host's walk along the chunks between them, the small copies of their results).  Tuning: KRISP_GZ_CHUNK =
+ * the chunk size when `chunk` is 0 (default 256 KB), KRISP_GZ_LANES = active lanes per wave of the decode (1 .. 64,
+ * default 64); KRISP_PGZIP_DEBUG=1 prints the chunks, starts found, line and window runs of every call. */
+int64_t kr_genome_upload_gzip(kr_ctx*, int id, const uint8_t* file, size_t n, size_t chunk, int one_shot, int64_t* stats);
 /* The large device buffers of `n` genomes (ids[]) of up to n_bases bases each -- upload buffer, sorted-key arrays, sort
  * lanes; with_text: the device reader's copy of the file text as well -- made ahead of the uploads, while host threads
  * still read and inflate the files (krisp_fasta.py:86-123 starts a process per genome; here the one context gets its

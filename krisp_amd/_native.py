@@ -93,6 +93,7 @@ SYMBOLS = [
     ("kr_read_file", _c.c_int64, [_c.c_char_p, _P, _P]),
     ("kr_genome_upload_text", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t, _c.c_int, _c.c_int, _P]),
     ("kr_genome_upload_bgzf", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t, _c.c_int, _P]),
+    ("kr_genome_upload_gzip", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _c.c_int, _P]),
     ("kr_reserve", _c.c_int, [_P, _P, _c.c_int, _c.c_size_t, _c.c_int]),
     ("kr_genome_fetch_bases", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t]),
     ("kr_host_free", None, [_P]),
@@ -396,6 +397,22 @@ class Engine:
             return None
         n = self._check(n, "kr_genome_upload_bgzf")
         return n, int(stats[0]), int(stats[1]), stats[2] == 1, bool(stats[3]), int(stats[4]), int(stats[7])
+
+    def upload_gzip(self, gid, raw, chunk=None, one_shot=True):
+        """the bytes of a `.gz` file of one plain gzip member -> genome gid: inflated on the device (chunks of `chunk`
+        compressed bytes, None: the library's choice; block starts found by trial, windows handed down the line, CRC-32 and
+        ISIZE checked), then parsed there (kr_genome_upload_gzip).  Returns (bases, records, special characters, rna, fasta,
+        chunks, microseconds of the inflate (wall time: kernels and the host steps between them), chunks joined, longest window run), or None -- nothing uploaded, the
+        reason in `last_gzip` -- when the device path does not take the file: the caller reads it as any other .gz."""
+        t = np.ascontiguousarray(raw, dtype=np.uint8)
+        stats = np.zeros(8, dtype=np.int64)
+        n = self.lib.kr_genome_upload_gzip(self.ctx, gid, _ptr(t), len(t), int(chunk or 0), 1 if one_shot else 0, _ptr(stats))
+        if n == ERR_HOST:
+            self.last_gzip = (int(stats[4]), int(stats[5]), int(stats[6]), self.lib.kr_last_error(self.ctx).decode())
+            return None
+        n = self._check(n, "kr_genome_upload_gzip")
+        return (n, int(stats[0]), int(stats[1]), stats[2] == 1, bool(stats[3]), int(stats[4]), int(stats[7]), int(stats[5]),
+                int(stats[6]))
 
     def reserve(self, ids, n_bases, with_text=False):
         """the large device buffers of genomes `ids` of up to n_bases bases, ahead of their uploads (kr_reserve)"""

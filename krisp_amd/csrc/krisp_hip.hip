@@ -41,6 +41,7 @@
 #include "k_intersect3t.inc" // ... with 32-bit heads where the geometry allows
 #include "k_text.inc"        // the reference reader on the device: file text -> upload buffer
 #include "k_inflate.inc"     // BGZF members inflated on the device, a lane per member (round 6)
+#include "k_gunzip.inc"      // one plain gzip member inflated on the device: chunks, block starts found by trial, windows
 #include "k_wide.inc"        // wide path kernels, copy kernel
 
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
@@ -48,6 +49,7 @@
 #include "h_wide.inc"        // kr_wide_run
 #include "h_pgzip.inc"       // one gzip member inflated on several threads (host only)
 #include "h_ingest.inc"      // file -> inflate -> parse -> pinned upload buffer (host side)
+#include "h_gunzip.inc"      // kr_genome_upload_gzip: the host side of k_gunzip.inc
 #include "h_comm.inc"        // multi-GPU exchange: RCCL (or files, for rehearsal) tree reduction of candidates, gather of records
 #include "h_text.inc"        // FASTA text parser, IUPAC side-channel scan (host only, no HIP)
 #include "h_misc.inc"        // timers, debug entries, FASTA text parser

@@ -113,6 +113,36 @@ class BgzfFile:
         return _read_text_host(self.filename)[0]
 
 
+class GzipTextLonger(Exception):
+    """the device declined a GzipFile (kr_genome_upload_gzip) and the host's text of the file is longer than the ISIZE word
+    len() said -- several members (`cat a.fa.gz b.fa.gz`), or a text of >= 4 GiB --: a plan made from len() does not hold.
+    The file is remembered (_GUNZIP_HOST); the caller runs again, and read_text then hands the file to the host."""
+
+    def __init__(self, filename, said, text_bytes):
+        super().__init__(f"{filename}: {text_bytes} bytes of text where its last ISIZE word says {said}")
+        self.filename = filename
+
+
+# files (path, size, mtime) whose text turned out longer than their last ISIZE word: the host path from then on
+_GUNZIP_HOST = set()
+
+
+def _file_key(path):
+    st = os.stat(path)
+    return (os.fspath(path), st.st_size, st.st_mtime_ns)
+
+
+class GzipFile(BgzfFile):
+    """a `.gz` file of (as far as its first and last bytes tell) one plain gzip member as read_text hands it to
+    ingest_on_device: the bytes as they lie on disk (`raw`) -- the device inflates them, chunk by chunk
+    (kr_genome_upload_gzip) --, len() = the ISIZE word of its last four bytes; `chunk`: KRISP_DEVICE_GUNZIP_CHUNK (None: the
+    library's choice)"""
+
+    def __init__(self, filename, raw, text_bytes, chunk=None):
+        super().__init__(filename, raw, text_bytes)
+        self.chunk = chunk
+
+
 # KRISP_DEVICE_INFLATE=0: BGZF files through the host inflate as before round 6 (A/B, tests).  A lane decodes its member
 # in ~40 ms whatever the file's size (profiles/r06/e2e_4x50Mbp.log: a 50 MB text is 800 lanes, a few of the GPU's 256 CUs --
 # 37 ms against 22 on host threads), so the device takes the files whose members occupy it: texts of KRISP_DEVICE_INFLATE_MIN
@@ -127,11 +157,44 @@ def device_inflate_min():
     return int(os.environ.get("KRISP_DEVICE_INFLATE_MIN", 1 << 28))
 
 
+# one plain gzip member (what `gzip` writes) inflated on the device (kr_genome_upload_gzip) from this many bytes of text on
+# (the ISIZE word): KRISP_DEVICE_GUNZIP_MIN.  The default is above every text the device reader takes: measured
+# (profiles/r07/gunzip_check_1024.log) the device inflates 1 GB of text at 0.55 GB/s, the chunked host inflate on 16
+# threads at 1.9 GB/s -- the route is there, opt-in, until its decode passes and window runs are faster
+DEVICE_GUNZIP_MIN = 1 << 32
+
+
+def device_gunzip_min():
+    return int(os.environ.get("KRISP_DEVICE_GUNZIP_MIN", DEVICE_GUNZIP_MIN))
+
+
+def _gzip_text_bytes(path, size):
+    """the ISIZE word of a `.gz` file that starts with a gzip header and is not BGZF, else None.  A word the compressed
+    size makes impossible is None too (deflate data is at most 8/7 of its text plus a few bytes; a file with zero padding
+    behind its trailer ends in no ISIZE word): such files keep the host path."""
+    if size < 18:
+        return None
+    try:
+        with open(path, "rb") as f:
+            head = f.read(18)
+            f.seek(size - 4)
+            isize = int.from_bytes(f.read(4), "little")
+    except OSError:
+        return None
+    if head[:3] != b"\x1f\x8b\x08" or head[3] & 0xE0 or (head[3] & 4 and head[12:14] == b"BC"):
+        return None
+    if isize < (size - 26) * 7 // 8 - 64:
+        return None
+    return isize
+
+
 def read_text(filename):
     """file -> (its text, universal_newlines): read + inflate only -- inside the library into pinned memory
     (kr_read_file) where it takes the file, else through Python's gzip / bz2.  The parse is left to the device
     (ingest_on_device).  Round 6: a `.gz` file that is BGZF all the way (bgzip: members that say how long they are) is only
-    READ here -- BgzfFile --: the device inflates it (kr_genome_upload_bgzf)."""
+    READ here -- BgzfFile --: the device inflates it (kr_genome_upload_bgzf); so is a `.gz` file of one plain gzip member
+    with at least KRISP_DEVICE_GUNZIP_MIN bytes of text -- GzipFile; kr_genome_upload_gzip.  KRISP_DEVICE_INFLATE=0: both
+    through the host."""
     if os.path.splitext(filename)[1] == ".gz" and device_inflate_on():
         size = os.path.getsize(filename)
         if 28 <= size < (1 << 32) - 64:
@@ -142,6 +205,15 @@ def read_text(filename):
                 LAST_TIMINGS[os.fspath(filename)] = dict(read_s=time.time() - t0, inflate_s=0.0, parse_s=0.0, members=0,
                                                          libdeflate=False, device_inflate=True)
                 return BgzfFile(os.fspath(filename), raw, tb), False
+            if tb is None:
+                tg = _gzip_text_bytes(filename, size)
+                if tg is not None and device_gunzip_min() <= tg < DEVICE_TEXT_MAX and _file_key(filename) not in _GUNZIP_HOST:
+                    t0 = time.time()
+                    raw = np.fromfile(filename, dtype=np.uint8)
+                    LAST_TIMINGS[os.fspath(filename)] = dict(read_s=time.time() - t0, inflate_s=0.0, parse_s=0.0, members=1,
+                                                             libdeflate=False, device_inflate=True)
+                    chunk = os.environ.get("KRISP_DEVICE_GUNZIP_CHUNK")
+                    return GzipFile(os.fspath(filename), raw, tg, int(chunk) if chunk else None), False
     return _read_text_host(filename)
 
 
@@ -216,7 +288,23 @@ def ingest_on_device(eng, gid, text, universal, k, omit_soft):
     """text of a sequence file -> genome gid of `eng`, parsed on the device with the reference reader's semantics
     (kr_genome_upload_text; the host never sees the bases unless the genome holds characters outside ACGTNacgtn:
     then they come back for the side channel of ingest()).  Returns (bases on the device, is_rna, IUPAC k-mers)."""
-    if isinstance(text, BgzfFile):
+    if isinstance(text, GzipFile):
+        got = eng.upload_gzip(gid, text.raw, chunk=text.chunk, one_shot=True)
+        if got is not None:
+            n, _nrec, nspecial, rna, _fasta, chunks, us, joined, run = got
+            tm = LAST_TIMINGS.get(text.filename)
+            if tm is not None:
+                tm.update(chunks=chunks, chunks_joined=joined, window_run=run, device_inflate_s=us * 1e-6)
+            special = scan_special(eng.fetch_bases(gid, n), k, omit_soft) if nspecial else []
+            return n, bool(rna), special
+        # (a second member, damage, scratch that does not fit: the host path, whose verdict on the file stands)
+        said, fn = len(text), text.filename
+        text = text.inflate()
+        if len(text) > said:
+            # (the caller planned the context with `said` bytes: it runs again, this file through the host from the start)
+            _GUNZIP_HOST.add(_file_key(fn))
+            raise GzipTextLonger(fn, said, len(text))
+    elif isinstance(text, BgzfFile):
         got = eng.upload_bgzf(gid, text.raw, one_shot=True)
         if got is not None:
             n, _nrec, nspecial, rna, _fasta, members, us = got

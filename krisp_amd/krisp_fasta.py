@@ -825,14 +825,27 @@ def find_regions(ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=Fa
     if not wide and os.environ.get("KRISP_HOST_PARSE") != "1":
         # files are read and inflated concurrently on the host (the library releases the GIL); the PARSE runs on the
         # device, genome by genome as the texts arrive (fasta.ingest_on_device), each followed at once by its sort
-        return _find_regions_device_ingest(files, ingroup_files, L, R, k, (Le, De, Re), omit_soft, device, verbose,
-                                           do_filter, quirk_all_fail, workers, t0)
+        while True:
+            try:
+                return _find_regions_device_ingest(files, ingroup_files, L, R, k, (Le, De, Re), omit_soft, device, verbose,
+                                                   do_filter, quirk_all_fail, workers, t0)
+            except fasta.GzipTextLonger as e:
+                # (a `.gz` file of several members handed to the device inflate: the run's plan came from its last member's
+                # length -- again from the start, that file read on the host: each round takes one more file off the device)
+                if verbose:
+                    print(f"=> {e}: again, that file inflated on the host", file=sys.stderr)
     if wide and not quirk_all_fail and os.environ.get("KRISP_HOST_PARSE") != "1":
         # round 6: amplicons longer than one key take the device's reader, too (the host's parser was the larger half of such a
         # run from files: 1.8 of 2.4 s at 8 x 500 Mbp, tools/e2e_profile.py) -- None: a genome set whose IUPAC windows make a
         # probe text longer than its genomes (tiny inputs): the host parse below
-        got = _find_regions_wide_device_ingest(files, ingroup_files, k, (Le, De, Re), omit_soft, device, verbose, do_filter,
-                                               workers, t0)
+        while True:
+            try:
+                got = _find_regions_wide_device_ingest(files, ingroup_files, k, (Le, De, Re), omit_soft, device, verbose,
+                                                       do_filter, workers, t0)
+                break
+            except fasta.GzipTextLonger as e:         # (as above)
+                if verbose:
+                    print(f"=> {e}: again, that file inflated on the host", file=sys.stderr)
         if got is not None:
             return got
     # ingest: files are read, inflated and parsed concurrently (the parser releases the GIL)
