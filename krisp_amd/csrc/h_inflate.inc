@@ -268,13 +268,13 @@ static int inflate_bgzf(const uint8_t* in, size_t n, RawBuf& out, int64_t* membe
             const Mem& M = mem[m];
             if (d) {
                 size_t ain = 0, aout = 0;
-                good = ld.gzip_ex(d, in + M.at, M.len, dst + M.oat, M.isize, &ain, &aout) == 0 && aout == M.isize;
+                good = ld.gzip_ex(d, in + M.at, M.len, dst + M.oat, M.isize, &ain, &aout) == 0 && aout == M.isize && ain == M.len;
             } else {
                 zs.next_in = (Bytef*)(in + M.at);
                 zs.avail_in = (uInt)M.len;
                 zs.next_out = dst + M.oat;
                 zs.avail_out = M.isize;
-                good = inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0;
+                good = inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0 && zs.avail_in == 0;
                 inflateReset(&zs);
             }
         }

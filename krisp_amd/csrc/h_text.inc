@@ -25,7 +25,28 @@ static bool kr_spawn(std::vector<std::thread>& th, A&&... a) {
 }
 }   // extern "C++"
 #endif
-static inline bool is_space(uint8_t c) { return c == ' ' || (c >= 9 && c <= 13); }
+// White space as the reference's str.strip() sees it on its decoded (UTF-8) lines: the ASCII bytes 9-13, 28-31 and ' ',
+// and 19 characters above U+007F -- U+0085, U+00A0 (two bytes), U+1680, U+2000-U+200A, U+2028, U+2029, U+202F, U+205F,
+// U+3000 (three).  Matched as byte sequences: in UTF-8 a lead byte is never a continuation byte, so a match at either end
+// of a line is a whole character.  (Text that is not UTF-8 makes the reference fail; nothing here decodes.)
+static inline bool is_space(uint8_t c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31); }
+static inline bool is_space2(uint8_t a, uint8_t b) { return a == 0xc2 && (b == 0x85 || b == 0xa0); }
+static inline bool is_space3(uint8_t a, uint8_t b, uint8_t c) {
+    if (a == 0xe2) return (b == 0x80 && (c <= 0x8a || c == 0xa8 || c == 0xa9 || c == 0xaf)) || (b == 0x81 && c == 0x9f);
+    return (a == 0xe1 && b == 0x9a && c == 0x80) || (a == 0xe3 && b == 0x80 && c == 0x80);
+}
+// bytes of the white space character at the start / end of [p, p + len); 0: none
+static inline size_t space_head(const uint8_t* p, size_t len) {
+    if (p[0] < 0x80) return is_space(p[0]) ? 1 : 0;
+    if (len >= 2 && is_space2(p[0], p[1])) return 2;
+    return len >= 3 && is_space3(p[0], p[1], p[2]) ? 3 : 0;
+}
+static inline size_t space_tail(const uint8_t* p, size_t len) {
+    const uint8_t* e = p + len;
+    if (e[-1] < 0x80) return is_space(e[-1]) ? 1 : 0;
+    if (len >= 2 && is_space2(e[-2], e[-1])) return 2;
+    return len >= 3 && is_space3(e[-3], e[-2], e[-1]) ? 3 : 0;
+}
 
 int64_t kr_fasta_to_bases(const uint8_t* text, size_t n, int universal_newlines, int one_shot, uint8_t* out,
                           size_t cap, int64_t* stats) {
@@ -64,8 +85,8 @@ int64_t kr_fasta_to_bases(const uint8_t* text, size_t n, int universal_newlines,
             fasta = memchr(ln, '>', len) != nullptr;         // decided on the first line only
             if (one_shot) continue;                          // ... which the detection consumed
         }
-        while (len && is_space(ln[0])) { ln++; len--; }
-        while (len && is_space(ln[len - 1])) len--;
+        for (size_t k; len && (k = space_head(ln, len));) { ln += k; len -= k; }
+        for (size_t k; len && (k = space_tail(ln, len));) len -= k;
         if (!fasta) {                                        // every stripped line is a record
             emit_separator();
             memcpy(out + o, ln, len);

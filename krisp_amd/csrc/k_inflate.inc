@@ -268,6 +268,8 @@ __global__ __launch_bounds__(BGZ_T) void k_bgzf_inflate(const uint8_t* __restric
         }
         if (err == BGZ_OK && b.used() > in_bits) err = BGZ_E_IN;
     }
+    // the trailer follows the stream's last byte (Python's gzip reads it there): spare bytes in front of it are damage too
+    if (err == BGZ_OK && (b.used() + 7) / 8 != (u64)M.in_len) err = BGZ_E_IN;
     if (err == BGZ_OK && o != nout) err = BGZ_E_LEN;
     status[m] = (u32)err;
 }

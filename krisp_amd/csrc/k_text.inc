@@ -1,8 +1,9 @@
 // k_text.inc -- part of krisp_hip.hip (one translation unit): the reference reader on the device (SURVEY 8f rank 1).
 // File text (FASTA, or one sequence per line) -> the upload buffer: record bodies joined by one '\n', with exactly the
 // semantics of kr_fasta_to_bases (h_text.inc; kstream.py:458-583): the first line decides FASTA mode (and is consumed
-// when the text comes from a file), lines are stripped of white space at both ends, header lines start a record, empty
-// lines and empty records vanish (FASTA) / every line is a record (plain).  The host then only reads and inflates.
+// when the text comes from a file), lines are stripped of white space at both ends (str.strip()'s, in UTF-8), header lines
+// start a record, empty lines and empty records vanish (FASTA) / every line is a record (plain).  The host then only reads
+// and inflates.
 //   k_tx_firstline     FASTA mode: a '>' anywhere in the first line
 //   k_tx_starts_*      line starts (p = 0, after '\n', after a lone '\r' under universal newlines) -> linestart[]
 //   k_tx_lineinfo      per line: stripped body [s, s + len), what the line does to the record state
@@ -14,7 +15,27 @@ struct TxState {           // device words of one parse (read back through the h
     u32 fasta, nlines, nout, nrec, special, pT, pU, q, rna, ucount;
 };
 
-__device__ __forceinline__ bool tx_space(u32 c) { return c == ' ' || (c >= 9 && c <= 13); }
+// white space as the reference's str.strip() sees it (is_space / space_head / space_tail of h_text.inc): ASCII 9-13, 28-31,
+// ' ', and the UTF-8 forms of U+0085, U+00A0, U+1680, U+2000-U+200A, U+2028, U+2029, U+202F, U+205F, U+3000
+__device__ __forceinline__ bool tx_space(u32 c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31); }
+__device__ __forceinline__ bool tx_space2(u32 a, u32 b) { return a == 0xc2 && (b == 0x85 || b == 0xa0); }
+__device__ __forceinline__ bool tx_space3(u32 a, u32 b, u32 c) {
+    if (a == 0xe2) return (b == 0x80 && (c <= 0x8a || c == 0xa8 || c == 0xa9 || c == 0xaf)) || (b == 0x81 && c == 0x9f);
+    return (a == 0xe1 && b == 0x9a && c == 0x80) || (a == 0xe3 && b == 0x80 && c == 0x80);
+}
+// bytes of the white space character at the start / end of [s, e) (s < e); 0: none
+__device__ __forceinline__ u32 tx_space_head(const uint8_t* __restrict__ t, u32 s, u32 e) {
+    const u32 c = t[s];
+    if (c < 0x80) return tx_space(c) ? 1u : 0u;
+    if (e - s >= 2 && tx_space2(c, t[s + 1])) return 2;
+    return e - s >= 3 && tx_space3(c, t[s + 1], t[s + 2]) ? 3u : 0u;
+}
+__device__ __forceinline__ u32 tx_space_tail(const uint8_t* __restrict__ t, u32 s, u32 e) {
+    const u32 c = t[e - 1];
+    if (c < 0x80) return tx_space(c) ? 1u : 0u;
+    if (e - s >= 2 && tx_space2(t[e - 2], c)) return 2;
+    return e - s >= 3 && tx_space3(t[e - 3], t[e - 2], c) ? 3u : 0u;
+}
 // is byte position p the start of a line?  (universal newlines: '\n', '\r' and "\r\n" all end a line)
 __device__ __forceinline__ bool tx_is_start(const uint8_t* __restrict__ t, u64 p, int universal) {
     if (p == 0) return true;
@@ -94,8 +115,8 @@ __global__ __launch_bounds__(256) void k_tx_lineinfo(const uint8_t* __restrict__
     const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nlines) return;
     u32 s = linestart[j], e = j + 1 < nlines ? linestart[j + 1] : n;
-    while (s < e && tx_space(t[s])) s++;
-    while (e > s && tx_space(t[e - 1])) e--;
+    for (u32 k; s < e && (k = tx_space_head(t, s, e));) s += k;
+    for (u32 k; e > s && (k = tx_space_tail(t, s, e));) e -= k;
     u32 o;
     if (j == 0 && one_shot) { o = 0; e = s; }
     else if (!st->fasta) o = 3;

@@ -6,7 +6,7 @@ Mirrors the reference's reader semantics exactly (kstream/kstream.py:430-583):
   * that first line is consumed by the detection when the input is a file or a
     one-shot iterator (kstream.py:450 rebinds the re-chained stream to an unused
     name) -- harmless for a FASTA header, a lost sequence otherwise;
-  * lines are strip()ped and concatenated between headers, empty records dropped
+  * lines are strip()ped (str.strip()'s white space, in UTF-8) and concatenated between headers, empty records dropped
     (kstream.py:556-583); non-FASTA input: one sequence per stripped line;
   * RNA iff the first record holding T/t/U/u holds U/u first (kstream.py:481-508).
 The output is what kr_genome_upload takes: ASCII bases, '\\n' between records.
@@ -25,6 +25,31 @@ _IUPAC = frozenset("RYMKSWBVDHrymkswbvdh")
 _PLAIN = np.zeros(256, dtype=bool)
 for _ch in b"ACGTNacgtn\n":
     _PLAIN[_ch] = True
+
+
+# white space as the reference's str.strip() sees it on its decoded (UTF-8) lines: ASCII 9-13, 28-31 and ' ', and the
+# UTF-8 forms of the 19 characters above U+007F (str.isspace()).  Stripped as bytes, as both C parsers do (h_text.inc
+# space_head / space_tail, k_text.inc): a lead byte is never a continuation byte, so a match at a line's end is a whole
+# character; text that is not UTF-8 (the reference fails on it) is not decoded.
+_WS_ASCII = bytes([9, 10, 11, 12, 13, 28, 29, 30, 31, 32])
+_WS_UTF8 = tuple(chr(c).encode() for c in (0x85, 0xA0, 0x1680, *range(0x2000, 0x200B), 0x2028, 0x2029, 0x202F, 0x205F,
+                                            0x3000))
+
+
+def strip_line(ln):
+    """bytes.strip() with the white space of str.strip() (see _WS_UTF8)"""
+    ln = ln.strip(_WS_ASCII)
+    while ln and ln[0] >= 0x80:
+        w = next((w for w in _WS_UTF8 if ln.startswith(w)), None)
+        if w is None:
+            break
+        ln = ln[len(w):].lstrip(_WS_ASCII)
+    while ln and ln[-1] >= 0x80:
+        w = next((w for w in _WS_UTF8 if ln.endswith(w)), None)
+        if w is None:
+            break
+        ln = ln[:-len(w)].rstrip(_WS_ASCII)
+    return ln
 
 
 # texts the device's reader (kr_genome_upload_text) takes; KRISP_DEVICE_TEXT_MAX: tests force the host-parse fallback
@@ -58,10 +83,10 @@ def read_records(source):
     if one_shot:
         lines = lines[1:]
     if not fasta:
-        return [ln.strip() for ln in lines]
+        return [strip_line(ln) for ln in lines]
     recs, cur = [], []
     for ln in lines:
-        ln = ln.strip()
+        ln = strip_line(ln)
         if ln.startswith(b">"):
             if cur:
                 recs.append(b"".join(cur))
@@ -377,19 +402,19 @@ def sniff_rna(filename, chunk=1 << 16):
         tail, first, fasta, saw_u = b"", True, False, False
         while True:
             buf = f.read(chunk)
-            data = tail + buf
+            data, carry = tail + buf, b""
             if universal:
-                data = data.replace(b"\r\n", b"\n").replace(b"\r", b"\n") if not (buf and data.endswith(b"\r")) else data
+                if buf and data.endswith(b"\r"):
+                    data, carry = data[:-1], b"\r"     # (a CR at the chunk edge may be half of a CRLF: stays in the tail)
+                data = data.replace(b"\r\n", b"\n").replace(b"\r", b"\n")
             lines = data.split(b"\n")
-            tail = lines.pop() if buf else b""
-            if universal and buf and tail.endswith(b"\r"):
-                pass                                    # (a lone CR at the chunk edge may be half of CRLF: stays in the tail)
+            tail = lines.pop() + carry if buf else b""
             for ln in lines:
                 if first:
                     fasta = b">" in ln
                     first = False
                     continue                            # (consumed by the detection, kstream.py:450)
-                ln = ln.strip()
+                ln = strip_line(ln)
                 header = fasta and ln.startswith(b">")
                 if header or not fasta:
                     if saw_u:                           # the record that held U ended without a T

@@ -777,7 +777,123 @@ def fasta_cases_r6():
     return cases
 
 
+# --------------------------------------------------------------------------
+# 3. the reader alone: file / list -> records, FASTA and RNA verdicts
+# --------------------------------------------------------------------------
+# the 29 code points str.strip() removes (str.isspace())
+WHITE = [chr(c) for c in range(0x110000) if chr(c).isspace()]
+
+
+def run_reader(text, source):
+    """the reference's reader chain as kstream.__call__ runs it (kstream.py:444-456) and the RNA detection
+    (kstream.py:481-508) over its records.  source: 'in.fa' (text mode, universal newlines), 'in.fa.gz' (a gzip file --
+    see reader_cases for the texts it leaves out) or 'list' (the text's lines, '\\n'-split, as an in-memory list of str)"""
+    ks = kstream()
+    with tempfile.TemporaryDirectory() as td:
+        if source == "list":
+            sequences = text.split("\n")
+        else:
+            path = os.path.join(td, source)
+            with (gzip.GzipFile(path, "wb", mtime=0) if source.endswith(".gz") else open(path, "wb")) as f:
+                f.write(text.encode())
+            sequences = ks._read_file(path)
+        is_fasta, _ = ks._detect_FASTA(sequences)
+        recs = list(ks._parse_FASTA(sequences) if is_fasta else ks._parse_seqs(sequences))
+    rna, _ = ks._detect_RNA(iter(recs))
+    return {"records": recs, "fasta": is_fasta, "rna": rna}
+
+
+def reader_cases():
+    """white space as str.strip() sees it, around and inside sequence lines, header lines and otherwise empty lines,
+    FASTA and not, from a plain file, a gzip file and a list; written to reader_cases.json"""
+    texts = []
+    for i, w in enumerate(WHITE):
+        v = WHITE[(i * 7 + 3) % len(WHITE)]
+        texts.append((f"fasta_{ord(w):04x}",
+                      f">h{w}\n{w}ACGT{w}\n{w} AC{w}GT\t{v}\n{w}\n{v}{w} {w}\n{w}>x{w}\n{w}TTU{w}{v}\n{w}{w}\n"
+                      f">y\nGG{w}\n>z\n{w}\n>u\n{v}UUCA\n"))
+        texts.append((f"plain_{ord(w):04x}", f"{w}first{w}\n{w}ACGT{w}\nAC{w}GT\n{w}\n\t{w}{v}UU{w}\n{w}TT"))
+        texts.append((f"rna_{ord(w):04x}", f">a{w}\n{w}\n{w}UUAC{w}\n>b\n{w}GGT{w}\n"))
+    # next to real line breaks (text mode splits on \n, \r and \r\n only; the binary lines on \n)
+    for w in ("\x85", "\u2028", "\u2029", "\x1c", "\x1d", "\x1e", "\x0b", "\x0c"):
+        texts.append((f"breaks_{ord(w):04x}", f">h\nAC{w}\nGT{w}\r\n{w}\rAA{w}\r{w}CC\n{w}\n\r\nGG{w}\n>x{w}\r\n{w}TT\r"))
+        texts.append((f"breaks_plain_{ord(w):04x}", f"x{w}\r\n{w}AC{w}\rGT\n{w}{w}\r\nTT{w}"))
+    # the issue's text: a record of white space only, a no-break space after the sequence
+    texts.append(("issue_example", ">h\n\x1cACGT\x1f\nAC\xa0\n\x0bGG\n>x\n\x1d\n>y\nTT\n"))
+    rng = random.Random(20261015)
+    ascii_ws = [w for w in WHITE if ord(w) < 128]
+    for i in range(160):
+        lines = []
+        for _ in range(rng.randint(0, 14)):
+            pre = "".join(rng.choice(WHITE) for _ in range(rng.choice([0, 0, 1, 2, 3])))
+            post = "".join(rng.choice(WHITE) for _ in range(rng.choice([0, 0, 1, 2, 3])))
+            kind = rng.random()
+            if kind < 0.25:
+                body = ">" + "".join(rng.choice(["a", "b", " ", ">"] + WHITE) for _ in range(rng.randint(0, 5)))
+            elif kind < 0.4:
+                body = ""
+            else:
+                body = "".join(rng.choice(["A", "C", "G", "T", "U", "a", "u", "N", ">"] + WHITE[:3] + WHITE[-3:])
+                               for _ in range(rng.randint(0, 20)))
+            lines.append(pre + body + post)
+        nl = rng.choice(["\n", "\r\n", "\r", "\n"])
+        text = nl.join(lines) + rng.choice(["", nl, nl + rng.choice(ascii_ws)])
+        texts.append((f"random{i}", text))
+    cases = []
+    for name, text in texts:
+        for source in ("in.fa", "in.fa.gz", "list"):
+            # (a '\r' that is not part of a '\r\n': a line break in a .gz file where fileinput wraps the stream in text
+            # mode -- Python >= 3.10 --, inside the line where it hands over binary lines; the readers here take the
+            # binary lines.  Such texts are pinned for plain files and lists only.)
+            if source.endswith(".gz") and "\r" in text.replace("\r\n", ""):
+                continue
+            cases.append({"name": f"{name}_{source.replace('.', '_')}", "text": text, "source": source,
+                          **run_reader(text, source)})
+    return cases
+
+
+def white_fasta_text(rng, records, width=60):
+    """fasta_text with white space of every kind (str.strip()'s) at the ends of the lines, and lines of white space only"""
+    def pad():
+        return "".join(rng.choice(WHITE) for _ in range(rng.choice([0, 1, 1, 2, 3])))
+    o = []
+    for i, s in enumerate(records):
+        o.append(f"{pad()}>rec{i}{pad()}")
+        for j in range(0, len(s), width):
+            o.append(pad() + s[j:j + width] + pad())
+            if rng.random() < 0.1:
+                o.append(pad())
+    return ("\n".join(o) + "\n").encode()
+
+
+def white_fasta_case():
+    """krisp_fasta over genomes whose lines carry white space of every kind: two in-group and one out-group genome"""
+    rng = random.Random(20261016)
+    L, D, R = 8, 1, 6
+    anc = ["".join(rng.choice("ACGT") for _ in range(400)) for _ in range(2)]
+    plants = [(r, rng.randrange(20, 380)) for r in range(2) for _ in range(3)]
+    files = {}
+    for gi, fn in enumerate(["inW0.fa", "inW1.fasta", "outW.fa"]):
+        recs = []
+        for r, s in enumerate(anc):
+            m = list(mutate(rng, s, 0.01))
+            for pr, pos in plants:
+                if pr == r:
+                    m[pos] = "G" if gi < 2 else "T"
+            recs.append("".join(m))
+        files[fn] = white_fasta_text(rng, recs)
+    c = run_fasta_case("white_space_8_1_6", files, ["inW0.fa", "inW1.fasta"], ["outW.fa"], L, D, R)
+    c["files"] = {fn: v.decode() for fn, v in files.items()}
+    return c
+
+
 def main():
+    if "--reader-only" in sys.argv:
+        rc = reader_cases()
+        with open(HERE / "reader_cases.json", "w") as f:
+            json.dump(rc, f, indent=1)
+        print(f"reader cases: {len(rc)}")
+        return
     if "--ks6-only" in sys.argv:
         k6 = kstream_cases_r6()
         with open(HERE / "kstream_cases_r6.json", "w") as f:
@@ -811,7 +927,11 @@ def main():
     with open(HERE / "kstream_cases.json", "w") as f:
         json.dump(ks, f, indent=1)
     print(f"kstream cases: {len(ks)}")
-    fc = fasta_cases()
+    rc = reader_cases()
+    with open(HERE / "reader_cases.json", "w") as f:
+        json.dump(rc, f, indent=1)
+    print(f"reader cases: {len(rc)}")
+    fc = fasta_cases() + [white_fasta_case()]
     with open(HERE / "fasta_cases.json", "w") as f:
         json.dump(fc, f, indent=1)
     print(f"krisp_fasta cases: {len(fc)}")

@@ -19,6 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 KS = json.load(open(os.path.join(GOLDEN, "kstream_cases.json")))
 FC = json.load(open(os.path.join(GOLDEN, "fasta_cases.json")))
+RC = json.load(open(os.path.join(GOLDEN, "reader_cases.json")))
+# the 29 code points str.strip() removes
+WHITE = [chr(c) for c in range(0x110000) if chr(c).isspace()]
 
 
 def _src(case, tmp_path):
@@ -382,13 +385,46 @@ def test_missing_library_fails_loudly(monkeypatch):
         _native.Engine()
 
 
+@pytest.mark.parametrize("case", RC, ids=[c["name"] for c in RC])
+def test_readers_strip_white_space_as_the_reference_reader(case, tmp_path):
+    """every reader against the reference's reader chain run over the same text (reader_cases.json): str.strip()'s 29
+    white space characters (ASCII 9-13, 28-31, ' ' and 19 above U+007F, in UTF-8) at the ends of sequence, header and
+    otherwise empty lines are stripped, inside a line kept; U+0085 / U+2028 next to line breaks do not break lines.
+    The oracle, fasta.read_records, the library's host parser (fasta.load_bases, kr_fasta_to_bases) and
+    fasta.sniff_rna: the same records, FASTA and RNA verdicts."""
+    text, want, rna = case["text"], case["records"], case["rna"]
+    if case["source"] == "list":
+        src = text.split("\n")
+        assert O.parse_records(src, one_shot=False) == want
+        assert [r.decode() for r in fasta.read_records(src)] == want
+        assert O.detect_rna(want) == rna
+        return
+    src = str(tmp_path / case["source"])
+    with (gzip.open if src.endswith(".gz") else open)(src, "wb") as f:
+        f.write(text.encode())
+    assert O.parse_records(O.read_lines(src)) == want
+    assert O.detect_rna(want) == rna
+    recs = fasta.read_records(src)
+    assert [r.decode() for r in recs] == want
+    assert fasta.detect_rna(recs) == rna
+    assert fasta.sniff_rna(src) == rna
+    assert fasta.sniff_rna(src, chunk=3) == rna         # (chunk edges inside CRLF pairs and UTF-8 characters)
+    wbases = fasta.to_bases([r.encode() for r in want], bool(rna))
+    bases, got_rna, nspecial = fasta.load_bases(src)
+    assert bases.tobytes() == wbases.tobytes()
+    assert got_rna == bool(rna)
+    assert nspecial == int((~fasta._PLAIN[wbases]).sum())
+    _, nrec, _, _, fa = _native.fasta_to_bases(text.encode(), not src.endswith(".gz"), one_shot=True)
+    assert (nrec, bool(fa)) == (len(want), bool(case["fasta"]))
+
+
 def test_library_ingest_matches_the_python_reader(tmp_path):
     """kr_fasta_to_bases (one-pass host parser in the library) == to_bases(read_records(...)),
     the reader that is itself pinned to the reference (test above): headers, blank and indented
     lines, CR/LF flavours, gzip, RNA, non-FASTA inputs, first-line consumption."""
     import random
 
-    def check(path):
+    def check(path, oracle=False):
         recs = fasta.read_records(path)
         rna = bool(fasta.detect_rna(recs))
         want = fasta.to_bases(recs, rna)
@@ -396,6 +432,10 @@ def test_library_ingest_matches_the_python_reader(tmp_path):
         assert got.tobytes() == want.tobytes(), path
         assert r == rna
         assert nspecial == int((~fasta._PLAIN[want]).sum())
+        if oracle:                  # ... and both against the oracle's reader (str lines, str.strip())
+            orecs = O.parse_records(O.read_lines(path))
+            assert [x.decode() for x in recs] == orecs, path
+            assert rna == bool(O.detect_rna(orecs))
 
     for c in KS:
         if c["file_text"] is not None:
@@ -410,17 +450,18 @@ def test_library_ingest_matches_the_python_reader(tmp_path):
             if kind < 0.25:
                 pieces.append(">" + "".join(rng.choice("abc >x") for _ in range(rng.randint(0, 6))))
             elif kind < 0.35:
-                pieces.append(rng.choice(["", " ", "\t"]))
+                pieces.append(rng.choice(["", " ", "\t"] + WHITE))
             else:
-                pieces.append(rng.choice(["", " ", "  "]) +
-                              "".join(rng.choice("ACGTacgtNnUuRY>x ") for _ in range(rng.randint(0, 30))) +
-                              rng.choice(["", " ", "\t "]))
+                # (str.strip()'s white space of every kind at the ends and inside)
+                pieces.append(rng.choice(["", " ", "  "] + WHITE) +
+                              "".join(rng.choice(list("ACGTacgtNnUuRY>x ") + WHITE) for _ in range(rng.randint(0, 30))) +
+                              rng.choice(["", " ", "\t "] + WHITE))
         nl = rng.choice(["\n", "\r\n", "\r", "\n"])
         text = nl.join(pieces) + rng.choice(["", nl, nl + nl])
         for ext in (".fa", ".txt.gz"):
             p = str(tmp_path / f"r{i}{ext}")
             (gzip.open if ext.endswith(".gz") else open)(p, "wb").write(text.encode())
-            check(p)
+            check(p, oracle=True)
 
 
 def _brute_wide_hits(texts, flags, L, D, R, omit, do_filter):
@@ -1047,3 +1088,25 @@ def test_window_renderer_equals_the_general_path():
             assert amplicon.render(wg, ingroup, dot) == want, (L, D, R, labels, ingroup, dot)
             same += 1
     assert same > 250 and declined > 20
+
+
+@pytest.mark.parametrize("spare", [1, 3])
+def test_host_inflate_refuses_bgzf_members_with_spare_bytes_before_the_trailer(spare, tmp_path):
+    """a BGZF member whose BSIZE leaves bytes between the end of its deflate stream and its trailer: Python's gzip reads
+    the trailer right after the stream and fails; so does the library's host inflate"""
+    import struct
+    import zlib
+    text = b">r\n" + b"ACGTTGCA" * 9000 + b"\n"
+    out = []
+    for ch in (text[:30000], text[30000:], b""):
+        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        cd = co.compress(ch) + co.flush() + (b"\x00\x07\x03"[:spare] if ch else b"")
+        out.append(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(cd) + 25) + cd
+                   + struct.pack("<II", zlib.crc32(ch) & 0xFFFFFFFF, len(ch)))
+    p = str(tmp_path / "spare.fa.gz")
+    with open(p, "wb") as f:
+        f.write(b"".join(out))
+    with pytest.raises(Exception):
+        gzip.decompress(open(p, "rb").read())
+    with pytest.raises(Exception):
+        fasta.load_bases(p)
