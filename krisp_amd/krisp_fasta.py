@@ -20,6 +20,7 @@ import os
 import sys
 import time
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -352,37 +353,122 @@ RESERVE_MIN = 128 << 20      # bytes of file text from which the context's memor
 STREAM_MIN = 1 << 30         # ... and from which the files are read one after the other, each on all host threads
 
 
-def _find_regions_device_ingest(files, ingroup_files, L, R, k, geo, omit_soft, device, verbose, do_filter, quirk_all_fail,
-                                workers, t0):
+class _Run(NamedTuple):
+    """one find_regions run (or one rank's share of a distributed run) as its flows see it"""
+    geo: tuple                  # (L, D, R) after codec.effective_geometry
+    k: int
+    do_filter: bool
+    quirk_all_fail: bool
+    wide: bool                  # amplicons longer than one key: kr_wide_run
+    labels: list                # one per genome, in the flow's file order
+    ingroup_labels: frozenset
+    flags: list                 # ingroup or not, per genome
+    omit_soft: bool
+    device: int
+    verbose: bool
+    workers: int                # host threads that read the files
+    t0: float
+
+
+def _describe_run(labels, ingroup_files, L, R, k, omit_soft, device, verbose, wide=None):
+    """the run's description; a geometry no flow carries raises UnsupportedGeometry here, before a file is read"""
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    # the reference filters whenever k > L + R (krisp_fasta.py:265); with R == 0 the
+    # diagnostic column is empty (kstream.py:824-830) and every group fails the filter
+    do_filter = k > L + R
+    quirk_all_fail = do_filter and De == 0
+    if wide is None:                 # (tests force the wide path on packable geometries)
+        wide = _is_wide(Le, De, Re)
+    if wide and not quirk_all_fail:
+        _check_wide(Le, De, Re)
+    elif not wide:
+        _check_geometry(Le, De, Re)
+    # ingroup / outgroup by LABEL, as the reference classifies (Amplicon.py:495-521): an outgroup file whose label
+    # equals an ingroup label counts as ingroup
+    ingroup_labels = frozenset(simplename(f) for f in ingroup_files)
+    return _Run((Le, De, Re), k, do_filter, quirk_all_fail, wide, labels, ingroup_labels,
+                [lab in ingroup_labels for lab in labels], omit_soft, device, verbose,
+                max(1, min(len(labels), os.cpu_count() or 1, 16)), time.time())
+
+
+def _engine(device):
+    """a context under KRISP_HBM_BUDGET (bytes; tests and shared devices: kr_create's HBM budget)"""
+    from . import _native
+    return _native.Engine(device=device, hbm_budget=int(os.environ.get("KRISP_HBM_BUDGET", "0")))
+
+
+def _ingest_genome(eng, g, text, universal, run):
+    """the text of one file -> genome g of `eng`, parsed on the device (fasta.ingest_on_device).  A packed run sorts it
+    at once, while the files behind it still inflate (kr_wide_run sorts inside).
+    -> (bases on the device, is RNA, its IUPAC windows as (left, diag, right))"""
+    n, rna, sp = fasta.ingest_on_device(eng, g, text, universal, run.k, run.omit_soft)
+    specials = [codec.split_window(w, *run.geo) for w in sp]
+    if not run.wide:
+        eng.sort(g)
+    return n, rna, specials
+
+
+def _packed_result(records, run, rna, touched, sgroups, stats):
+    """a packed run's records (collected in label order) and the groups IUPAC windows touch (rebuilt on the host:
+    sgroups) -> (groups, stats).  rna: the reader's verdict per genome (the streaming flow's fasta.sniff_rna gives the
+    same: tests/test_host_glue.py)"""
+    if run.quirk_all_fail:
+        return [], stats
+    Le, De, Re = run.geo
+    if any(rna) and not all(rna):
+        groups = _mixed_finish(records, run.labels, run.geo, rna, run.ingroup_labels, run.do_filter)
+        if touched:
+            groups = _merge_groups(groups, touched, sgroups)
+        stats["candidates"] = len(groups)
+        return groups, stats
+    if not touched and not any(rna):
+        # (plain records: the renderer works from them directly, the list of groups is built only if someone walks it)
+        return amplicon.RecordGroups(records, run.labels, Le, De, Re), stats
+    groups = amplicon.groups_from_records(records, run.labels, Le, De, Re)
+    if touched:
+        groups = _merge_groups(groups, touched, sgroups)
+    return (_to_rna(groups) if all(rna) else groups), stats
+
+
+def _touched_pairs(specials, D):
+    """the (left,right) pairs IUPAC windows touch, those of them with plain flanks, and the probe genome made of these
+    (left + A..A + right, a record each: _wide_probe_members)"""
+    touched = {(l, r) for sp in specials for (l, d, r) in sp}
+    probes = sorted(p for p in touched if _pure(p[0]) and _pure(p[1]))
+    return touched, probes, np.frombuffer("\n".join(l + "A" * D + r for l, r in probes).encode(), dtype=np.uint8)
+
+
+def _mixed_wide_groups(groups, run):
+    """wide groups of a run that mixes DNA and RNA genomes: text decides -- flank pairs that hold T / U are in no DNA
+    genome and RNA genome alike, and the filter's columns are compared letter by letter (_mixed_finish's rule on member
+    windows)"""
+    groups = [g for g in groups if not (set(g[0].left + g[0].right) & set("TU"))]
+    if run.do_filter and run.ingroup_labels:
+        groups = [g for g in groups if amplicon.ingroup_unique_columns(g, run.ingroup_labels)]
+    return groups
+
+
+def _find_regions_device_ingest(files, run):
     """find_regions' packed path; a genome set the plan thought would fit and the device then could not hold (the plan
     is an estimate: candidate lists, slices of a skewed genome, another process on the device) is run again in batches"""
     from . import _native
     try:
-        return _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, verbose, do_filter, quirk_all_fail,
-                                   workers, t0, None)
+        return _device_ingest_flow(files, run, None)
     except _native.KrispHipError as e:
         if e.code != _native.ERR_CAPACITY or len(files) < 2 or os.environ.get("KRISP_STREAM_BATCH"):
             raise
-        if verbose:
+        if run.verbose:
             print(f"=> the genome set does not fit the device at once ({e}): in batches", file=sys.stderr)
-    return _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, verbose, do_filter, quirk_all_fail,
-                               workers, t0, (len(files) + 1) // 2)
+    return _device_ingest_flow(files, run, (len(files) + 1) // 2)
 
 
-def _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, verbose, do_filter, quirk_all_fail,
-                        workers, t0, force_batch):
+def _device_ingest_flow(files, run, force_batch):
     """find_regions' packed path with the reader on the device: the host threads read and inflate, the main thread
-    hands each text to the GPU (parse -> sort) as it arrives.  Same results as the host-parse flow (the device reader
-    equals kr_fasta_to_bases byte for byte: tests/test_gpu_kernels.py)."""
+    hands each text to the GPU (parse -> sort) as it arrives (the device reader equals kr_fasta_to_bases byte for byte:
+    tests/test_gpu_kernels.py)."""
     from concurrent.futures import ThreadPoolExecutor
     from . import _native
-    Le, De, Re = geo
-    if len(files) == 1:
-        labels = ["merged_file"]
-    else:
-        labels = [simplename(f) for f in files]
-    ingroup_labels = frozenset(simplename(f) for f in ingroup_files)
-    flags = [lab in ingroup_labels for lab in labels]
+    Le, De, Re = run.geo
     try:
         est = max(fasta.estimate_text_bytes(f) for f in files)
     except OSError:
@@ -391,33 +477,19 @@ def _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, v
     # files whose inflate takes every host thread by itself (one large gzip member, a bz2 stream of many blocks) are read
     # one after the other: the first genome is parsed and sorted on the device while the second still inflates
     # (plain text files use no inflate threads: they keep their readers side by side -- ADVICE r4)
+    workers = run.workers
     if ahead and est >= int(os.environ.get("KRISP_STREAM_MIN", STREAM_MIN)) and \
             any(str(f).lower().endswith((".gz", ".bz2", ".bgz")) for f in files):
         workers = 1
-    budget = int(os.environ.get("KRISP_HBM_BUDGET", "0"))       # (bytes; tests and shared devices: kr_create's HBM budget)
-    with ThreadPoolExecutor(max_workers=workers) as pool, _native.Engine(device=device, hbm_budget=budget) as eng:
-        # a genome set the device cannot hold sorted at once goes through it in batches (the streaming flow above)
+    with ThreadPoolExecutor(max_workers=workers) as pool, _engine(run.device) as eng:
+        # a genome set the device cannot hold sorted at once goes through it in batches (the streaming flow below)
         batch = force_batch or (_plan_batch(eng, len(files), est) if len(files) > 1 else None)
         if batch is not None:
             t1 = time.time()
-            eng.set_params(Le, De, Re, omit_soft=omit_soft, max_bases=max(est, 1))
-            records, touched, sgroups, all_rna, stats = _find_regions_streaming(
-                eng, pool, files, labels, flags, k, geo, omit_soft, verbose, do_filter, quirk_all_fail, batch, t0, max(est, 1))
+            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=max(est, 1))
+            records, rna, touched, sgroups, stats = _find_regions_streaming(eng, pool, files, run, batch, max(est, 1))
             stats["device_s"] = time.time() - t1
-            if quirk_all_fail:
-                return [], stats
-            if stats.get("mixed_rna"):
-                groups = _mixed_finish(records, labels, (Le, De, Re), stats["mixed_rna"], ingroup_labels, do_filter)
-                if touched:
-                    groups = _merge_groups(groups, touched, sgroups)
-                stats["candidates"] = len(groups)
-                return groups, stats
-            if not touched and not all_rna:
-                return amplicon.RecordGroups(records, labels, Le, De, Re), stats
-            groups = amplicon.groups_from_records(records, labels, Le, De, Re, rna=False)
-            if touched:
-                groups = _merge_groups(groups, touched, sgroups)
-            return (_to_rna(groups) if all_rna else groups), stats
+            return _packed_result(records, run, rna, touched, sgroups, stats)
         futures = [pool.submit(fasta.read_text, f) for f in files]
         # large genomes: the context gets its memory (device memory another process has just given back takes the driver 15-40 ms per GB to hand over: seconds at 3 Gbp) while the
         # host threads read and inflate -- planned from the files' sizes, planned again below if they said too little
@@ -429,10 +501,10 @@ def _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, v
             # texts once they are read
             planned = est
             try:
-                eng.set_params(Le, De, Re, omit_soft=omit_soft, max_bases=planned)
+                eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=planned)
                 eng.reserve(list(range(len(files))), planned, with_text=True)
             except _native.KrispHipError as e:
-                if verbose:
+                if run.verbose:
                     print(f"=> memory plan for {planned:,} bases per genome not taken ({e}): sizing from the texts instead", file=sys.stderr)
                 for i in range(len(files)):
                     try:
@@ -445,14 +517,13 @@ def _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, v
         for i, fu in enumerate(futures):
             text, universal = fu.result()
             if t1 is None:
-                read_s = time.time() - t0           # (until the first text is there: from then on the device has work)
+                read_s = time.time() - run.t0       # (until the first text is there: from then on the device has work)
                 t1 = time.time()
             if planned and len(text) <= planned and not first:
                 # the plan stands: this genome goes to the device now, the files behind it are still being read
-                _n, r, sp = fasta.ingest_on_device(eng, i, text, universal, k, omit_soft)
+                _n, r, sp = _ingest_genome(eng, i, text, universal, run)
                 rna.append(r)
-                specials.append([codec.split_window(w, Le, De, Re) for w in sp])
-                eng.sort(i)
+                specials.append(sp)
                 del text
             else:
                 first.append((text, universal))     # (no plan, or a file larger than planned: all sizes first)
@@ -466,33 +537,32 @@ def _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, v
             true_max = max(max(len(t) for t, _ in first), 1)
             for i in (range(len(files)) if planned else ()):
                 eng.free(i)
-            eng.set_params(Le, De, Re, omit_soft=omit_soft, max_bases=true_max)
+            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=true_max)
             for i, (text, universal) in enumerate(first):
-                _n, r, sp = fasta.ingest_on_device(eng, i, text, universal, k, omit_soft)
+                _n, r, sp = _ingest_genome(eng, i, text, universal, run)
                 rna.append(r)
-                specials.append([codec.split_window(w, Le, De, Re) for w in sp])
-                eng.sort(i)
+                specials.append(sp)
         t2 = time.time()
         del first
         t3 = time.time()
         mixed = any(rna) and not all(rna)
         if mixed:
             eng.set_mixed_alphabets(True)
-        finish = _to_rna if all(rna) else (lambda groups: groups)
         ids = list(range(len(files)))
-        ncand = eng.intersect(ids, flags, apply_filter=do_filter and not quirk_all_fail)
+        ncand = eng.intersect(ids, run.flags, apply_filter=run.do_filter and not run.quirk_all_fail)
         if mixed and ncand:
             ncand = _mixed_prefix_filter(eng, Le, Re)
         counts = [eng.count(i) for i in ids]
         t4 = time.time()
-        if verbose:
+        if run.verbose:
             for f, cnt in zip(files, counts):
-                print(f"=> Extracted and sorted {cnt:,} {k}-kmers from {f}", file=sys.stderr)
-        by_label = sorted(ids, key=lambda i: labels[i])
-        records = eng.collect(by_label) if (ncand and not quirk_all_fail) else np.empty(0, dtype=_native.RECORD)
+                print(f"=> Extracted and sorted {cnt:,} {run.k}-kmers from {f}", file=sys.stderr)
+        # (genomes listed by label: kr_collect's (key, position in the call) order is then the renderer's)
+        by_label = sorted(ids, key=lambda i: run.labels[i])
+        records = eng.collect(by_label) if (ncand and not run.quirk_all_fail) else np.empty(0, dtype=_native.RECORD)
         touched, sgroups = set(), []
-        if any(specials) and not quirk_all_fail:
-            touched, sgroups = _special_groups(eng, ids, labels, specials, (Le, De, Re), ingroup_labels, do_filter,
+        if any(specials) and not run.quirk_all_fail:
+            touched, sgroups = _special_groups(eng, ids, run.labels, specials, run.geo, run.ingroup_labels, run.do_filter,
                                                rna_genomes=rna if mixed else None)
         t5 = time.time()
     # (device_s ends where the context is gone: its buffers freed, the reader threads joined)
@@ -500,20 +570,7 @@ def _device_ingest_flow(files, ingroup_files, L, R, k, geo, omit_soft, device, v
              "kmers": int(sum(counts)) + sum(len(sp) for sp in specials), "candidates": int(ncand),
              "stage_s": {"texts arrive, parse + sort launches": t2 - t1, "texts freed": t3 - t2, "sorts + intersect": t4 - t3,
                          "collect": t5 - t4, "context freed": time.time() - t5}}
-    if quirk_all_fail:
-        return [], stats
-    if mixed:
-        groups = _mixed_finish(records, labels, (Le, De, Re), rna, ingroup_labels, do_filter)
-        if touched:
-            groups = _merge_groups(groups, touched, sgroups)
-        stats["candidates"] = len(groups)
-        return groups, stats
-    if not touched and not any(rna):
-        return amplicon.RecordGroups(records, labels, Le, De, Re), stats
-    groups = amplicon.groups_from_records(records, labels, Le, De, Re, rna=False)
-    if touched:
-        groups = _merge_groups(groups, touched, sgroups)
-    return finish(groups), stats
+    return _packed_result(records, run, rna, touched, sgroups, stats)
 
 
 # ----------------------------------------------------------------------------
@@ -543,8 +600,7 @@ def _plan_batch(eng, nfiles, est_bases):
     return max(1, fit)
 
 
-def _find_regions_streaming(eng, pool, files, labels, flags, k, geo, omit_soft, verbose, do_filter, quirk_all_fail, batch, t0,
-                            max_bases):
+def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
     """find_regions for a genome set that does not fit the GPU at once (the reference has no such limit: it sorts in
     external memory, kstream.py:108-119, and merges files pairwise, intersectAmplicons.py:232-310).  The genomes go
     through the device in batches of `batch`: sort the batch; the first batch is intersected (with the diagnostic filter:
@@ -554,16 +610,17 @@ def _find_regions_streaming(eng, pool, files, labels, flags, k, geo, omit_soft, 
     the final candidates are what remains of those; only when the running set was too large to collect from (no
     outgroup, no filter: every conserved pair is a candidate) or IUPAC windows touch groups whose ACGT members must be
     looked up, a second pass sorts every batch again and collects then.  Same records, same order, same text as the
-    in-core flow (tests/test_gpu_cli.py)."""
+    in-core flow (tests/test_gpu_cli.py).  -> (records, RNA per genome, touched (left,right) pairs, their groups, stats)"""
     from . import _native
-    Le, De, Re = geo
+    Le, De, Re = run.geo
+    labels, flags = run.labels, run.flags
     n = len(files)
     ing = [i for i in range(n) if flags[i]]
     outg = [i for i in range(n) if not flags[i]]
     order = []
     for j in range(max(len(ing), len(outg))):
         order += ing[j:j + 1] + outg[j:j + 1]
-    apply_f = do_filter and not quirk_all_fail
+    apply_f = run.do_filter and not run.quirk_all_fail
     rank_of = {g: r for r, g in enumerate(sorted(range(n), key=lambda i: labels[i]))}
     rna, specials, counts = [None] * n, [None] * n, [0] * n
     pmask = np.uint64((~0 << (64 - 2 * (Le + Re))) & 0xFFFFFFFFFFFFFFFF) if Le + Re < 32 else np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -588,22 +645,21 @@ def _find_regions_streaming(eng, pool, files, labels, flags, k, geo, omit_soft, 
         done = []
         texts = {g: futs[g].result() for g in ids_b}
         if read_s[0] is None:
-            read_s[0] = time.time() - t0
+            read_s[0] = time.time() - run.t0
         biggest = max(len(t) for t, _ in texts.values())
         if biggest > maxb[0]:
             # (the plan came from the files' sizes: a text longer than it said -- nothing is resident between batches)
             maxb[0] = biggest
-            eng.set_params(Le, De, Re, omit_soft=omit_soft, max_bases=biggest)
+            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=biggest)
         try:
             for g in ids_b:
                 text, universal = texts.pop(g)
                 done.append(g)          # (before the ingest: a genome that fails half way holds buffers, too -- ADVICE r5)
-                _n, r, sp = fasta.ingest_on_device(eng, g, text, universal, k, omit_soft)
+                _n, r, sp = _ingest_genome(eng, g, text, universal, run)
                 del text
                 if first_pass:
                     rna[g] = r
-                    specials[g] = [codec.split_window(w, Le, De, Re) for w in sp]
-                eng.sort(g)
+                    specials[g] = sp
             for g in ids_b:
                 counts[g] = eng.count(g)
         except _native.KrispHipError:
@@ -668,10 +724,10 @@ def _find_regions_streaming(eng, pool, files, labels, flags, k, geo, omit_soft, 
             # their diagnostic bases into the masks, the filter -- instead of being intersected whole: the candidate list
             # of a batch that holds one side only is every prefix of its genomes, 24 bytes each)
             running[0] = eng.probe_cands(ids_b, bflags, apply_filter=apply_f)
-        if verbose:
+        if run.verbose:
             for g in ids_b:
-                print(f"=> Extracted and sorted {counts[g]:,} {k}-kmers from {files[g]}", file=sys.stderr)
-        if quirk_all_fail or not running[0]:
+                print(f"=> Extracted and sorted {counts[g]:,} {run.k}-kmers from {files[g]}", file=sys.stderr)
+        if run.quirk_all_fail or not running[0]:
             return
         if eager[0] and running[0] <= STREAM_EAGER_MAX:
             kept.append(eng.collect(sorted(ids_b, key=lambda g: rank_of[g])))
@@ -684,10 +740,10 @@ def _find_regions_streaming(eng, pool, files, labels, flags, k, geo, omit_soft, 
         running[0] = _mixed_prefix_filter(eng, Le, Re)
     final = eng.cands().copy() if running[0] else np.empty(0, dtype=_native.CAND)
     stats["mixed_rna"] = [bool(r) for r in rna] if mixed else None
-    touched = {(l, r) for sp in specials for (l, d, r) in sp} if not quirk_all_fail else set()
+    touched = {(l, r) for sp in specials for (l, d, r) in sp} if not run.quirk_all_fail else set()
     pure = sorted({_prefix_key(l, r) for (l, r) in touched if _pure(l) and _pure(r)})
     srecs = []
-    if (len(final) and not eager[0] and not quirk_all_fail) or pure:
+    if (len(final) and not eager[0] and not run.quirk_all_fail) or pure:
         stats["passes"] = 2
         tc = np.zeros(len(pure), dtype=_native.CAND)
         tc["prefix"] = np.array(pure, dtype=np.uint64)
@@ -711,86 +767,100 @@ def _find_regions_streaming(eng, pool, files, labels, flags, k, geo, omit_soft, 
     sgroups = []
     if touched:
         recs = np.concatenate(srecs) if srecs else None
-        sgroups = _special_groups_from(recs, list(range(n)), labels, specials, geo, frozenset(l for l, f in zip(labels, flags) if f),
-                                       do_filter, rna_genomes=[bool(r) for r in rna] if mixed else None)
+        sgroups = _special_groups_from(recs, list(range(n)), labels, specials, run.geo, run.ingroup_labels, run.do_filter,
+                                       rna_genomes=[bool(r) for r in rna] if mixed else None)
     stats.update(read_s=read_s[0] or 0.0, kmers=int(sum(counts)) + sum(len(sp) for sp in specials), candidates=int(len(final)))
-    return records, touched, sgroups, all(rna), stats
+    return records, [bool(r) for r in rna], touched, sgroups, stats
 
 
-def _find_regions_wide_device_ingest(files, ingroup_files, k, geo, omit_soft, device, verbose, do_filter, workers, t0):
-    """find_regions for amplicons longer than one key with the PARSE on the device: the files are read (and inflated) on host
-    threads, every text goes to the device as it is (fasta.ingest_on_device: kr_genome_upload_text, or kr_genome_upload_bgzf
-    for a BGZF file), kr_wide_run follows.  The host sees a genome's bases again only where it needs them -- IUPAC windows
-    (scan_special), mixed DNA / RNA runs, the groups IUPAC windows touch -- through kr_genome_fetch_bases.  Same results as
-    the host-parse flow (KRISP_HOST_PARSE=1 keeps that one: A/B, tests).  -> (groups, stats), or None: take the host parse."""
+def _find_regions_wide(files, run, host_parse):
+    """find_regions for amplicons longer than one key (kr_wide_run).  The files are read (and inflated) on host threads,
+    every text goes to the device as it is (fasta.ingest_on_device: kr_genome_upload_text, or kr_genome_upload_bgzf for a
+    BGZF file), and the host sees a genome's bases again only where it needs them -- IUPAC windows (scan_special), mixed
+    DNA / RNA runs, the groups IUPAC windows touch -- through kr_genome_fetch_bases.  host_parse: the files are parsed on
+    the host threads (fasta.ingest) and their bases uploaded -- for a run whose groups all fail the filter, and for one
+    whose probe text is longer than its genomes.  -> (groups, stats), or None: the probe text does not fit, take the host
+    parse."""
     from concurrent.futures import ThreadPoolExecutor
     from . import _native
-    Le, De, Re = geo
-    with ThreadPoolExecutor(max_workers=workers) as pool:
-        raw = list(pool.map(fasta.read_text, files))
-    labels = ["merged_file"] if len(files) == 1 else [simplename(f) for f in files]
-    ingroup_labels = frozenset(simplename(f) for f in ingroup_files)
-    flags = [lab in ingroup_labels for lab in labels]
-    stats = {"read_s": time.time() - t0}
+    Le, De, Re = run.geo
+    with ThreadPoolExecutor(max_workers=run.workers) as pool:
+        if host_parse:
+            loaded = list(pool.map(lambda f: fasta.ingest(f, run.k, run.omit_soft), files))
+        else:
+            loaded = list(pool.map(fasta.read_text, files))
+    stats = {"read_s": time.time() - run.t0}
     t1 = time.time()
-    budget = int(os.environ.get("KRISP_HBM_BUDGET", "0"))
-    maxb = max(max(len(t) for t, _ in raw), 64)
-    with _native.Engine(device=device, hbm_budget=budget) as eng:
-        eng.set_params_wide(Le, De, Re, omit_soft=omit_soft, max_bases=maxb)
-        nb, rna, specials = [], [], []
-        for i, (text, universal) in enumerate(raw):
-            n, r, sp = fasta.ingest_on_device(eng, i, text, universal, k, omit_soft)
-            nb.append(n)
-            rna.append(bool(r))
-            specials.append([codec.split_window(w, Le, De, Re) for w in sp])
-            raw[i] = None
-        mixed = any(rna) and not all(rna)
-        touched = {(l, r) for sp in specials for (l, d, r) in sp}
-        probes = sorted(p for p in touched if _pure(p[0]) and _pure(p[1]))
-        probe_text = np.frombuffer("\n".join(l + "A" * De + r for l, r in probes).encode(), dtype=np.uint8)
-        if len(probe_text) > maxb:
-            return None
-        texts = None
+    if run.quirk_all_fail:
+        stats.update(device_s=0.0, kmers=0, candidates=0)
+        return [], stats
+    ids = list(range(len(files)))
+    with _engine(run.device) as eng:
+        # k-mers holding IUPAC letters (kept by the reference): the (left,right) groups they touch
+        # are rebuilt on the host; those with plain flanks need their ACGT members from every
+        # genome, found on the device through a probe "genome" of the touched flank pairs
+        if host_parse:
+            texts = [b for b, _, _ in loaded]
+            rna = [bool(r) for _, r, _ in loaded]
+            specials = [[codec.split_window(w, Le, De, Re) for w in sp] for _, _, sp in loaded]
+            touched, probes, probe_text = _touched_pairs(specials, De)
+            eng.set_params_wide(Le, De, Re, omit_soft=run.omit_soft,
+                                max_bases=max(max(len(t) for t in texts), len(probe_text)))
+            for i, t in enumerate(texts):
+                eng.upload(i, t)
+        else:
+            texts = None                # (the bases come back from the device when a branch below needs them)
+            maxb = max(max(len(t) for t, _ in loaded), 64)
+            eng.set_params_wide(Le, De, Re, omit_soft=run.omit_soft, max_bases=maxb)
+            nb, rna, specials = [], [], []
+            for i, (text, universal) in enumerate(loaded):
+                n, r, sp = _ingest_genome(eng, i, text, universal, run)
+                nb.append(n)
+                rna.append(bool(r))
+                specials.append(sp)
+                loaded[i] = None
+            touched, probes, probe_text = _touched_pairs(specials, De)
+            if len(probe_text) > maxb:
+                return None
 
         def host_texts():
             nonlocal texts
             if texts is None:
-                texts = [eng.fetch_bases(i, nb[i]).copy() for i in range(len(files))]
+                texts = [eng.fetch_bases(i, nb[i]).copy() for i in ids]
             return texts
-        ids = list(range(len(files)))
+        mixed = any(rna) and not all(rna)
         if mixed:
             eng.set_mixed_alphabets(True)
-        nhits = eng.wide_run(ids, flags, apply_filter=do_filter)
+        nhits = eng.wide_run(ids, run.flags, apply_filter=run.do_filter)
         hits = eng.wide_fetch(_native.WIDE_HITS) if nhits else np.empty(0, dtype=_native.WIDE_HIT)
         ngroups = int(eng.wide_fetch(_native.WIDE_NGROUPS)[0])
         counts = eng.wide_fetch(_native.WIDE_COUNTS).tolist()
-        stats["wide_batch"] = int(eng.wide_fetch(_native.WIDE_BATCH_USED)[0])
-        if verbose:
+        stats["wide_batch"] = int(eng.wide_fetch(_native.WIDE_BATCH_USED)[0])       # (0: every genome sorted at once)
+        if run.verbose:
             for f, cnt in zip(files, counts):
-                print(f"=> Extracted and sorted {cnt:,} {k}-kmers from {f}", file=sys.stderr)
-        finish = _to_rna if all(rna) else (lambda groups: groups)
+                print(f"=> Extracted and sorted {cnt:,} {run.k}-kmers from {f}", file=sys.stderr)
         if mixed:
-            groups = _groups_from_hits(hits, host_texts(), labels, Le, De, Re, rna_genomes=rna)
-            groups = [g for g in groups if not (set(g[0].left + g[0].right) & set("TU"))]
-            if do_filter and ingroup_labels:
-                groups = [g for g in groups if amplicon.ingroup_unique_columns(g, ingroup_labels)]
+            groups = _mixed_wide_groups(_groups_from_hits(hits, host_texts(), run.labels, Le, De, Re, rna_genomes=rna), run)
             if touched:
-                sgroups = _special_groups_wide(eng, host_texts(), labels, specials, touched, probes, probe_text,
-                                               (Le, De, Re), ingroup_labels, do_filter, rna_genomes=rna)
+                sgroups = _special_groups_wide(eng, host_texts(), run.labels, specials, touched, probes, probe_text,
+                                               run.geo, run.ingroup_labels, run.do_filter, rna_genomes=rna)
                 groups = _merge_groups(groups, touched | {(g[0].left, g[0].right) for g in sgroups}, sgroups)
             ngroups = len(groups)
-            finish = lambda g: g        # noqa: E731
         elif touched:
-            groups = _groups_from_hits(hits, host_texts(), labels, Le, De, Re)
-            sgroups = _special_groups_wide(eng, host_texts(), labels, specials, touched, probes, probe_text,
-                                           (Le, De, Re), ingroup_labels, do_filter)
+            groups = _groups_from_hits(hits, host_texts(), run.labels, Le, De, Re)
+            sgroups = _special_groups_wide(eng, host_texts(), run.labels, specials, touched, probes, probe_text,
+                                           run.geo, run.ingroup_labels, run.do_filter)
             groups = _merge_groups(groups, touched, sgroups)
+            if all(rna):
+                groups = _to_rna(groups)
         else:
-            rows = eng.wide_windows(k) if nhits else np.empty((0, k), dtype=np.uint8)
-            groups = amplicon.WindowGroups(rows, hits["cand"], hits["genome"], labels, Le, De, Re, rna=all(rna))
-            finish = lambda g: g        # noqa: E731  (the RNA letters are the renderer's)
+            # the member windows are cut on the device (kr_wide_fetch_windows) and rendered from their rows in the
+            # library (amplicon.WindowGroups: no object per window; the list of groups only if someone walks it; the RNA
+            # letters are the renderer's)
+            rows = eng.wide_windows(run.k) if nhits else np.empty((0, run.k), dtype=np.uint8)
+            groups = amplicon.WindowGroups(rows, hits["cand"], hits["genome"], run.labels, Le, De, Re, rna=all(rna))
     stats.update(device_s=time.time() - t1, kmers=int(sum(counts)) + sum(len(sp) for sp in specials), candidates=ngroups)
-    return finish(groups), stats
+    return groups, stats
 
 
 # ----------------------------------------------------------------------------
@@ -804,162 +874,30 @@ def find_regions(ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=Fa
     (krisp_fasta.py:237-272), on the GPU: one sort per genome, one n-way
     intersection with the diagnostic filter fused in, one collect.
     Returns (groups, stats)."""
-    from . import _native
-    k = amplicon_len
-    D_nominal = k - L - R
-    Le, De, Re = codec.effective_geometry(L, D_nominal, R)
     files = list(ingroup_files) + list(outgroup_files)
-    # the reference filters whenever k > L + R (krisp_fasta.py:265); with R == 0 the
-    # diagnostic column is empty (kstream.py:824-830) and every group fails the filter
-    do_filter = k > L + R
-    quirk_all_fail = do_filter and De == 0
-    if wide is None:                 # (tests force the wide path on packable geometries)
-        wide = _is_wide(Le, De, Re)
-    if wide and not quirk_all_fail:
-        _check_wide(Le, De, Re)
-    elif not wide:
-        _check_geometry(Le, De, Re)
-    t0 = time.time()
-    from concurrent.futures import ThreadPoolExecutor
-    workers = max(1, min(len(files), os.cpu_count() or 1, 16))
-    if not wide and os.environ.get("KRISP_HOST_PARSE") != "1":
-        # files are read and inflated concurrently on the host (the library releases the GIL); the PARSE runs on the
-        # device, genome by genome as the texts arrive (fasta.ingest_on_device), each followed at once by its sort
-        while True:
-            try:
-                return _find_regions_device_ingest(files, ingroup_files, L, R, k, (Le, De, Re), omit_soft, device, verbose,
-                                                   do_filter, quirk_all_fail, workers, t0)
-            except fasta.GzipTextLonger as e:
-                # (a `.gz` file of several members handed to the device inflate: the run's plan came from its last member's
-                # length -- again from the start, that file read on the host: each round takes one more file off the device)
-                if verbose:
-                    print(f"=> {e}: again, that file inflated on the host", file=sys.stderr)
-    if wide and not quirk_all_fail and os.environ.get("KRISP_HOST_PARSE") != "1":
-        # round 6: amplicons longer than one key take the device's reader, too (the host's parser was the larger half of such a
-        # run from files: 1.8 of 2.4 s at 8 x 500 Mbp, tools/e2e_profile.py) -- None: a genome set whose IUPAC windows make a
-        # probe text longer than its genomes (tiny inputs): the host parse below
-        while True:
-            try:
-                got = _find_regions_wide_device_ingest(files, ingroup_files, k, (Le, De, Re), omit_soft, device, verbose,
-                                                       do_filter, workers, t0)
-                break
-            except fasta.GzipTextLonger as e:         # (as above)
-                if verbose:
-                    print(f"=> {e}: again, that file inflated on the host", file=sys.stderr)
-        if got is not None:
-            return got
-    # ingest: files are read, inflated and parsed concurrently (the parser releases the GIL)
-    with ThreadPoolExecutor(max_workers=workers) as pool:
-        loaded = list(pool.map(lambda f: fasta.ingest(f, k, omit_soft), files))
-    texts = [b for b, _, _ in loaded]
-    specials = [[codec.split_window(w, Le, De, Re) for w in sp] for _, _, sp in loaded]
-    rna = [bool(r) for _, r, _ in loaded]
-    mixed = any(rna) and not all(rna)
-    finish = _to_rna if all(rna) else (lambda groups: groups)
-    if len(files) == 1:
-        # mergeFiles moves the lone k-mer file; its lines carry no label, so later stages
-        # label them with the file they read: simplename('merged_file.txt') (shared.py:373)
-        labels = ["merged_file"]
-    else:
-        labels = [simplename(f) for f in files]
-    ingroup_labels = frozenset(simplename(f) for f in ingroup_files)
-    flags = [lab in ingroup_labels for lab in labels]
-    stats = {"read_s": time.time() - t0}
-    t1 = time.time()
-    if wide:
-        if quirk_all_fail:
-            stats.update(device_s=0.0, kmers=0, candidates=0)
-            return [], stats
-        # k-mers holding IUPAC letters (kept by the reference): the (left,right) groups they touch
-        # are rebuilt on the host; those with plain flanks need their ACGT members from every
-        # genome, found on the device through a probe "genome" of the touched flank pairs
-        touched = {(l, r) for sp in specials for (l, d, r) in sp}
-        probes = sorted(p for p in touched if _pure(p[0]) and _pure(p[1]))
-        probe_text = np.frombuffer("\n".join(l + "A" * De + r for l, r in probes).encode(), dtype=np.uint8)
-        budget = int(os.environ.get("KRISP_HBM_BUDGET", "0"))       # (bytes; tests and shared devices: kr_create's HBM budget)
-        with _native.Engine(device=device, hbm_budget=budget) as eng:
-            eng.set_params_wide(Le, De, Re, omit_soft=omit_soft,
-                                max_bases=max(max(len(t) for t in texts), len(probe_text)))
-            ids = list(range(len(files)))
-            for i, t in enumerate(texts):
-                eng.upload(i, t)
-            if mixed:
-                eng.set_mixed_alphabets(True)
-            nhits = eng.wide_run(ids, flags, apply_filter=do_filter)
-            hits = eng.wide_fetch(_native.WIDE_HITS) if nhits else np.empty(0, dtype=_native.WIDE_HIT)
-            ngroups = int(eng.wide_fetch(_native.WIDE_NGROUPS)[0])
-            counts = eng.wide_fetch(_native.WIDE_COUNTS).tolist()
-            stats["wide_batch"] = int(eng.wide_fetch(_native.WIDE_BATCH_USED)[0])       # (0: every genome sorted at once)
+    # mergeFiles moves the lone k-mer file; its lines carry no label, so later stages
+    # label them with the file they read: simplename('merged_file.txt') (shared.py:373)
+    labels = ["merged_file"] if len(files) == 1 else [simplename(f) for f in files]
+    run = _describe_run(labels, ingroup_files, L, R, amplicon_len, omit_soft, device, verbose, wide)
+    if run.wide and run.quirk_all_fail:
+        return _find_regions_wide(files, run, host_parse=True)
+    # files are read and inflated concurrently on the host (the library releases the GIL); the PARSE runs on the device,
+    # genome by genome as the texts arrive (fasta.ingest_on_device), each followed at once by its sort -- round 6: amplicons
+    # longer than one key, too (the host's parser was the larger half of such a run from files: 1.8 of 2.4 s at 8 x 500 Mbp,
+    # tools/e2e_profile.py)
+    while True:
+        try:
+            got = _find_regions_wide(files, run, host_parse=False) if run.wide else _find_regions_device_ingest(files, run)
+            break
+        except fasta.GzipTextLonger as e:
+            # (a `.gz` file of several members handed to the device inflate: the run's plan came from its last member's
+            # length -- again from the start, that file read on the host: each round takes one more file off the device)
             if verbose:
-                for f, cnt in zip(files, counts):
-                    print(f"=> Extracted and sorted {cnt:,} {k}-kmers from {f}", file=sys.stderr)
-            if mixed:
-                # (text decides: flank pairs that hold T / U are in no DNA genome and RNA genome alike, and the filter's
-                # columns are compared letter by letter -- _mixed_finish's rule on member windows)
-                groups = _groups_from_hits(hits, texts, labels, Le, De, Re, rna_genomes=rna)
-                groups = [g for g in groups if not (set(g[0].left + g[0].right) & set("TU"))]
-                if do_filter and ingroup_labels:
-                    groups = [g for g in groups if amplicon.ingroup_unique_columns(g, ingroup_labels)]
-                if touched:
-                    sgroups = _special_groups_wide(eng, texts, labels, specials, touched, probes, probe_text,
-                                                   (Le, De, Re), ingroup_labels, do_filter, rna_genomes=rna)
-                    groups = _merge_groups(groups, touched | {(g[0].left, g[0].right) for g in sgroups}, sgroups)
-                ngroups = len(groups)
-                finish = lambda g: g        # noqa: E731
-            elif touched:
-                groups = _groups_from_hits(hits, texts, labels, Le, De, Re)
-                sgroups = _special_groups_wide(eng, texts, labels, specials, touched, probes, probe_text,
-                                               (Le, De, Re), ingroup_labels, do_filter)
-                groups = _merge_groups(groups, touched, sgroups)
-            else:
-                # the member windows are cut on the device (kr_wide_fetch_windows) and rendered from their rows in the
-                # library (amplicon.WindowGroups: no object per window; the list of groups only if someone walks it)
-                rows = eng.wide_windows(k) if nhits else np.empty((0, k), dtype=np.uint8)
-                groups = amplicon.WindowGroups(rows, hits["cand"], hits["genome"], labels, Le, De, Re, rna=all(rna))
-                finish = lambda g: g        # noqa: E731  (the RNA letters are the renderer's)
-        stats.update(device_s=time.time() - t1, kmers=int(sum(counts)) + sum(len(sp) for sp in specials),
-                     candidates=ngroups)
-        return finish(groups), stats
-    with _native.Engine(device=device) as eng:
-        eng.set_params(Le, De, Re, omit_soft=omit_soft, max_bases=max(len(t) for t in texts))
-        counts = []
-        for i, t in enumerate(texts):
-            eng.upload(i, t)
-            eng.sort(i)
-        ids = list(range(len(files)))
-        if mixed:
-            eng.set_mixed_alphabets(True)
-        ncand = eng.intersect(ids, flags, apply_filter=do_filter and not quirk_all_fail)
-        if mixed and ncand:
-            ncand = _mixed_prefix_filter(eng, Le, Re)
-        counts = [eng.count(i) for i in ids]
-        if verbose:
-            for f, c in zip(files, counts):
-                print(f"=> Extracted and sorted {c:,} {k}-kmers from {f}", file=sys.stderr)
-        # (genomes listed by label: kr_collect's (key, position in the call) order is then the renderer's)
-        by_label = sorted(ids, key=lambda i: labels[i])
-        records = eng.collect(by_label) if (ncand and not quirk_all_fail) else np.empty(0, dtype=_native.RECORD)
-        touched, sgroups = set(), []
-        if any(specials) and not quirk_all_fail:
-            touched, sgroups = _special_groups(eng, ids, labels, specials, (Le, De, Re), ingroup_labels,
-                                               do_filter, rna_genomes=rna if mixed else None)
-    stats.update(device_s=time.time() - t1, kmers=int(sum(counts)) + sum(len(sp) for sp in specials),
-                 candidates=int(ncand))
-    if quirk_all_fail:
-        return [], stats
-    if mixed:
-        groups = _mixed_finish(records, labels, (Le, De, Re), rna, ingroup_labels, do_filter)
-        if touched:
-            groups = _merge_groups(groups, touched, sgroups)
-        stats["candidates"] = len(groups)
-        return groups, stats
-    if not touched and not any(rna):
-        # (plain records: the renderer works from them directly, the list of groups is built only if someone walks it)
-        return amplicon.RecordGroups(records, labels, Le, De, Re), stats
-    groups = amplicon.groups_from_records(records, labels, Le, De, Re, rna=False)
-    if touched:
-        groups = _merge_groups(groups, touched, sgroups)
-    return finish(groups), stats
+                print(f"=> {e}: again, that file inflated on the host", file=sys.stderr)
+    if got is None:
+        # (a genome set whose IUPAC windows make a probe text longer than its genomes -- tiny inputs: the host parse)
+        got = _find_regions_wide(files, run, host_parse=True)
+    return got
 
 
 class PeerFailed(RuntimeError):
@@ -971,14 +909,6 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
     engine its communicator.  Returns (groups, stats) on rank 0 and (None, stats) elsewhere."""
     from . import _native
     from . import distributed as D
-    k = amplicon_len
-    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
-    do_filter = k > L + R
-    wide = Le + De + Re > 32 or De > 16            # amplicons longer than one key: kr_wide_run, collective inside
-    if wide and not (do_filter and De == 0):
-        _check_wide(Le, De, Re)
-    elif not wide:
-        _check_geometry(Le, De, Re)
     # interleave ingroup / outgroup files so that a round-robin shard holds both kinds
     ing, outg = list(ingroup_files), list(outgroup_files)
     order = []
@@ -987,12 +917,11 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
             order.append(ing[i])
         if i < len(outg):
             order.append(outg[i])
+    # (amplicons longer than one key: kr_wide_run, collective inside; a lone genome is labelled by its file here)
+    run = _describe_run([simplename(f) for f in order], ing, L, R, amplicon_len, omit_soft, device, False)
     if len(order) < world:
         raise ValueError(f"{len(order)} genomes cannot be sharded over {world} GPUs")
-    labels = [simplename(f) for f in order]
-    # ingroup / outgroup by LABEL, as the reference classifies (Amplicon.py:495-521) and as
-    # find_regions does: an outgroup file whose label equals an ingroup label counts as ingroup
-    ingroup_labels = frozenset(simplename(f) for f in ing)
+    Le, De, Re = run.geo
     mine = D.shard(list(range(len(order))), rank, world)
 
     with _native.Engine(device=device) as eng:
@@ -1012,8 +941,8 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
                 raise PeerFailed(f"rank {rank}: another rank failed")
             return out
 
-        t0 = time.time()
-        loaded = together(lambda: [fasta.ingest(order[g], k, omit_soft) for g in mine])
+        run = run._replace(t0=time.time())          # (the clock starts once the rank is connected)
+        loaded = together(lambda: [fasta.ingest(order[g], run.k, run.omit_soft) for g in mine])
         kinds = eng.comm_allreduce([1.0 if any(sp for _, _, sp in loaded) else 0.0,
                                     1.0 if any(r for _, r, _ in loaded) else 0.0,
                                     float(max(len(b) for b, _, _ in loaded)),
@@ -1043,13 +972,12 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
             for blob in eng.comm_allgather(json.dumps(mine_sp).encode()):
                 for g, sp in json.loads(blob.decode()).items():
                     specials_all[int(g)] = [tuple(w) for w in sp]
-        stats = {"read_s": time.time() - t0}
+        stats = {"read_s": time.time() - run.t0}
         t1 = time.time()
-        quirk_all_fail = do_filter and De == 0
-        filt = do_filter and not quirk_all_fail
+        filt = run.do_filter and not run.quirk_all_fail
 
-        if wide:
-            if quirk_all_fail:
+        if run.wide:
+            if run.quirk_all_fail:
                 eng.comm_barrier()
                 stats.update(device_s=0.0, kmers=0, candidates=0, records=0)
                 return ([] if rank == 0 else None), stats
@@ -1057,10 +985,10 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
             def wide_part():
                 # the spectra lists, the group list and the kept groups' masks are exchanged inside kr_wide_run
                 # (the same calls in the same order on every rank); hits name genomes by their global number
-                eng.set_params_wide(Le, De, Re, omit_soft=omit_soft, max_bases=int(kinds[2]))
+                eng.set_params_wide(Le, De, Re, omit_soft=run.omit_soft, max_bases=int(kinds[2]))
                 for g, (bases, _, _) in zip(mine, loaded):
                     eng.upload(g, bases)
-                nh = eng.wide_run(mine, [labels[g] in ingroup_labels for g in mine], apply_filter=do_filter)
+                nh = eng.wide_run(mine, [run.flags[g] for g in mine], apply_filter=run.do_filter)
                 return nh, int(sum(eng.wide_fetch(_native.WIDE_COUNTS).tolist())), int(eng.wide_fetch(_native.WIDE_NGROUPS)[0])
 
             nh, counts, ngroups = together(wide_part)
@@ -1072,15 +1000,13 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
             wide_sp = None
             if specials_all is not None:
                 import json
-                touched_w = {(l, r) for sp in specials_all for (l, d, r) in sp}
-                probes = sorted(p for p in touched_w if _pure(p[0]) and _pure(p[1]))
-                probe_text = np.frombuffer("\n".join(l + "A" * De + r for l, r in probes).encode(), dtype=np.uint8)
+                touched_w, probes, probe_text = _touched_pairs(specials_all, De)
 
                 def probe_part():
                     if not probes:
                         return {}
                     with _native.Engine(device=device) as e2:
-                        e2.set_params_wide(Le, De, Re, omit_soft=omit_soft, max_bases=max(int(kinds[2]), len(probe_text)))
+                        e2.set_params_wide(Le, De, Re, omit_soft=run.omit_soft, max_bases=max(int(kinds[2]), len(probe_text)))
                         for g, (bases, _, _) in zip(mine, loaded):
                             e2.upload(g, bases)
                         return _wide_probe_members(e2, [b for b, _, _ in loaded], list(mine), probes, probe_text,
@@ -1105,17 +1031,16 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
                 texts[g] = bases
             for g in sorted(set(hits["genome"].tolist())):
                 if texts[g] is None:
-                    texts[g] = fasta.ingest(order[g], k, omit_soft)[0]
-            wg = _groups_from_hits(hits, texts, labels, Le, De, Re, rna_genomes=rna_all)
+                    texts[g] = fasta.ingest(order[g], run.k, run.omit_soft)[0]
+            wg = _groups_from_hits(hits, texts, run.labels, Le, De, Re, rna_genomes=rna_all)
             if mixed:
-                wg = [g for g in wg if not (set(g[0].left + g[0].right) & set("TU"))]
-                if do_filter and ingroup_labels:
-                    wg = [g for g in wg if amplicon.ingroup_unique_columns(g, ingroup_labels)]
+                wg = _mixed_wide_groups(wg, run)
                 stats["candidates"] = len(wg)
                 return wg, stats
             if wide_sp is not None:
                 touched_w, members_w = wide_sp
-                sg = _special_groups_wide_from(members_w, len(order), labels, specials_all, touched_w, ingroup_labels, do_filter)
+                sg = _special_groups_wide_from(members_w, len(order), run.labels, specials_all, touched_w, run.ingroup_labels,
+                                               run.do_filter)
                 wg = _merge_groups(wg, touched_w, sg)
             return (_to_rna(wg) if all_rna else wg), stats
 
@@ -1125,7 +1050,7 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
         # second pass over the shard and travel to rank 0 as bytes (kr_comm_allgather) instead of from the device buffer of
         # ONE kr_collect.  KRISP_STREAM_BATCH=n forces batches of n genomes per rank (tests).
         bases_of = {g: b for g, (b, _, _) in zip(mine, loaded)}
-        flag_of = {g: labels[g] in ingroup_labels for g in mine}
+        flag_of = {g: run.flags[g] for g in mine}
         batched = [None]
 
         def shard_batches():
@@ -1138,7 +1063,7 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
                 at, first = at + m, False
 
         def device_part():
-            eng.set_params(Le, De, Re, omit_soft=omit_soft, max_bases=int(kinds[2]))
+            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=int(kinds[2]))
             batched[0] = _plan_batch(eng, len(mine), int(kinds[2])) if len(mine) > 1 else None
             if batched[0] is None:
                 for g in mine:
@@ -1192,15 +1117,15 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
         if mixed:
             together(lambda: _mixed_prefix_filter(eng, Le, Re))       # (the same list on every rank: the same cut)
         if any_batched:
-            myrec = together(lambda: np.empty(0, dtype=_native.RECORD) if quirk_all_fail else collect_shard())
+            myrec = together(lambda: np.empty(0, dtype=_native.RECORD) if run.quirk_all_fail else collect_shard())
             nrec = len(myrec)
-            allrec = gather_host_records(myrec) if not quirk_all_fail else None
+            allrec = gather_host_records(myrec) if not run.quirk_all_fail else None
         else:
-            nrec = together(lambda: 0 if quirk_all_fail else eng.collect(mine, fetch=False))
-            total = eng.records_gather() if not quirk_all_fail else 0
-            allrec = eng.fetch_records(total) if rank == 0 and not quirk_all_fail else None
+            nrec = together(lambda: 0 if run.quirk_all_fail else eng.collect(mine, fetch=False))
+            total = eng.records_gather() if not run.quirk_all_fail else 0
+            allrec = eng.fetch_records(total) if rank == 0 and not run.quirk_all_fail else None
         sprec, touched = None, set()
-        if specials_all is not None and not quirk_all_fail:
+        if specials_all is not None and not run.quirk_all_fail:
             # the ACGT members of every (left,right) group an IUPAC window touches: each rank looks them up in ITS
             # genomes (the touched prefixes as a candidate list), rank 0 gets all the records
             touched = {(l, r) for sp in specials_all for (l, d, r) in sp}
@@ -1225,21 +1150,12 @@ def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_file
                      candidates=int(max(ncand, 0)), records=int(nrec))
     if rank != 0:
         return None, stats
-    if quirk_all_fail:
-        return [], stats
-    if mixed:
-        groups = _mixed_finish(allrec, labels, (Le, De, Re), rna_all, ingroup_labels, do_filter)
-        stats["candidates"] = len(groups)
-        return groups, stats
-    finish = _to_rna if all_rna else (lambda groups: groups)
-    if not touched and not all_rna:
-        return amplicon.RecordGroups(allrec, labels, Le, De, Re), stats
-    groups = amplicon.groups_from_records(allrec, labels, Le, De, Re)
+    sgroups = []
     if touched:
-        sgroups = _special_groups_from(sprec, list(range(len(order))), labels, specials_all, (Le, De, Re),
-                                       ingroup_labels, do_filter)
-        groups = _merge_groups(groups, touched, sgroups)
-    return finish(groups), stats
+        sgroups = _special_groups_from(sprec, list(range(len(order))), run.labels, specials_all, run.geo,
+                                       run.ingroup_labels, run.do_filter)
+    # (a mixed run holds no IUPAC windows: MixedAlphabet above)
+    return _packed_result(allrec, run, rna_all if mixed else [all_rna] * len(order), touched, sgroups, stats)
 
 
 def find_regions_distributed(ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=False,
@@ -1528,9 +1444,7 @@ def _merge_files_wide(contents, labels, L, D, R, device):
         texts.append(np.frombuffer(t.replace(b"U", b"T") if rna else t, dtype=np.uint8))
     ids = list(range(len(texts)))
     mixed = any(rnas) and not all(rnas)
-    touched = {(l, r) for sp in specials for (l, d, r) in sp}
-    probes = sorted(p for p in touched if _pure(p[0]) and _pure(p[1]))
-    probe_text = np.frombuffer("\n".join(l + "A" * D + r for l, r in probes).encode(), dtype=np.uint8)
+    touched, probes, probe_text = _touched_pairs(specials, D)
     with _native.Engine(device=device) as eng:
         eng.set_params_wide(L, D, R, omit_soft=False, max_bases=max(1, max(len(t) for t in texts), len(probe_text)))
         eng.set_strands(_native.STRANDS_FORWARD)
