@@ -266,6 +266,36 @@ int64_t kr_wide_fetch(kr_ctx*, int what, void* out, size_t cap_bytes);   /* retu
  * rank: the hits of other ranks' genomes have no bases here).  Returns the number of rows; rows == NULL: size query. */
 int64_t kr_wide_fetch_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
 
+/* ---- locations: where the windows of the surviving groups lie (krisp_fasta --out_locations) ------------------------
+ * No seam inside krisp_fasta: the upstream project's misc_scripts/grepFastaSequence.py re-reads the FASTA files and
+ * str.find()s every sequence and its reverse complement, record by record.  Here each genome is scanned once on the
+ * device (csrc/k_locate.inc) against a hash table of the groups' (left, right) flank texts, with the window rules of
+ * kstream.py:617-677 (no N / n, no separator, no lower case under omit-soft, upper case otherwise; the reverse strand by
+ * COMP_MAP, kstream.py:11-18), for packed and wide geometries alike.
+ *
+ * kr_set_params_locate: a context for this pass only -- genomes go up through kr_genome_upload / _upload_text /
+ * _upload_bgzf / _upload_gzip with no sort plan (kr_genome_sort refuses them); 0 <= L, R <= KR_WIDE_MAX_FLANK,
+ * 1 <= L+D+R <= KR_WIDE_MAX_K, max_bases < 2^33. */
+int     kr_set_params_locate(kr_ctx*, int L, int D, int R, int softmask_mode, size_t max_bases);
+/* the groups' flanks: ngroups rows of L+R bytes (left then right, upper case, U written as T), row i = group i.  Builds the
+ * open-addressing table (a power of two >= 2 ngroups slots) and the membership bitmap the scan keeps in LDS.  Returns the
+ * number of slots; KR_ERR_PARAM when two rows are equal, KR_ERR_CAPACITY when the table does not fit. */
+int64_t kr_locate_table(kr_ctx*, const uint8_t* flanks, uint64_t ngroups);
+/* one hit: the group (row of kr_locate_table), strand 0 = the window as written ('+'), 1 = its reverse complement ('-'),
+ * pos = the window's first base in the uploaded bases (separators counted) */
+typedef struct { uint32_t group, strand; uint64_t pos; } kr_loc_hit;
+/* scans uploaded genome `id` against the table: returns the number of hits, kept on the device for kr_locate_fetch, in
+ * position order, '+' before '-' at one position (counted, scanned, written: the same order on every run) */
+int64_t kr_locate_scan(kr_ctx*, int id);
+int64_t kr_locate_fetch(kr_ctx*, kr_loc_hit* out, size_t cap);
+/* the hits' windows as text, cut on the device from the scanned genome (still uploaded): row i = the L+D+R letters of hit
+ * i, upper case, the reverse complement for strand 1 -- the k-mer the alignment lists (kstream.py:622-659).  Returns the
+ * number of rows; rows == NULL: size query */
+int64_t kr_locate_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
+/* the positions of the record separators ('\n') of uploaded genome `id`, ascending: the host maps a position to (record,
+ * offset) with them without fetching the bases.  Returns their number; out == NULL: the number only */
+int64_t kr_locate_seps(kr_ctx*, int id, uint64_t* out, size_t cap);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("KRISP_HIP_LIB") or os.path.join(HERE, "libkrisp_hip.s
 CAND = np.dtype([("prefix", "<u8"), ("in_mask", "<u8"), ("out_mask", "<u8")])
 RECORD = np.dtype([("key", "<u8"), ("genome", "<u4"), ("count", "<u4")])
 WIDE_HIT = np.dtype([("cand", "<u4"), ("genome", "<u4"), ("pos", "<u4"), ("strand", "<u4")])
+LOC_HIT = np.dtype([("group", "<u4"), ("strand", "<u4"), ("pos", "<u8")])     # kr_loc_hit
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -86,6 +87,12 @@ SYMBOLS = [
     ("kr_wide_run", _c.c_int64, [_P, _P, _c.c_int, _P, _c.c_int]),
     ("kr_wide_fetch", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t]),
     ("kr_wide_fetch_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_set_params_locate", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_size_t]),
+    ("kr_locate_table", _c.c_int64, [_P, _P, _c.c_uint64]),
+    ("kr_locate_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_locate_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_locate_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_locate_seps", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -621,6 +628,41 @@ class Engine:
         n = self._check(self.lib.kr_wide_fetch_windows(self.ctx, None, 0), "kr_wide_fetch_windows")
         out = np.empty((max(n, 1), k), dtype=np.uint8)
         self._check(self.lib.kr_wide_fetch_windows(self.ctx, _ptr(out), out.nbytes), "kr_wide_fetch_windows")
+        return out[:n]
+
+    # ---- locations (krisp_fasta --out_locations)
+    def set_params_locate(self, L, D, R, omit_soft=False, max_bases=0):
+        """a context for the locate pass only: genomes go up with no sort plan (kr_set_params_locate)"""
+        self._check(self.lib.kr_set_params_locate(self.ctx, L, D, R, SOFT_OMIT if omit_soft else SOFT_MAP, max_bases),
+                    "kr_set_params_locate")
+        self.params = (L, D, R)
+
+    def locate_table(self, flanks):
+        """flanks: uint8 [ngroups, L+R] (left then right, upper case, T for U) -> slots of the table (kr_locate_table)"""
+        f = np.ascontiguousarray(flanks, dtype=np.uint8)
+        return self._check(self.lib.kr_locate_table(self.ctx, _ptr(f) if f.size else None, len(f)), "kr_locate_table")
+
+    def locate(self, gid):
+        """LOC_HIT array of uploaded genome gid against the table: position order, strand 0 before 1 (kr_locate_scan)"""
+        n = self._check(self.lib.kr_locate_scan(self.ctx, gid), "kr_locate_scan")
+        out = np.empty(max(n, 1), dtype=LOC_HIT)
+        self._check(self.lib.kr_locate_fetch(self.ctx, _ptr(out), n), "kr_locate_fetch")
+        return out[:n]
+
+    def locate_windows(self, k):
+        """the latest locate()'s windows as text, cut on the device: uint8 [nhits, k] (kr_locate_windows)"""
+        n = self._check(self.lib.kr_locate_windows(self.ctx, None, 0), "kr_locate_windows")
+        out = np.empty((max(n, 1), k), dtype=np.uint8)
+        if n:
+            self._check(self.lib.kr_locate_windows(self.ctx, _ptr(out), out.nbytes), "kr_locate_windows")
+        return out[:n]
+
+    def locate_seps(self, gid):
+        """the positions of genome gid's record separators, ascending (kr_locate_seps)"""
+        n = self._check(self.lib.kr_locate_seps(self.ctx, gid, None, 0), "kr_locate_seps")
+        out = np.empty(max(n, 1), dtype=np.uint64)
+        if n:
+            self._check(self.lib.kr_locate_seps(self.ctx, gid, _ptr(out), n), "kr_locate_seps")
         return out[:n]
 
     # ---- timing

@@ -197,6 +197,15 @@ struct kr_ctx {
         u64 ngroups = 0;                // (left,right) groups present in all genomes (= nfin unless the list is canonical)
         int64_t nhits = -1;
     } wide;
+    // the locate pass (kr_set_params_locate / kr_locate_*: h_locate.inc)
+    struct Loc {
+        bool on = false;
+        int L = 0, D = 0, R = 0, k = 0, omit = 0;
+        u64 ngroups = 0, slots = 0;
+        int64_t nhits = -1;
+        int gid = -1;                   // the genome of the latest kr_locate_scan
+        DevBuf arena, table, bitmap, tcount, toff, hits, seps, rows;
+    } loc;
 };
 
 static int fail(kr_ctx* c, int code, const char* fmt, ...) {
@@ -487,6 +496,11 @@ void kr_destroy(kr_ctx* c) {
                 auto& d = w.fd[f][q];
                 release(c, d.keys); release(c, d.idx); release(c, d.slots); release(c, d.mzT); release(c, d.mzB);
             }
+    }
+    {
+        auto& l = c->loc;
+        DevBuf* lb[] = {&l.arena, &l.table, &l.bitmap, &l.tcount, &l.toff, &l.hits, &l.seps, &l.rows};
+        for (DevBuf* b : lb) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);
     for (auto e : c->pool) (void)hipEventDestroy(e);
@@ -1100,7 +1114,7 @@ int kr_genome_upload(kr_ctx* c, int id, const uint8_t* bases, size_t n) {
 // the genome's bookkeeping once its n bases are (being copied) on the device: slice plan, sort scratch
 static int upload_finish(kr_ctx* c, Genome& G, int id, size_t n) {
     int rc;
-    if (c->wide.on) {            // the slices are counted per phase by kr_wide_run
+    if (c->wide.on || c->loc.on) {   // the slices are counted per phase by kr_wide_run; a locate context sorts nothing
         G.uploaded = true;
         return KR_OK;
     }

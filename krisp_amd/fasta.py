@@ -98,6 +98,72 @@ def read_records(source):
     return recs
 
 
+def _header_id(line):
+    """the ID of a stripped header line: the text after '>' up to the first white space (Biopython's record.id)"""
+    words = line[1:].decode("utf-8", "surrogateescape").split(None, 1)
+    return words[0] if words else ""
+
+
+def _has_sequence(seg):
+    """does a run of whole lines hold a line that is not empty after strip_line?"""
+    rest = seg.strip(_WS_ASCII)
+    if not rest:
+        return False
+    if rest[0] < 0x80:
+        return True
+    return any(strip_line(ln) for ln in seg.split(b"\n"))
+
+
+def record_ids_text(text, universal):
+    """the ID of every record read_records yields for a file whose (inflated) text is `text` (bytes or a uint8 array;
+    universal: the text-mode line breaks of a plain file), in its order: the ID of the header that last preceded the
+    record's first sequence line ('' before any header: a first line that holds '>' elsewhere than at its start, and in
+    line mode, where every stripped line is a record).  Empty records are dropped as read_records drops them.  The scan
+    looks at the lines that hold '>' and at the ends of the runs of lines between them, not at every line."""
+    data = text.tobytes() if isinstance(text, np.ndarray) else bytes(text)
+    if universal and b"\r" in data:
+        data = data.replace(b"\r\n", b"\n").replace(b"\r", b"\n")
+    if not data:
+        return []
+    end0 = data.find(b"\n")
+    first = data if end0 < 0 else data[:end0]
+    body = len(data) if end0 < 0 else end0 + 1          # the first line is consumed by the detection (kstream.py:450)
+    if b">" not in first:
+        nlines = data.count(b"\n") + (0 if data.endswith(b"\n") else 1)
+        return [""] * (nlines - 1)
+    s = strip_line(first)
+    last = _header_id(s) if s.startswith(b">") else ""
+    ids, prev, pos = [], body, body
+    while True:
+        at = data.find(b">", pos)
+        if at < 0:
+            break
+        ls = data.rfind(b"\n", body, at) + 1 if at > body else body
+        ls = max(ls, body)
+        le = data.find(b"\n", at)
+        le = len(data) if le < 0 else le
+        pos = le + 1
+        line = strip_line(data[ls:le])
+        if not line.startswith(b">"):
+            continue                                    # ('>' inside a sequence line)
+        if _has_sequence(data[prev:ls]):
+            ids.append(last)
+        last, prev = _header_id(line), le + 1
+    if _has_sequence(data[prev:]):
+        ids.append(last)
+    return ids
+
+
+def record_ids(filename):
+    """record_ids_text of a file read again from disk (.gz / .bz2 by extension, as read_records reads it)"""
+    ext = os.path.splitext(filename)[1]
+    if ext in (".gz", ".bz2"):
+        with (gzip.open if ext == ".gz" else bz2.open)(filename, "rb") as f:
+            return record_ids_text(f.read(), False)
+    with open(filename, "rb") as f:
+        return record_ids_text(f.read(), True)
+
+
 def load_bases(filename):
     """file -> (upload buffer, is_rna, n_special): the same result as
     to_bases(read_records(filename)) through the library's one-pass host parser."""

@@ -1221,6 +1221,120 @@ def find_regions_multi_device(ingroup_files, outgroup_files, L, R, amplicon_len,
 
 
 # ----------------------------------------------------------------------------
+# locations of the surviving groups' windows (--out_locations)
+# ----------------------------------------------------------------------------
+LOCATION_HEADER = "region\tfile\trecord\trecord_index\tstart\tend\tstrand\tsequence"
+LOCATION = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"),
+                     ("end", "<i8"), ("strand", "U1"), ("sequence", "O")])
+
+
+def _group_flanks(groups, L, R):
+    """the (left, right) flank text of every group, in the groups' order -> uint8 [groups, L + R], upper case, T for U.
+    RecordGroups and WindowGroups give theirs from the device's records / windows: no Amplicon is made."""
+    if isinstance(groups, amplicon.RecordGroups):
+        keys = groups.records["key"]
+        if len(keys) == 0:
+            return np.empty((0, L + R), dtype=np.uint8)
+        pre = keys & codec.prefix_mask(L, R)
+        first = np.flatnonzero(np.concatenate([[True], pre[1:] != pre[:-1]]))
+        return np.ascontiguousarray(codec.keys_to_matrix(keys[first], groups.L, groups.D, groups.R)[:, :L + R])
+    if isinstance(groups, amplicon.WindowGroups):
+        rows = groups.rows
+        if len(rows) == 0:
+            return np.empty((0, L + R), dtype=np.uint8)
+        fl = np.concatenate([rows[:, :L], rows[:, rows.shape[1] - R:]], axis=1)
+        return np.ascontiguousarray(np.unique(fl, axis=0))      # (groups_from_windows orders groups by these bytes)
+    text = "".join(g[0].left + g[0].right for g in groups).replace("U", "T").encode("ascii")
+    return np.frombuffer(text, dtype=np.uint8).reshape(-1, L + R)
+
+
+def _locate_genome(eng, path, read, k, omit_soft):
+    """one genome (its text as fasta.read_text gave it: `read`) on the device of the locate context -> (hits, its windows
+    as text rows, record starts, record IDs, RNA)"""
+    text, universal = read
+    while True:
+        try:
+            n, rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
+            break
+        except fasta.GzipTextLonger:
+            text, universal = fasta.read_text(path)     # (that file is read on the host from now on: read_text knows it)
+    hits = eng.locate(0)
+    rows = eng.locate_windows(k)
+    seps = eng.locate_seps(0)
+    # the record IDs: from the text the host holds, or -- a file the device inflated -- from the file read again
+    names = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
+    nrec = len(seps) + 1 if n else 0
+    if n and len(names) != nrec:
+        raise RuntimeError(f"{path}: {len(names)} record IDs, but the device's bases hold {nrec} records")
+    return hits, rows, seps, names, rna
+
+
+def locate_regions(groups, ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=False, device=0):
+    """Where every window of every group lies: `groups` as find_regions / find_regions_multi_device /
+    find_regions_distributed returned them (lists, amplicon.RecordGroups, amplicon.WindowGroups), the same files and
+    geometry.  A separate pass over the inputs on one device (kr_locate_*): each genome is uploaded alone and scanned
+    against a hash table of the groups' (left, right) flanks.  Returns a LOCATION array, one row per window and strand:
+    region = the group's index, file = the path as given, record / record_index = the record's ID and its index among
+    the records the reader yields (fasta.read_records), start / end = 0-based half-open coordinates on the record's
+    forward strand, strand '+' (the window as written) or '-' (its reverse complement), sequence = the k-mer as the
+    alignment lists it for that genome.  Rows in (region, file in command-line order, record_index, start, strand) order.
+    For every group, genome label and sequence there are as many rows as the label occurs in that Amplicon's labels."""
+    from . import _native
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    flanks = _group_flanks(groups, Le, Re)
+    if len(flanks) == 0:
+        return np.empty(0, dtype=LOCATION)
+    from concurrent.futures import ThreadPoolExecutor
+    parts = []
+    # (the next file is read and inflated on a host thread while the device holds the current one: two texts at most)
+    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
+        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=(1 << 33) - 65)   # (the packed path's limit, KR_MAX_BASES)
+        eng.locate_table(flanks)
+        ahead = pool.submit(fasta.read_text, files[0]) if files else None
+        for fi, path in enumerate(files):
+            read = ahead.result()
+            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
+            hits, rows, seps, names, rna = _locate_genome(eng, path, read, k, omit_soft)
+            del read
+            if len(hits) == 0:
+                continue
+            pos = hits["pos"].astype(np.int64)
+            ri = np.searchsorted(seps.astype(np.int64), pos)
+            rec_start = np.where(ri > 0, seps.astype(np.int64)[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
+            if rna:
+                rows = np.where(rows == ord("T"), np.uint8(ord("U")), rows)
+            part = np.empty(len(hits), dtype=LOCATION)
+            part["region"] = hits["group"]
+            part["file"] = path
+            part["record"] = np.asarray(names, dtype=object)[ri]
+            part["record_index"] = ri
+            part["start"] = pos - rec_start
+            part["end"] = part["start"] + k
+            part["strand"] = np.where(hits["strand"] == 0, "+", "-")
+            part["sequence"] = np.ascontiguousarray(rows).view(f"S{k}").ravel().astype(f"U{k}").astype(object)
+            parts.append((fi, part))
+    if not parts:
+        return np.empty(0, dtype=LOCATION)
+    out = np.concatenate([p for _, p in parts])
+    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p in parts])
+    # (a file's rows are in (position, strand) order already: a stable sort by (region, file) keeps it)
+    order = np.lexsort((fidx, out["region"]))
+    return out[order]
+
+
+def write_locations(path, locs):
+    """the TSV of --out_locations: LOCATION_HEADER, then a line per row"""
+    with open(path, "w") as f:
+        f.write(LOCATION_HEADER + "\n")
+        f.writelines(f"{r}\t{fn}\t{rec}\t{ri}\t{s}\t{e}\t{st}\t{seq}\n"
+                     for r, fn, rec, ri, s, e, st, seq in zip(locs["region"].tolist(), locs["file"], locs["record"],
+                                                               locs["record_index"].tolist(), locs["start"].tolist(),
+                                                               locs["end"].tolist(), locs["strand"], locs["sequence"]))
+
+
+# ----------------------------------------------------------------------------
 # stage functions (reference signatures)
 # ----------------------------------------------------------------------------
 def _hit_windows(sel, text, k):
@@ -1593,6 +1707,11 @@ def build_parser():
                    help="Write results as human-readable alignments to a file. (default: do not write alignment output)")
     p.add_argument("-s", "--out_csv", type=str, metavar="PATH",
                    help="Write results to as a CSV (comma-separated value) file. (default: print to screen (stdout))")
+    p.add_argument("--out_locations", type=str, metavar="PATH",
+                   help="Also write where every diagnostic region lies in every genome, as a tab-separated file:\n"
+                        "region, file, record, record_index, start, end (0-based, half-open), strand, sequence.\n"
+                        "A separate pass that reads every input again (and inflates again a file the GPU inflated);\n"
+                        "not with --primer3. (default: no locations, no extra pass)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -1646,6 +1765,10 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)
     args = deduce_geometry(args, parser)
+    if args.out_locations is not None and args.primer3:
+        print("ERROR: --out_locations cannot be combined with --primer3 (the regions Primer3 keeps are not located)",
+              file=sys.stderr)
+        sys.exit(2)
     if args.primer3:
         from . import primers
         if not primers.available():
@@ -1663,8 +1786,10 @@ def main(argv=None):
         print(file=sys.stderr)
     devices = [int(x) for x in str(args.devices).split(",")] if getattr(args, "devices", None) else None
     from . import distributed as _dist
-    launch_world = _dist.env_rank_world()[2]     # torchrun / mpirun / srun alike (one place decides: distributed.py)
+    _rank, local_rank, launch_world = _dist.env_rank_world()   # torchrun / mpirun / srun alike (one place decides: distributed.py)
+    locate_device = args.device
     if devices and len(devices) > 1 and launch_world == 1:
+        locate_device = devices[0]
         # one process, a thread per device
         groups, stats = find_regions_multi_device(args.files, args.outgroup, args.conserved_left,
                                                   args.conserved_right, args.amplicon, devices,
@@ -1677,6 +1802,9 @@ def main(argv=None):
                                                  verbose=args.verbose)
         if groups is None:
             return 0                     # rank 0 writes the output
+        locate_device = local_rank
+        if os.environ.get("KRISP_COMM_TRANSPORT", "rccl") == "dir":
+            locate_device %= max(1, int(os.environ.get("KRISP_VISIBLE_GPUS", "1")))
     else:
         groups, stats = find_regions(args.files, args.outgroup, args.conserved_left, args.conserved_right,
                                      args.amplicon, omit_soft=args.omit_soft, device=args.device,
@@ -1699,6 +1827,13 @@ def main(argv=None):
     if args.out_align is not None:
         with open(args.out_align, "w") as f:
             f.write(align_text)
+    if args.out_locations is not None:
+        # (every group is located, also those a stopped renderer left out of the CSV: amplicon.RendererStopped)
+        if args.verbose:
+            print("Locating the regions in every genome ... ", file=sys.stderr)
+        write_locations(args.out_locations,
+                        locate_regions(groups, args.files, args.outgroup, args.conserved_left, args.conserved_right,
+                                       args.amplicon, omit_soft=args.omit_soft, device=locate_device))
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
