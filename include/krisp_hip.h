@@ -296,6 +296,33 @@ int64_t kr_locate_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
  * offset) with them without fetching the bases.  Returns their number; out == NULL: the number only */
 int64_t kr_locate_seps(kr_ctx*, int id, uint64_t* out, size_t cap);
 
+/* ---- near matches: the windows within Hamming distance M of an ingroup window (krisp_fasta --out_near) ---------------
+ * No seam in the reference: its k-mer intersection sees a window only where both conserved flanks are equal base for
+ * base.  This pass reports, for every genome, every window (kstream.py:617-677's window rules, both strands through
+ * COMP_MAP, as the locate pass) that differs from a target -- the L+D+R letters of an ingroup window of a diagnostic
+ * region -- in at most M columns, wherever it lies.  It runs in the locate context (kr_set_params_locate; the genome is
+ * uploaded by the same entry points, kr_locate_seps lists its records), on the device in csrc/k_near.inc: pigeonhole
+ * seeds (the columns cut into M + 1 pieces; a near window equals the target in one of them) filter, a byte-by-byte
+ * comparison decides.
+ *
+ * kr_near_table: ntargets rows of L+D+R bytes (upper case, U written as T), row i = target i; 0 <= mismatches <= 3 and
+ * mismatches < L+D+R (KR_ERR_PARAM otherwise).  Builds the text of every target and its reverse complement, the table of
+ * (piece, hash of the piece's bytes) -> the range of the entry list with that piece, and the membership bitmap the scan
+ * keeps in LDS.  Returns the number of slots; KR_ERR_CAPACITY for 2^24 targets or more, or a table that does not fit. */
+int64_t kr_near_table(kr_ctx*, const uint8_t* targets, uint64_t ntargets, int mismatches);
+/* one hit: the target (row of kr_near_table), strand 0 = the window as written ('+'), 1 = its reverse complement ('-'),
+ * the columns in which the strand's window differs from the target, those of them in the conserved flanks (the first L
+ * and the last R columns of the target), pos = the window's first base in the uploaded bases (separators counted) */
+typedef struct { uint32_t target; uint8_t strand, mismatches, flank_mismatches, pad; uint64_t pos; } kr_near_hit;
+/* scans uploaded genome `id` against the table: returns the number of hits, kept on the device for kr_near_fetch, in
+ * position order (at one position: by seed piece, then by the table's entry order; a (target, strand, pos) occurs once).
+ * Counted, scanned, written: the same bytes on every run.  KR_ERR_CAPACITY for 2^32 hits or more, or hits that do not fit. */
+int64_t kr_near_scan(kr_ctx*, int id);
+int64_t kr_near_fetch(kr_ctx*, kr_near_hit* out, size_t cap);
+/* the hits' windows as text, as kr_locate_windows gives the locate pass's: row i = the L+D+R letters of hit i, upper
+ * case, the reverse complement for strand 1.  Returns the number of rows; rows == NULL: size query */
+int64_t kr_near_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

@@ -18,6 +18,8 @@ CAND = np.dtype([("prefix", "<u8"), ("in_mask", "<u8"), ("out_mask", "<u8")])
 RECORD = np.dtype([("key", "<u8"), ("genome", "<u4"), ("count", "<u4")])
 WIDE_HIT = np.dtype([("cand", "<u4"), ("genome", "<u4"), ("pos", "<u4"), ("strand", "<u4")])
 LOC_HIT = np.dtype([("group", "<u4"), ("strand", "<u4"), ("pos", "<u8")])     # kr_loc_hit
+NEAR_HIT = np.dtype([("target", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("flank_mismatches", "u1"), ("pad", "u1"),
+                     ("pos", "<u8")])                                          # kr_near_hit
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -93,6 +95,10 @@ SYMBOLS = [
     ("kr_locate_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_locate_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_locate_seps", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t]),
+    ("kr_near_table", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int]),
+    ("kr_near_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_near_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_near_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -663,6 +669,26 @@ class Engine:
         out = np.empty(max(n, 1), dtype=np.uint64)
         if n:
             self._check(self.lib.kr_locate_seps(self.ctx, gid, _ptr(out), n), "kr_locate_seps")
+        return out[:n]
+
+    def near_table(self, targets, mismatches):
+        """targets: uint8 [n, L+D+R] (upper case, T for U), in a locate context -> slots of the seed table (kr_near_table)"""
+        t = np.ascontiguousarray(targets, dtype=np.uint8)
+        return self._check(self.lib.kr_near_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches), "kr_near_table")
+
+    def near(self, gid):
+        """NEAR_HIT array of uploaded genome gid against the seed table, in position order (kr_near_scan)"""
+        n = self._check(self.lib.kr_near_scan(self.ctx, gid), "kr_near_scan")
+        out = np.empty(max(n, 1), dtype=NEAR_HIT)
+        self._check(self.lib.kr_near_fetch(self.ctx, _ptr(out), n), "kr_near_fetch")
+        return out[:n]
+
+    def near_windows(self, k):
+        """the latest near()'s windows as text, cut on the device: uint8 [nhits, k] (kr_near_windows)"""
+        n = self._check(self.lib.kr_near_windows(self.ctx, None, 0), "kr_near_windows")
+        out = np.empty((max(n, 1), k), dtype=np.uint8)
+        if n:
+            self._check(self.lib.kr_near_windows(self.ctx, _ptr(out), out.nbytes), "kr_near_windows")
         return out[:n]
 
     # ---- timing

@@ -206,6 +206,14 @@ struct kr_ctx {
         int gid = -1;                   // the genome of the latest kr_locate_scan
         DevBuf arena, table, bitmap, tcount, toff, hits, seps, rows;
     } loc;
+    // the near-match pass (kr_near_*: h_near.inc), in the locate context: it shares loc's geometry, tcount and toff
+    struct Near {
+        int M = 0;
+        u64 ntargets = 0, slots = 0;
+        int64_t nhits = -1;
+        int gid = -1;                   // the genome of the latest kr_near_scan
+        DevBuf arena, table, list, bitmap, flag, hits, rows;
+    } near;
 };
 
 static int fail(kr_ctx* c, int code, const char* fmt, ...) {
@@ -501,6 +509,9 @@ void kr_destroy(kr_ctx* c) {
         auto& l = c->loc;
         DevBuf* lb[] = {&l.arena, &l.table, &l.bitmap, &l.tcount, &l.toff, &l.hits, &l.seps, &l.rows};
         for (DevBuf* b : lb) release(c, *b);
+        auto& nr = c->near;
+        DevBuf* nb[] = {&nr.arena, &nr.table, &nr.list, &nr.bitmap, &nr.flag, &nr.hits, &nr.rows};
+        for (DevBuf* b : nb) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);
     for (auto e : c->pool) (void)hipEventDestroy(e);

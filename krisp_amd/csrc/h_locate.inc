@@ -19,6 +19,8 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     l.omit = softmask_mode == KR_SOFT_OMIT;
     l.ngroups = l.slots = 0;
     l.nhits = -1;
+    c->near.slots = c->near.ntargets = 0;       // (a table of another geometry: kr_near_table again)
+    c->near.nhits = -1;
     c->wide.on = false;
     c->max_bases = max_bases;
     c->have_params = true;

@@ -1335,6 +1335,132 @@ def write_locations(path, locs):
 
 
 # ----------------------------------------------------------------------------
+# near matches of the ingroup windows in every genome (--out_near)
+# ----------------------------------------------------------------------------
+NEAR_HEADER = "region\ttarget\tfile\trecord\trecord_index\tstart\tend\tstrand\tmismatches\tflank_mismatches\tsequence"
+NEAR = np.dtype([("region", "<u4"), ("target", "O"), ("file", "O"), ("record", "O"), ("record_index", "<i8"),
+                 ("start", "<i8"), ("end", "<i8"), ("strand", "U1"), ("mismatches", "<u4"), ("flank_mismatches", "<u4"),
+                 ("sequence", "O")])
+NEAR_MAX_MISMATCHES = 3
+
+
+def near_refusal(L, R, amplicon_len, mismatches):
+    """why the near-match pass does not take this geometry and distance (one line), or None"""
+    k = amplicon_len
+    if mismatches < 0 or mismatches > NEAR_MAX_MISMATCHES:
+        return f"--near-mismatches must lie between 0 and {NEAR_MAX_MISMATCHES} (got {mismatches})"
+    if mismatches >= k:
+        return f"--near-mismatches must be smaller than the amplicon length {k} (got {mismatches})"
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    if _is_wide(Le, De, Re):
+        return (f"--out_near takes amplicons of at most 32 bases with at most 16 diagnostic bases (got {Le}/{De}/{Re}): for "
+                "longer amplicons near matches are a question of primers, not of Hamming distance")
+    return None
+
+
+def near_targets(groups, ingroup_labels):
+    """The targets of the near-match pass: for group i, the sequence (U written as T) of every Amplicon that has at least
+    one ingroup label -- of every Amplicon when ingroup_labels is None (a run without outgroup) --, equal texts once,
+    ordered by their bytes.  `groups` in any form find_regions* returns.  -> list of (i, text), ordered by (i, text)."""
+    ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
+    out = []
+    for i, g in enumerate(groups):
+        texts = {a.sequence.replace("U", "T").replace("u", "t") for a in g
+                 if ingroup is None or not ingroup.isdisjoint(a.labels)}
+        out.extend((i, t) for t in sorted(texts, key=lambda t: t.encode("ascii")))
+    return out
+
+
+def near_matches(groups, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1, omit_soft=False, device=0):
+    """Every window of every input genome within Hamming distance `mismatches` of a target (near_targets: the ingroup
+    windows of the diagnostic regions), on both strands, wherever it lies -- what the exact k-mer intersection cannot
+    see: a window whose conserved FLANK differs by a substitution or two.  `groups` as find_regions* returned them, the
+    same files and geometry.  A separate pass over the inputs on one device in the manner of locate_regions
+    (kr_near_*: pigeonhole seeds filter, a byte comparison decides).  Returns a NEAR array: region, target (DNA letters),
+    file, record, record_index, start, end, strand, sequence as in LOCATION; mismatches = the differing columns,
+    flank_mismatches = those of them in the conserved flanks.  Rows in (region, target, file in command-line order,
+    record_index, start, '+' before '-') order.  Packed geometries only, 0 <= mismatches <= 3 (ValueError otherwise)."""
+    why = near_refusal(L, R, amplicon_len, mismatches)
+    if why is not None:
+        raise ValueError(why)
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    ingroup = [simplename(f) for f in ingroup_files] if len(outgroup_files) else None
+    targets = near_targets(groups, ingroup)
+    if not targets:
+        return np.empty(0, dtype=NEAR)
+    t_region = np.array([i for i, _ in targets], dtype=np.uint32)
+    t_text = np.array([t for _, t in targets], dtype=object)
+    t_bytes = np.frombuffer("".join(t for _, t in targets).encode("ascii"), dtype=np.uint8).reshape(-1, k)
+    from concurrent.futures import ThreadPoolExecutor
+    parts = []
+    # (the next file is read and inflated on a host thread while the device holds the current one: two texts at most)
+    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
+        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=(1 << 33) - 65)
+        eng.near_table(t_bytes, mismatches)
+        ahead = pool.submit(fasta.read_text, files[0]) if files else None
+        for fi, path in enumerate(files):
+            read = ahead.result()
+            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
+            text, universal = read
+            while True:
+                try:
+                    n, rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
+                    break
+                except fasta.GzipTextLonger:
+                    text, universal = fasta.read_text(path)
+            hits = eng.near(0)
+            if len(hits) == 0:
+                del read, text
+                continue
+            rows = eng.near_windows(k)
+            seps = eng.locate_seps(0).astype(np.int64)
+            names = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
+            del read, text
+            if len(names) != len(seps) + 1:
+                raise RuntimeError(f"{path}: {len(names)} record IDs, but the device's bases hold {len(seps) + 1} records")
+            pos = hits["pos"].astype(np.int64)
+            ri = np.searchsorted(seps, pos)
+            rec_start = np.where(ri > 0, seps[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
+            if rna:
+                rows = np.where(rows == ord("T"), np.uint8(ord("U")), rows)
+            tg = hits["target"].astype(np.int64)
+            # (a file's hits come in position order; within the table they go by target, then position, then strand)
+            order = np.lexsort((hits["strand"], pos, tg))
+            part = np.empty(len(hits), dtype=NEAR)
+            part["region"] = t_region[tg]
+            part["target"] = t_text[tg]
+            part["file"] = path
+            part["record"] = np.asarray(names, dtype=object)[ri]
+            part["record_index"] = ri
+            part["start"] = pos - rec_start
+            part["end"] = part["start"] + k
+            part["strand"] = np.where(hits["strand"] == 0, "+", "-")
+            part["mismatches"] = hits["mismatches"]
+            part["flank_mismatches"] = hits["flank_mismatches"]
+            part["sequence"] = np.ascontiguousarray(rows).view(f"S{k}").ravel().astype(f"U{k}").astype(object)
+            parts.append((fi, part[order], tg[order]))
+    if not parts:
+        return np.empty(0, dtype=NEAR)
+    out = np.concatenate([p for _, p, _ in parts])
+    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p, _ in parts])
+    tidx = np.concatenate([t for _, _, t in parts])
+    return out[np.lexsort((fidx, tidx))]       # (stable: a file's rows of one target keep their order)
+
+
+def write_near(path, rows):
+    """the TSV of --out_near: NEAR_HEADER, then a line per row"""
+    with open(path, "w") as f:
+        f.write(NEAR_HEADER + "\n")
+        f.writelines(f"{r}\t{t}\t{fn}\t{rec}\t{ri}\t{s}\t{e}\t{st}\t{mm}\t{fm}\t{seq}\n"
+                     for r, t, fn, rec, ri, s, e, st, mm, fm, seq in zip(
+                         rows["region"].tolist(), rows["target"], rows["file"], rows["record"], rows["record_index"].tolist(),
+                         rows["start"].tolist(), rows["end"].tolist(), rows["strand"], rows["mismatches"].tolist(),
+                         rows["flank_mismatches"].tolist(), rows["sequence"]))
+
+
+# ----------------------------------------------------------------------------
 # stage functions (reference signatures)
 # ----------------------------------------------------------------------------
 def _hit_windows(sel, text, k):
@@ -1712,6 +1838,14 @@ def build_parser():
                         "region, file, record, record_index, start, end (0-based, half-open), strand, sequence.\n"
                         "A separate pass that reads every input again (and inflates again a file the GPU inflated);\n"
                         "not with --primer3. (default: no locations, no extra pass)")
+    p.add_argument("--out_near", type=str, metavar="PATH",
+                   help="Also write every window of every genome within --near-mismatches substitutions of an ingroup window\n"
+                        "of a diagnostic region (both strands, wherever it lies), as a tab-separated file: region, target, file,\n"
+                        "record, record_index, start, end, strand, mismatches, flank_mismatches, sequence.  A separate pass that\n"
+                        "reads every input again; amplicons of at most 32 bases; not with --primer3.\n"
+                        "(default: no near matches, no extra pass)")
+    p.add_argument("--near-mismatches", type=int, default=None, metavar="INT",
+                   help="Hamming distance of --out_near: 0 .. 3, smaller than the amplicon length (default: 1)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -1769,6 +1903,19 @@ def main(argv=None):
         print("ERROR: --out_locations cannot be combined with --primer3 (the regions Primer3 keeps are not located)",
               file=sys.stderr)
         sys.exit(2)
+    if args.out_near is not None and args.primer3:
+        print("ERROR: --out_near cannot be combined with --primer3 (the regions Primer3 keeps are not searched)", file=sys.stderr)
+        sys.exit(2)
+    if args.near_mismatches is not None and args.out_near is None:
+        print("ERROR: --near-mismatches needs --out_near", file=sys.stderr)
+        sys.exit(2)
+    if args.out_near is not None:
+        if args.near_mismatches is None:
+            args.near_mismatches = 1
+        why = near_refusal(args.conserved_left, args.conserved_right, args.amplicon, args.near_mismatches)
+        if why is not None:
+            print("ERROR: " + why, file=sys.stderr)
+            sys.exit(2)
     if args.primer3:
         from . import primers
         if not primers.available():
@@ -1834,6 +1981,14 @@ def main(argv=None):
         write_locations(args.out_locations,
                         locate_regions(groups, args.files, args.outgroup, args.conserved_left, args.conserved_right,
                                        args.amplicon, omit_soft=args.omit_soft, device=locate_device))
+    if args.out_near is not None:
+        # (as the locations: for every group, on one device, written by rank 0)
+        if args.verbose:
+            print(f"Searching every genome for windows within {args.near_mismatches} mismatches of the ingroup's ... ",
+                  file=sys.stderr)
+        write_near(args.out_near,
+                   near_matches(groups, args.files, args.outgroup, args.conserved_left, args.conserved_right, args.amplicon,
+                                mismatches=args.near_mismatches, omit_soft=args.omit_soft, device=locate_device))
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
