@@ -308,7 +308,9 @@ int64_t kr_locate_seps(kr_ctx*, int id, uint64_t* out, size_t cap);
  * kr_near_table: ntargets rows of L+D+R bytes (upper case, U written as T), row i = target i; 0 <= mismatches <= 3 and
  * mismatches < L+D+R (KR_ERR_PARAM otherwise).  Builds the text of every target and its reverse complement, the table of
  * (piece, hash of the piece's bytes) -> the range of the entry list with that piece, and the membership bitmap the scan
- * keeps in LDS.  Returns the number of slots; KR_ERR_CAPACITY for 2^24 targets or more, or a table that does not fit. */
+ * keeps in LDS.  Equal rows are not refused (kr_locate_table refuses equal flank pairs): each stays a target of its own,
+ * and a window near one is a hit of each.  Returns the number of slots; KR_ERR_CAPACITY for 2^24 targets or more, or a
+ * table that does not fit. */
 int64_t kr_near_table(kr_ctx*, const uint8_t* targets, uint64_t ntargets, int mismatches);
 /* one hit: the target (row of kr_near_table), strand 0 = the window as written ('+'), 1 = its reverse complement ('-'),
  * the columns in which the strand's window differs from the target, those of them in the conserved flanks (the first L
