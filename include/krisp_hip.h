@@ -325,6 +325,42 @@ int64_t kr_near_fetch(kr_ctx*, kr_near_hit* out, size_t cap);
  * case, the reverse complement for strand 1.  Returns the number of rows; rows == NULL: size query */
 int64_t kr_near_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
 
+/* ---- predicted PCR products of the regions' flanks (krisp_fasta --out_products) ---------------------------------------
+ * No seam in the reference.  The conserved flanks of a long amplicon are primer regions; this pass reports, for every
+ * genome, every pair of SITES that would amplify: a site of a text X is a window of len(X) bases (the locate pass's window
+ * rules) within Hamming distance M of X.  A product of the pair (A, B) on one record is a site of A at s1 and a site of B
+ * at s2 (strand 0), or a site of rc(B) at s1 and a site of rc(A) at s2 (strand 1, rc through COMP_MAP), with
+ * s2 >= s1 + the first site's length and s2 + the second site's length - s1 <= max_product; whatever lies between the
+ * sites is not looked at.  It runs in the locate context (kr_set_params_locate: its L and R are the lengths of the left
+ * and right texts, D plays no part), on the device in csrc/k_products.inc: pigeonhole seeds per text length filter, a
+ * byte comparison decides, the sites of one genome are joined in position order.
+ *
+ * kr_products_table: nleft rows of L bytes and nright rows of R bytes (upper case, U written as T; equal rows are not
+ * refused, each stays a text of its own), npairs rows of two u32 (row of left, row of right): pair p is what a product's
+ * `pair` names.  0 <= mismatches <= 3 and mismatches < min(L, R), max_product >= L + R, indices in range and no pair
+ * twice (KR_ERR_PARAM otherwise).  Returns the number of slots of the seed table; KR_ERR_CAPACITY for 2^24 texts or
+ * more, or a table that does not fit. */
+int64_t kr_products_table(kr_ctx*, const uint8_t* left, uint64_t nleft, const uint8_t* right, uint64_t nright,
+                          const uint32_t* pairs, uint64_t npairs, int mismatches, uint32_t max_product);
+/* one site: entry 2 i = left text i as written, 2 i + 1 = its reverse complement, 2 nleft + 2 j = right text j,
+ * 2 nleft + 2 j + 1 = its reverse complement; the columns in which the window differs from the entry's text, those of
+ * them in the min(5, length) columns at the primer's 3' end (the last columns of a left text and the first of a right
+ * one, as the amplicon's strand reads them); pos = the window's first base in the uploaded bases */
+typedef struct { uint64_t pos; uint32_t entry; uint8_t mismatches, end_mismatches; uint16_t pad; } kr_product_site;
+/* one product: pos = the first base of its first site, length = to the last base of its second site, pair = row of
+ * `pairs`, strand 0 / 1 as above, the mismatches of the left text's site (A or rc(A)) and the right text's, and those of
+ * them at the 3' ends */
+typedef struct { uint64_t pos; uint32_t length, pair; uint8_t strand, left_mm, right_mm, left_end_mm, right_end_mm, pad[3]; } kr_product_hit;
+/* scans uploaded genome `id`: lists its separators, its sites (position order; at one position by text length, seed
+ * piece and the table's entry order; an (entry, pos) occurs once), their records, and joins them.  Returns the number of
+ * products, kept on the device with the sites.  Counted, scanned, written: the same bytes on every run.
+ * KR_ERR_CAPACITY for 2^32 sites or products or more, or lists that do not fit. */
+int64_t kr_products_scan(kr_ctx*, int id);
+/* the products of the latest scan in (pos, length, strand, pair) order */
+int64_t kr_products_fetch(kr_ctx*, kr_product_hit* out, size_t cap);
+/* the sites of the latest scan, as the device lists them.  Returns their number; out == NULL: the number only */
+int64_t kr_products_sites(kr_ctx*, kr_product_site* out, size_t cap);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

@@ -20,6 +20,10 @@ WIDE_HIT = np.dtype([("cand", "<u4"), ("genome", "<u4"), ("pos", "<u4"), ("stran
 LOC_HIT = np.dtype([("group", "<u4"), ("strand", "<u4"), ("pos", "<u8")])     # kr_loc_hit
 NEAR_HIT = np.dtype([("target", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("flank_mismatches", "u1"), ("pad", "u1"),
                      ("pos", "<u8")])                                          # kr_near_hit
+PRODUCT_SITE = np.dtype([("pos", "<u8"), ("entry", "<u4"), ("mismatches", "u1"), ("end_mismatches", "u1"),
+                         ("pad", "<u2")])                                      # kr_product_site
+PRODUCT_HIT = np.dtype([("pos", "<u8"), ("length", "<u4"), ("pair", "<u4"), ("strand", "u1"), ("left_mm", "u1"),
+                        ("right_mm", "u1"), ("left_end_mm", "u1"), ("right_end_mm", "u1"), ("pad", "u1", (3,))])   # kr_product_hit
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -99,6 +103,10 @@ SYMBOLS = [
     ("kr_near_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_near_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_near_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_products_table", _c.c_int64, [_P, _P, _c.c_uint64, _P, _c.c_uint64, _P, _c.c_uint64, _c.c_int, _c.c_uint32]),
+    ("kr_products_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_products_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_products_sites", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -689,6 +697,31 @@ class Engine:
         out = np.empty((max(n, 1), k), dtype=np.uint8)
         if n:
             self._check(self.lib.kr_near_windows(self.ctx, _ptr(out), out.nbytes), "kr_near_windows")
+        return out[:n]
+
+    def products_table(self, left, right, pairs, mismatches, max_product):
+        """left: uint8 [nl, L], right: uint8 [nr, R] (upper case, T for U), pairs: [np, 2] rows of (left, right), in a
+        locate context whose L and R are the texts' lengths -> slots of the seed table (kr_products_table)"""
+        lf = np.ascontiguousarray(left, dtype=np.uint8)
+        rt = np.ascontiguousarray(right, dtype=np.uint8)
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        return self._check(self.lib.kr_products_table(self.ctx, _ptr(lf) if lf.size else None, len(lf),
+                                                      _ptr(rt) if rt.size else None, len(rt), _ptr(pr) if pr.size else None,
+                                                      len(pr), mismatches, max_product), "kr_products_table")
+
+    def products(self, gid):
+        """PRODUCT_HIT array of uploaded genome gid in (pos, length, strand, pair) order (kr_products_scan)"""
+        n = self._check(self.lib.kr_products_scan(self.ctx, gid), "kr_products_scan")
+        out = np.empty(max(n, 1), dtype=PRODUCT_HIT)
+        self._check(self.lib.kr_products_fetch(self.ctx, _ptr(out), n), "kr_products_fetch")
+        return out[:n]
+
+    def product_sites(self):
+        """the latest products()'s primer sites as the device lists them: PRODUCT_SITE, position order (kr_products_sites)"""
+        n = self._check(self.lib.kr_products_sites(self.ctx, None, 0), "kr_products_sites")
+        out = np.empty(max(n, 1), dtype=PRODUCT_SITE)
+        if n:
+            self._check(self.lib.kr_products_sites(self.ctx, _ptr(out), n), "kr_products_sites")
         return out[:n]
 
     # ---- timing

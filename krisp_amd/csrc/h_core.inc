@@ -214,6 +214,14 @@ struct kr_ctx {
         int gid = -1;                   // the genome of the latest kr_near_scan
         DevBuf arena, table, list, bitmap, flag, hits, rows;
     } near;
+    // the product pass (kr_products_*: h_products.inc), in the locate context: loc.L / loc.R are the texts' lengths
+    struct Prod {
+        int M = 0;
+        u32 max_product = 0;
+        u64 nleft = 0, nright = 0, npairs = 0, slots = 0;
+        int64_t nsites = -1, nhits = -1;
+        DevBuf arena, table, list, bitmap, flag, pairkeys, pairidx, tcount, toff, seps, sites, rec, hits;
+    } prod;
 };
 
 static int fail(kr_ctx* c, int code, const char* fmt, ...) {
@@ -512,6 +520,10 @@ void kr_destroy(kr_ctx* c) {
         auto& nr = c->near;
         DevBuf* nb[] = {&nr.arena, &nr.table, &nr.list, &nr.bitmap, &nr.flag, &nr.hits, &nr.rows};
         for (DevBuf* b : nb) release(c, *b);
+        auto& pr = c->prod;
+        DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.flag, &pr.pairkeys, &pr.pairidx, &pr.tcount, &pr.toff,
+                        &pr.seps, &pr.sites, &pr.rec, &pr.hits};
+        for (DevBuf* b : pb) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);
     for (auto e : c->pool) (void)hipEventDestroy(e);

@@ -21,6 +21,8 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     l.nhits = -1;
     c->near.slots = c->near.ntargets = 0;       // (a table of another geometry: kr_near_table again)
     c->near.nhits = -1;
+    c->prod.slots = 0;                          // (likewise: kr_products_table again)
+    c->prod.nsites = c->prod.nhits = -1;
     c->wide.on = false;
     c->max_bases = max_bases;
     c->have_params = true;

@@ -1461,6 +1461,126 @@ def write_near(path, rows):
 
 
 # ----------------------------------------------------------------------------
+# predicted PCR products of the regions' flanks in every genome (--out_products)
+# ----------------------------------------------------------------------------
+PRODUCT_HEADER = ("region\tfile\trecord\trecord_index\tstart\tend\tstrand\tlength\tleft_mismatches\tright_mismatches\t"
+                  "left_end_mismatches\tright_end_mismatches")
+PRODUCT = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"),
+                    ("end", "<i8"), ("strand", "U1"), ("length", "<i8"), ("left_mismatches", "<u4"), ("right_mismatches", "<u4"),
+                    ("left_end_mismatches", "<u4"), ("right_end_mismatches", "<u4")])
+PRODUCT_MAX_MISMATCHES = 3
+PRODUCT_MIN_PRIMER = 10      # bases of a flank from which it is searched as a primer (a condition, not a measurement)
+PRODUCT_END = 5              # the "last five 3' bases" of --max_end_gc: where the end mismatches are counted
+
+
+def products_refusal(L, R, amplicon_len, mismatches, max_product):
+    """why the product pass does not take this geometry, distance and product length (one line), or None"""
+    k = amplicon_len
+    if mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES:
+        return f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    if min(Le, Re) < PRODUCT_MIN_PRIMER:
+        return (f"--out_products takes conserved flanks of at least {PRODUCT_MIN_PRIMER} bases each (got {Le}/{De}/{Re}): a "
+                "shorter text with a mismatch or two binds nearly everywhere")
+    if max_product < Le + Re:
+        return f"--max-product must be at least the two flanks together, {Le + Re} bases (got {max_product})"
+    if max_product >= 1 << 31:
+        return f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    return None
+
+
+def predict_products(groups, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1, max_product=1000,
+                     omit_soft=False, device=0):
+    """In-silico PCR of every region's conserved flanks against every input genome: a product is a window within
+    `mismatches` substitutions of the left flank and one within as many of the right flank on ONE record, facing each
+    other ('+': left ... right as written; '-': rc(right) ... rc(left)), not overlapping, at most `max_product` bases
+    from the first base of the first to the last base of the second -- whatever lies between them.  What the exact
+    k-mer intersection cannot see: a genome whose flank differs by a substitution, or whose diagnostic stretch is longer
+    or shorter, still amplifies.  `groups` as find_regions* returned them, the same files and geometry.  A separate pass
+    over the inputs on one device in the manner of locate_regions (kr_products_*).  Returns a PRODUCT array: region, file,
+    record, record_index, start, end, strand as in LOCATION (end - start = length); left / right_mismatches = the distance
+    of the left flank's and the right flank's window, left / right_end_mismatches = those of them in the PRODUCT_END
+    columns at the primer's 3' end (the last of the left flank, the first of the right).  Rows in (region, file in
+    command-line order, record_index, start, end, '+' before '-') order.  Flanks of at least PRODUCT_MIN_PRIMER bases,
+    0 <= mismatches <= 3 (ValueError otherwise)."""
+    why = products_refusal(L, R, amplicon_len, mismatches, max_product)
+    if why is not None:
+        raise ValueError(why)
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    flanks = _group_flanks(groups, Le, Re)
+    if len(flanks) == 0:
+        return np.empty(0, dtype=PRODUCT)
+    # (distinct texts once: regions that overlap share a flank; region i is pair i)
+    left, li = np.unique(flanks[:, :Le], axis=0, return_inverse=True)
+    right, ri_ = np.unique(flanks[:, Le:], axis=0, return_inverse=True)
+    pairs = np.stack([li.ravel(), ri_.ravel()], axis=1).astype(np.uint32)
+    from concurrent.futures import ThreadPoolExecutor
+    parts = []
+    # (the next file is read and inflated on a host thread while the device holds the current one: two texts at most)
+    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
+        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=(1 << 33) - 65)
+        eng.products_table(left, right, pairs, mismatches, max_product)
+        ahead = pool.submit(fasta.read_text, files[0]) if files else None
+        for fi, path in enumerate(files):
+            read = ahead.result()
+            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
+            text, universal = read
+            while True:
+                try:
+                    n, _rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
+                    break
+                except fasta.GzipTextLonger:
+                    text, universal = fasta.read_text(path)
+            hits = eng.products(0)
+            if len(hits) == 0:
+                del read, text
+                continue
+            seps = eng.locate_seps(0).astype(np.int64)
+            names = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
+            del read, text
+            if len(names) != len(seps) + 1:
+                raise RuntimeError(f"{path}: {len(names)} record IDs, but the device's bases hold {len(seps) + 1} records")
+            pos = hits["pos"].astype(np.int64)
+            ri = np.searchsorted(seps, pos)
+            rec_start = np.where(ri > 0, seps[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
+            part = np.empty(len(hits), dtype=PRODUCT)
+            part["region"] = hits["pair"]
+            part["file"] = path
+            part["record"] = np.asarray(names, dtype=object)[ri]
+            part["record_index"] = ri
+            part["start"] = pos - rec_start
+            part["length"] = hits["length"]
+            part["end"] = part["start"] + part["length"]
+            part["strand"] = np.where(hits["strand"] == 0, "+", "-")
+            part["left_mismatches"] = hits["left_mm"]
+            part["right_mismatches"] = hits["right_mm"]
+            part["left_end_mismatches"] = hits["left_end_mm"]
+            part["right_end_mismatches"] = hits["right_end_mm"]
+            parts.append((fi, part))
+    if not parts:
+        return np.empty(0, dtype=PRODUCT)
+    out = np.concatenate([p for _, p in parts])
+    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p in parts])
+    # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start) --:
+    # a stable sort by (region, file) keeps it)
+    return out[np.lexsort((fidx, out["region"]))]
+
+
+def write_products(path, rows):
+    """the TSV of --out_products: PRODUCT_HEADER, then a line per row"""
+    with open(path, "w") as f:
+        f.write(PRODUCT_HEADER + "\n")
+        f.writelines(f"{r}\t{fn}\t{rec}\t{ri}\t{s}\t{e}\t{st}\t{n}\t{lm}\t{rm}\t{le}\t{re_}\n"
+                     for r, fn, rec, ri, s, e, st, n, lm, rm, le, re_ in zip(
+                         rows["region"].tolist(), rows["file"], rows["record"], rows["record_index"].tolist(),
+                         rows["start"].tolist(), rows["end"].tolist(), rows["strand"], rows["length"].tolist(),
+                         rows["left_mismatches"].tolist(), rows["right_mismatches"].tolist(),
+                         rows["left_end_mismatches"].tolist(), rows["right_end_mismatches"].tolist()))
+
+
+# ----------------------------------------------------------------------------
 # stage functions (reference signatures)
 # ----------------------------------------------------------------------------
 def _hit_windows(sel, text, k):
@@ -1846,6 +1966,18 @@ def build_parser():
                         "(default: no near matches, no extra pass)")
     p.add_argument("--near-mismatches", type=int, default=None, metavar="INT",
                    help="Hamming distance of --out_near: 0 .. 3, smaller than the amplicon length (default: 1)")
+    p.add_argument("--out_products", type=str, metavar="PATH",
+                   help="Also write the predicted PCR products of every region's conserved flanks in every genome: a window\n"
+                        "within --primer-mismatches substitutions of the left flank and one of the right flank on one record,\n"
+                        "facing each other, at most --max-product bases from end to end (either strand), as a tab-separated\n"
+                        "file: region, file, record, record_index, start, end, strand, length, left_mismatches,\n"
+                        "right_mismatches, left_end_mismatches, right_end_mismatches (those in the five 3' bases).  A separate\n"
+                        "pass that reads every input again; flanks of at least 10 bases; not with --primer3.\n"
+                        "(default: no products, no extra pass)")
+    p.add_argument("--primer-mismatches", type=int, default=None, metavar="INT",
+                   help="substitutions allowed in each flank of --out_products: 0 .. 3 (default: 1)")
+    p.add_argument("--max-product", type=int, default=None, metavar="INT",
+                   help="longest product of --out_products in bases, at least the two flanks together (default: 1000)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -1913,6 +2045,22 @@ def main(argv=None):
         if args.near_mismatches is None:
             args.near_mismatches = 1
         why = near_refusal(args.conserved_left, args.conserved_right, args.amplicon, args.near_mismatches)
+        if why is not None:
+            print("ERROR: " + why, file=sys.stderr)
+            sys.exit(2)
+    if args.out_products is not None and args.primer3:
+        print("ERROR: --out_products cannot be combined with --primer3 (the primers Primer3 designs are not searched)", file=sys.stderr)
+        sys.exit(2)
+    for opt, val in (("--primer-mismatches", args.primer_mismatches), ("--max-product", args.max_product)):
+        if val is not None and args.out_products is None:
+            print(f"ERROR: {opt} needs --out_products", file=sys.stderr)
+            sys.exit(2)
+    if args.out_products is not None:
+        if args.primer_mismatches is None:
+            args.primer_mismatches = 1
+        if args.max_product is None:
+            args.max_product = 1000
+        why = products_refusal(args.conserved_left, args.conserved_right, args.amplicon, args.primer_mismatches, args.max_product)
         if why is not None:
             print("ERROR: " + why, file=sys.stderr)
             sys.exit(2)
@@ -1989,6 +2137,14 @@ def main(argv=None):
         write_near(args.out_near,
                    near_matches(groups, args.files, args.outgroup, args.conserved_left, args.conserved_right, args.amplicon,
                                 mismatches=args.near_mismatches, omit_soft=args.omit_soft, device=locate_device))
+    if args.out_products is not None:
+        # (as the locations: for every group, on one device, written by rank 0)
+        if args.verbose:
+            print(f"Predicting the products of the flanks with up to {args.primer_mismatches} mismatches each ... ", file=sys.stderr)
+        write_products(args.out_products,
+                       predict_products(groups, args.files, args.outgroup, args.conserved_left, args.conserved_right, args.amplicon,
+                                        mismatches=args.primer_mismatches, max_product=args.max_product,
+                                        omit_soft=args.omit_soft, device=locate_device))
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
