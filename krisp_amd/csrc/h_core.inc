@@ -204,15 +204,16 @@ struct kr_ctx {
         u64 ngroups = 0, slots = 0;
         int64_t nhits = -1;
         int gid = -1;                   // the genome of the latest kr_locate_scan
-        DevBuf arena, table, bitmap, tcount, toff, hits, seps, rows;
+        DevBuf arena, table, bitmap, hits, seps, rows;
+        DevBuf tcount, toff, flag;      // the two-pass scratch of all three passes (h_scan.inc: scan_two_pass)
     } loc;
-    // the near-match pass (kr_near_*: h_near.inc), in the locate context: it shares loc's geometry, tcount and toff
+    // the near-match pass (kr_near_*: h_near.inc), in the locate context: it shares loc's geometry and scratch
     struct Near {
         int M = 0;
         u64 ntargets = 0, slots = 0;
         int64_t nhits = -1;
         int gid = -1;                   // the genome of the latest kr_near_scan
-        DevBuf arena, table, list, bitmap, flag, hits, rows;
+        DevBuf arena, table, list, bitmap, hits, rows;
     } near;
     // the product pass (kr_products_*: h_products.inc), in the locate context: loc.L / loc.R are the texts' lengths
     struct Prod {
@@ -220,7 +221,7 @@ struct kr_ctx {
         u32 max_product = 0;
         u64 nleft = 0, nright = 0, npairs = 0, slots = 0;
         int64_t nsites = -1, nhits = -1;
-        DevBuf arena, table, list, bitmap, flag, pairkeys, pairidx, tcount, toff, seps, sites, rec, hits;
+        DevBuf arena, table, list, bitmap, pairkeys, pairidx, seps, sites, rec, hits;
     } prod;
 };
 
@@ -515,14 +516,13 @@ void kr_destroy(kr_ctx* c) {
     }
     {
         auto& l = c->loc;
-        DevBuf* lb[] = {&l.arena, &l.table, &l.bitmap, &l.tcount, &l.toff, &l.hits, &l.seps, &l.rows};
+        DevBuf* lb[] = {&l.arena, &l.table, &l.bitmap, &l.tcount, &l.toff, &l.flag, &l.hits, &l.seps, &l.rows};
         for (DevBuf* b : lb) release(c, *b);
         auto& nr = c->near;
-        DevBuf* nb[] = {&nr.arena, &nr.table, &nr.list, &nr.bitmap, &nr.flag, &nr.hits, &nr.rows};
+        DevBuf* nb[] = {&nr.arena, &nr.table, &nr.list, &nr.bitmap, &nr.hits, &nr.rows};
         for (DevBuf* b : nb) release(c, *b);
         auto& pr = c->prod;
-        DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.flag, &pr.pairkeys, &pr.pairidx, &pr.tcount, &pr.toff,
-                        &pr.seps, &pr.sites, &pr.rec, &pr.hits};
+        DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.pairkeys, &pr.pairidx, &pr.seps, &pr.sites, &pr.rec, &pr.hits};
         for (DevBuf* b : pb) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);

@@ -1,5 +1,6 @@
 // h_locate.inc -- part of krisp_hip.hip (one translation unit): host side of the locate pass (k_locate.inc): a context that
-// only uploads genomes, the flank table of the surviving groups, the scan of one genome, its record separators.
+// only uploads genomes, the flank table of the surviving groups, the scan of one genome, its record separators.  What it
+// shares with the near-match and product passes is h_scan.inc.
 // One genome is resident at a time (the caller uploads the next under the same id); beside it live the table (16 bytes a
 // slot, >= 2 slots a group), the flank text, the bitmap, the per-tile counts and the hits.
 
@@ -29,20 +30,9 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     return KR_OK;
 }
 
-static u32 loc_hash(const uint8_t* s, int m) {
-    u32 h = 0;
-    for (int i = 0; i < m; i++) h = h * LOC_HB + s[i];
-    return h;
-}
-
-static u32 loc_pow(int e) {
-    u32 r = 1;
-    for (int i = 0; i < e; i++) r *= LOC_HB;
-    return r;
-}
-
 int64_t kr_locate_table(kr_ctx* c, const uint8_t* flanks, uint64_t ngroups) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
     if (!flanks && ngroups) return fail(c, KR_ERR_PARAM, "kr_locate_table: null flanks");
     if (ngroups >= LOC_EMPTY) return fail(c, KR_ERR_CAPACITY, "kr_locate_table: %llu groups (the limit is %u)",
                                           (unsigned long long)ngroups, LOC_EMPTY - 1);
@@ -72,7 +62,6 @@ int64_t kr_locate_table(kr_ctx* c, const uint8_t* flanks, uint64_t ngroups) {
         const u32 b = (u32)(h >> (64 - LOC_BM_LOG));
         bm[b >> 5] |= 1u << (b & 31);
     }
-    int rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure(c, l.table, slots * sizeof(LocSlot))) || (rc = ensure(c, l.arena, ngroups * LR + 16)) ||
         (rc = ensure(c, l.bitmap, (size_t)LOC_BM_WORDS * 4)))
@@ -87,28 +76,16 @@ int64_t kr_locate_table(kr_ctx* c, const uint8_t* flanks, uint64_t ngroups) {
     return (int64_t)slots;
 }
 
-static size_t loc_lds_bytes(int k) {
-    const u32 tb = LOC_T * LOC_S + k - 1;
-    return (size_t)LOC_BM_WORDS * 4 + LOC_T * 4 + 256 + (((tb + 16) + ((tb + 16) >> LOC_SH) * 4 + 15) & ~15u);
-}
-
 int64_t kr_locate_scan(kr_ctx* c, int id) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
+    const Genome* G;
+    int rc;
+    if ((rc = scan_genome(c, id, c && c->loc.slots, "kr_locate_table first", &G))) return rc;
     auto& l = c->loc;
-    if (!l.slots) return fail(c, KR_ERR_STATE, "kr_locate_table first");
-    auto it = c->genomes.find(id);
-    if (it == c->genomes.end() || !it->second.uploaded) return fail(c, KR_ERR_STATE, "genome %d not uploaded", id);
-    const Genome& G = it->second;
-    HIPCHK(c, hipSetDevice(c->device));
     l.nhits = 0;
     l.gid = id;
-    const u64 n = G.n_bases, k = (u64)l.k;
-    const u64 nw = n >= k ? n - k + 1 : 0;
-    const u64 TP = (u64)LOC_T * LOC_S;
-    const u64 ntiles = (nw + TP - 1) / TP;
+    u64 nw;
+    const u64 n = G->n_bases, ntiles = scan_tiles(n, (u64)l.k, &nw);
     if (!ntiles || !l.ngroups) return 0;
-    int rc;
-    if ((rc = ensure(c, l.tcount, (ntiles + 1) * 4)) || (rc = ensure(c, l.toff, (ntiles + 1) * 8))) return rc;
     LocGeom lg;
     lg.L = (u32)l.L; lg.D = (u32)l.D; lg.R = (u32)l.R; lg.k = (u32)l.k; lg.omit = (u32)l.omit;
     u32 inv = LOC_HB;
@@ -116,100 +93,55 @@ int64_t kr_locate_scan(kr_ctx* c, int id) {
     lg.binv = inv;
     lg.powL = l.L ? loc_pow(l.L - 1) : 0u;
     lg.powR = l.R ? loc_pow(l.R - 1) : 0u;
-    const size_t lds = loc_lds_bytes(l.k);
-    int per = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_loc_scan<false>, LOC_T, lds) != hipSuccess || per < 1) {
-        (void)hipGetLastError();
-        per = 1;
-    }
-    const u64 grid = std::min<u64>(ntiles, (u64)c->ncu * per);
-    hipStream_t st = c->stream;
-    const uint8_t* b = (const uint8_t*)G.bases.p;
-    const u32* bm = (const u32*)l.bitmap.p;
-    const LocSlot* tab = (const LocSlot*)l.table.p;
-    const uint8_t* ar = (const uint8_t*)l.arena.p;
-    u32* tc = (u32*)l.tcount.p;
-    u64* to = (u64*)l.toff.p;
-    hipLaunchKernelGGL(k_loc_scan<false>, dim3((u32)grid), dim3(LOC_T), lds, st, b, n, lg, bm, tab, (u64)(l.slots - 1), ar, ntiles,
-                       tc, (const u64*)nullptr, (kr_loc_hit*)nullptr);
-    hipLaunchKernelGGL(k_loc_offsets, dim3(1), dim3(1024), 0, st, (const u32*)tc, ntiles, to);
+    const size_t lds = scan_lds_bytes((u32)l.k, LOC_T * 4 + 256);     // (a 32-bit scan array, comp)
+    const u32 grid = scan_grid(c, k_loc_scan<false>, lds, ntiles);
+    auto launch = [&](auto kernel, u32* tc, const u64* to, kr_loc_hit* out) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(LOC_T), lds, c->stream, (const uint8_t*)G->bases.p, n, lg, (const u32*)l.bitmap.p,
+                           (const LocSlot*)l.table.p, (u64)(l.slots - 1), (const uint8_t*)l.arena.p, ntiles, tc, to, out);
+    };
     u64 total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, to + ntiles, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    if (total) {
-        if ((rc = ensure(c, l.hits, total * sizeof(kr_loc_hit))))
-            return fail(c, rc, "kr_locate_scan: %llu hits of genome %d do not fit the device (%s)", (unsigned long long)total, id,
-                        c->err.c_str());
-        hipLaunchKernelGGL(k_loc_scan<true>, dim3((u32)grid), dim3(LOC_T), lds, st, b, n, lg, bm, tab, (u64)(l.slots - 1), ar,
-                           ntiles, tc, (const u64*)to, (kr_loc_hit*)l.hits.p);
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-    }
+    rc = scan_two_pass(
+        c, ntiles, nullptr, [&](u32* tc, u32*) { launch(k_loc_scan<false>, tc, nullptr, nullptr); },
+        [&](u64 total) {
+            const int rc = ensure(c, l.hits, total * sizeof(kr_loc_hit));
+            return rc ? fail(c, rc, "kr_locate_scan: %llu hits of genome %d do not fit the device (%s)", (unsigned long long)total, id,
+                             c->err.c_str())
+                      : KR_OK;
+        },
+        [&](u32* tc, const u64* to, u32*) { launch(k_loc_scan<true>, tc, to, (kr_loc_hit*)l.hits.p); }, &total);
+    if (rc) return rc;
     l.nhits = (int64_t)total;
     return (int64_t)total;
 }
 
 int64_t kr_locate_fetch(kr_ctx* c, kr_loc_hit* out, size_t cap) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
-    const int64_t n = c->loc.nhits;
-    if (n < 0) return fail(c, KR_ERR_STATE, "kr_locate_scan first");
-    if ((size_t)n > cap) return fail(c, KR_ERR_CAPACITY, "hit buffer too small: %lld > %zu", (long long)n, cap);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n) HIPCHK(c, hipMemcpy(out, c->loc.hits.p, (size_t)n * sizeof(kr_loc_hit), hipMemcpyDeviceToHost));
-    return n;
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
+    return scan_fetch(c, c->loc.nhits, "kr_locate_scan first", "hit", c->loc.hits, out, cap, sizeof(kr_loc_hit));
 }
 
 int64_t kr_locate_windows(kr_ctx* c, uint8_t* rows, size_t cap_bytes) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
-    auto& l = c->loc;
-    if (l.nhits < 0) return fail(c, KR_ERR_STATE, "kr_locate_scan first");
-    if (!rows || !l.nhits) return l.nhits;
-    auto it = c->genomes.find(l.gid);
-    if (it == c->genomes.end() || !it->second.uploaded) return fail(c, KR_ERR_STATE, "genome %d is gone", l.gid);
-    const u64 bytes = (u64)l.nhits * l.k;
-    if (bytes > cap_bytes) return fail(c, KR_ERR_CAPACITY, "row buffer too small: %llu > %zu", (unsigned long long)bytes, cap_bytes);
-    HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, l.rows, bytes))) return rc;
-    const u32 grid = (u32)std::min<u64>((bytes + 255) / 256, (u64)c->ncu * 16);
-    hipLaunchKernelGGL(k_loc_cut, dim3(grid), dim3(256), 0, c->stream, (const uint8_t*)it->second.bases.p,
-                       (const kr_loc_hit*)l.hits.p, (u64)l.nhits, (u32)l.k, (uint8_t*)l.rows.p);
-    HIPCHK(c, hipMemcpyAsync(rows, l.rows.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return l.nhits;
+    if ((rc = scan_ctx(c))) return rc;
+    auto& l = c->loc;
+    return scan_windows<kr_loc_hit>(c, l.nhits, l.gid, "kr_locate_scan first", l.hits, l.rows, rows, cap_bytes);
 }
 
 int64_t kr_locate_seps(kr_ctx* c, int id, uint64_t* out, size_t cap) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
-    auto it = c->genomes.find(id);
-    if (it == c->genomes.end() || !it->second.uploaded) return fail(c, KR_ERR_STATE, "genome %d not uploaded", id);
-    const Genome& G = it->second;
-    auto& l = c->loc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const u64 n = G.n_bases, TB = (u64)LOC_T * LOC_SEP_BYTES;
-    const u64 ntiles = (n + TB - 1) / TB;
-    if (!ntiles) return 0;
-    if (ntiles >= (1ull << 31)) return fail(c, KR_ERR_PARAM, "kr_locate_seps: %llu bases", (unsigned long long)n);
+    const Genome* G;
     int rc;
-    if ((rc = ensure(c, l.tcount, (ntiles + 1) * 4)) || (rc = ensure(c, l.toff, (ntiles + 1) * 8))) return rc;
-    hipStream_t st = c->stream;
-    const uint8_t* b = (const uint8_t*)G.bases.p;
-    u32* tc = (u32*)l.tcount.p;
-    u64* to = (u64*)l.toff.p;
-    hipLaunchKernelGGL(k_loc_sep<false>, dim3((u32)ntiles), dim3(LOC_T), 0, st, b, n, tc, (const u64*)nullptr, (u64*)nullptr);
-    hipLaunchKernelGGL(k_loc_offsets, dim3(1), dim3(1024), 0, st, (const u32*)tc, ntiles, to);
+    if ((rc = scan_genome(c, id, true, nullptr, &G))) return rc;
+    auto& l = c->loc;
     u64 total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, to + ntiles, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    if (!out || !total) return (int64_t)total;
-    if (total > cap) return fail(c, KR_ERR_CAPACITY, "separator buffer too small: %llu > %zu", (unsigned long long)total, cap);
-    if ((rc = ensure(c, l.seps, total * 8))) return rc;
-    hipLaunchKernelGGL(k_loc_sep<true>, dim3((u32)ntiles), dim3(LOC_T), 0, st, b, n, tc, (const u64*)to, (u64*)l.seps.p);
-    HIPCHK(c, hipMemcpyAsync(out, l.seps.p, total * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
+    rc = scan_seps(
+        c, *G, "kr_locate_seps", l.seps,
+        [&](u64 total) {
+            if (!out) return SCAN_COUNT_ONLY;
+            if (total > cap) return fail(c, KR_ERR_CAPACITY, "separator buffer too small: %llu > %zu", (unsigned long long)total, cap);
+            return ensure(c, l.seps, total * 8);
+        },
+        &total);
+    if (rc) return rc;
+    if (out && total) HIPCHK(c, hipMemcpy(out, l.seps.p, total * 8, hipMemcpyDeviceToHost));
     return (int64_t)total;
 }

@@ -22,7 +22,8 @@ static void prod_geom(const kr_ctx* c, ProdGeom* pg) {
 
 int64_t kr_products_table(kr_ctx* c, const uint8_t* left, uint64_t nleft, const uint8_t* right, uint64_t nright,
                           const uint32_t* pairs, uint64_t npairs, int mismatches, uint32_t max_product) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
     auto& l = c->loc;
     auto& pr = c->prod;
     const int Le = l.L, Re = l.R, M = mismatches;
@@ -47,10 +48,8 @@ int64_t kr_products_table(kr_ctx* c, const uint8_t* left, uint64_t nleft, const 
     const u64 ne = 2 * (nleft + nright), nk = ne * NP;
     std::vector<uint8_t> text;
     std::vector<std::pair<u64, u32>> keyed;
-    std::vector<NearSlot> tab;
-    std::vector<u32> list, bm, pidx;
+    std::vector<u32> pidx;
     std::vector<std::pair<u64, u32>> pk;
-    u64 slots = 1024;
     try {
         text.resize(2 * (nleft * Le + nright * Re) + 16);
         for (u64 e = 0; e < ne; e += 2) {
@@ -71,13 +70,6 @@ int64_t kr_products_table(kr_ctx* c, const uint8_t* left, uint64_t nleft, const 
                                                                                      (int)(pg.off[q][j + 1] - pg.off[q][j]))),
                                    (u32)e);
         }
-        std::sort(keyed.begin(), keyed.end());
-        u64 distinct = 0;
-        for (u64 i = 0; i < nk; i++) distinct += i == 0 || keyed[i].first != keyed[i - 1].first;
-        while (slots < 2 * distinct) slots <<= 1;
-        tab.assign(slots, NearSlot{0, 0, NEAR_EMPTY});
-        bm.assign(LOC_BM_WORDS, 0u);
-        list.resize(nk + 1);
         pk.reserve(npairs);
         for (u64 p = 0; p < npairs; p++) {
             if (pairs[2 * p] >= nleft || pairs[2 * p + 1] >= nright)
@@ -98,116 +90,41 @@ int64_t kr_products_table(kr_ctx* c, const uint8_t* left, uint64_t nleft, const 
         pkeys[p] = pk[p].first;
         pidx[p] = pk[p].second;
     }
-    const u64 mask = slots - 1;
-    for (u64 i = 0; i < nk;) {
-        u64 j = i;
-        for (; j < nk && keyed[j].first == keyed[i].first; j++) list[j] = keyed[j].second;
-        const u64 key = keyed[i].first;
-        u64 s = key & mask;
-        while (tab[s].count != NEAR_EMPTY) s = (s + 1) & mask;
-        tab[s].key = key;
-        tab[s].start = (u32)i;                      // (nk < 2^28)
-        tab[s].count = (u32)(j - i);
-        const u32 b = (u32)(key >> (64 - LOC_BM_LOG));
-        bm[b >> 5] |= 1u << (b & 31);
-        i = j;
-    }
-    int rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure(c, pr.table, slots * sizeof(NearSlot))) || (rc = ensure(c, pr.arena, text.size())) ||
-        (rc = ensure(c, pr.list, list.size() * 4)) || (rc = ensure(c, pr.bitmap, (size_t)LOC_BM_WORDS * 4)) ||
-        (rc = ensure(c, pr.flag, 16)) || (rc = ensure(c, pr.pairkeys, pkeys.size() * 8)) || (rc = ensure(c, pr.pairidx, pidx.size() * 4)))
+    const int64_t slots = seed_table_build(c, keyed, text, pr.table, pr.arena, pr.list, pr.bitmap, "kr_products_table", nleft + nright,
+                                           "texts");
+    if (slots < 0) return slots;
+    if ((rc = ensure(c, pr.pairkeys, pkeys.size() * 8)) || (rc = ensure(c, pr.pairidx, pidx.size() * 4)))
         return fail(c, rc, "kr_products_table: the table of %llu texts does not fit the device (%s)", (unsigned long long)(nleft + nright),
                     c->err.c_str());
-    HIPCHK(c, hipMemcpy(pr.table.p, tab.data(), slots * sizeof(NearSlot), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(pr.arena.p, text.data(), text.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(pr.list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(pr.bitmap.p, bm.data(), (size_t)LOC_BM_WORDS * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(pr.pairkeys.p, pkeys.data(), pkeys.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(pr.pairidx.p, pidx.data(), pidx.size() * 4, hipMemcpyHostToDevice));
-    pr.slots = slots;
-    return (int64_t)slots;
-}
-
-static size_t prod_lds_bytes(u32 maxlen) {
-    const u32 tb = LOC_T * LOC_S + maxlen - 1;
-    return (size_t)LOC_BM_WORDS * 4 + LOC_T * 8 + (((tb + 16) + ((tb + 16) >> LOC_SH) * 4 + 15) & ~15u);
-}
-
-// the separators of the genome into prod.seps (k_loc_sep as kr_locate_seps runs it)
-static int prod_seps(kr_ctx* c, const Genome& G, u64* nseps) {
-    auto& pr = c->prod;
-    const u64 n = G.n_bases, TB = (u64)LOC_T * LOC_SEP_BYTES;
-    const u64 ntiles = (n + TB - 1) / TB;
-    *nseps = 0;
-    if (!ntiles) return KR_OK;
-    if (ntiles >= (1ull << 31)) return fail(c, KR_ERR_PARAM, "kr_products_scan: %llu bases", (unsigned long long)n);
-    int rc;
-    if ((rc = ensure(c, pr.tcount, (ntiles + 1) * 4)) || (rc = ensure(c, pr.toff, (ntiles + 1) * 8))) return rc;
-    hipStream_t st = c->stream;
-    const uint8_t* b = (const uint8_t*)G.bases.p;
-    u32* tc = (u32*)pr.tcount.p;
-    u64* to = (u64*)pr.toff.p;
-    hipLaunchKernelGGL(k_loc_sep<false>, dim3((u32)ntiles), dim3(LOC_T), 0, st, b, n, tc, (const u64*)nullptr, (u64*)nullptr);
-    hipLaunchKernelGGL(k_loc_offsets, dim3(1), dim3(1024), 0, st, (const u32*)tc, ntiles, to);
-    u64 total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, to + ntiles, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    if ((rc = ensure(c, pr.seps, (total + 1) * 8))) return rc;
-    if (total) {
-        hipLaunchKernelGGL(k_loc_sep<true>, dim3((u32)ntiles), dim3(LOC_T), 0, st, b, n, tc, (const u64*)to, (u64*)pr.seps.p);
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-    }
-    *nseps = total;
-    return KR_OK;
+    pr.slots = (u64)slots;
+    return slots;
 }
 
 extern "C++" {    // (a template inside the translation unit's extern "C" block)
 template <u32 NP, u32 NC>
 static int prod_sites_launch(kr_ctx* c, const Genome& G, const ProdGeom& pg, u64 nw, u64 ntiles, u64* total_out) {
     auto& pr = c->prod;
-    const size_t lds = prod_lds_bytes(pg.maxlen);
-    int per = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_prod_scan<NP, NC, false>, LOC_T, lds) != hipSuccess || per < 1) {
-        (void)hipGetLastError();
-        per = 1;
-    }
-    const u64 grid = std::min<u64>(ntiles, (u64)c->ncu * per);
-    hipStream_t st = c->stream;
-    const uint8_t* b = (const uint8_t*)G.bases.p;
-    const u64 n = G.n_bases;
-    const u32* bm = (const u32*)pr.bitmap.p;
-    const NearSlot* tab = (const NearSlot*)pr.table.p;
-    const u32* li = (const u32*)pr.list.p;
-    const uint8_t* ar = (const uint8_t*)pr.arena.p;
-    u32* tc = (u32*)pr.tcount.p;
-    u64* to = (u64*)pr.toff.p;
-    u32* fl = (u32*)pr.flag.p;
-    HIPCHK(c, hipMemsetAsync(fl, 0, 4, st));
-    hipLaunchKernelGGL((k_prod_scan<NP, NC, false>), dim3((u32)grid), dim3(LOC_T), lds, st, b, n, pg, bm, tab, (u64)(pr.slots - 1), li, ar,
-                       nw, ntiles, tc, (const u64*)nullptr, (kr_product_site*)nullptr, fl);
-    hipLaunchKernelGGL(k_loc_offsets, dim3(1), dim3(1024), 0, st, (const u32*)tc, ntiles, to);
-    u64 total = 0;
-    u32 over = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, to + ntiles, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&over, fl, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    if (over || total >= (1ull << 32))
-        return fail(c, KR_ERR_CAPACITY, "kr_products_scan: 2^32 or more primer sites in one genome (fewer mismatches or regions)");
-    if (total) {
-        int rc;
-        if ((rc = ensure(c, pr.sites, total * sizeof(kr_product_site))) || (rc = ensure(c, pr.rec, total * 4)))
-            return fail(c, rc, "kr_products_scan: %llu primer sites do not fit the device (%s)", (unsigned long long)total, c->err.c_str());
-        hipLaunchKernelGGL((k_prod_scan<NP, NC, true>), dim3((u32)grid), dim3(LOC_T), lds, st, b, n, pg, bm, tab, (u64)(pr.slots - 1), li,
-                           ar, nw, ntiles, tc, (const u64*)to, (kr_product_site*)pr.sites.p, fl);
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-    }
-    *total_out = total;
-    return KR_OK;
+    const size_t lds = scan_lds_bytes(pg.maxlen, LOC_T * 8);      // (a 64-bit scan array)
+    const u32 grid = scan_grid(c, k_prod_scan<NP, NC, false>, lds, ntiles);
+    auto launch = [&](auto kernel, u32* tc, const u64* to, kr_product_site* out, u32* fl) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(LOC_T), lds, c->stream, (const uint8_t*)G.bases.p, (u64)G.n_bases, pg,
+                           (const u32*)pr.bitmap.p, (const NearSlot*)pr.table.p, (u64)(pr.slots - 1), (const u32*)pr.list.p,
+                           (const uint8_t*)pr.arena.p, nw, ntiles, tc, to, out, fl);
+    };
+    return scan_two_pass(
+        c, ntiles, "kr_products_scan: 2^32 or more primer sites in one genome (fewer mismatches or regions)",
+        [&](u32* tc, u32* fl) { launch(k_prod_scan<NP, NC, false>, tc, nullptr, nullptr, fl); },
+        [&](u64 total) -> int {
+            int rc;
+            if ((rc = ensure(c, pr.sites, total * sizeof(kr_product_site))) || (rc = ensure(c, pr.rec, total * 4)))
+                return fail(c, rc, "kr_products_scan: %llu primer sites do not fit the device (%s)", (unsigned long long)total,
+                            c->err.c_str());
+            return KR_OK;
+        },
+        [&](u32* tc, const u64* to, u32* fl) { launch(k_prod_scan<NP, NC, true>, tc, to, (kr_product_site*)pr.sites.p, fl); },
+        total_out);
 }
 }  // extern "C++"
 
@@ -217,64 +134,41 @@ static int prod_join(kr_ctx* c, const ProdGeom& pg, u64 ns, u64* total_out) {
     *total_out = 0;
     if (!ns || !pr.npairs) return KR_OK;
     const u64 nblocks = (ns + LOC_T - 1) / LOC_T;                 // (ns < 2^32: < 2^24 blocks)
-    int rc;
-    if ((rc = ensure(c, pr.tcount, (nblocks + 1) * 4)) || (rc = ensure(c, pr.toff, (nblocks + 1) * 8))) return rc;
-    hipStream_t st = c->stream;
-    const kr_product_site* si = (const kr_product_site*)pr.sites.p;
-    const u32* rec = (const u32*)pr.rec.p;
-    const u64* pk = (const u64*)pr.pairkeys.p;
-    const u32* pi = (const u32*)pr.pairidx.p;
-    u32* bc = (u32*)pr.tcount.p;
-    u64* bo = (u64*)pr.toff.p;
-    u32* fl = (u32*)pr.flag.p;
-    HIPCHK(c, hipMemsetAsync(fl, 0, 4, st));
-    hipLaunchKernelGGL(k_prod_join<false>, dim3((u32)nblocks), dim3(LOC_T), 0, st, si, ns, rec, pg, pk, pi, (u32)pr.npairs, pr.max_product,
-                       bc, (const u64*)nullptr, (kr_product_hit*)nullptr, fl);
-    hipLaunchKernelGGL(k_loc_offsets, dim3(1), dim3(1024), 0, st, (const u32*)bc, nblocks, bo);
-    u64 total = 0;
-    u32 over = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, bo + nblocks, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&over, fl, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    if (over || total >= (1ull << 32))
-        return fail(c, KR_ERR_CAPACITY, "kr_products_scan: 2^32 or more products in one genome (a smaller max_product or fewer mismatches)");
-    if (total) {
-        if ((rc = ensure(c, pr.hits, total * sizeof(kr_product_hit))))
-            return fail(c, rc, "kr_products_scan: %llu products do not fit the device (%s)", (unsigned long long)total, c->err.c_str());
-        hipLaunchKernelGGL(k_prod_join<true>, dim3((u32)nblocks), dim3(LOC_T), 0, st, si, ns, rec, pg, pk, pi, (u32)pr.npairs,
-                           pr.max_product, bc, (const u64*)bo, (kr_product_hit*)pr.hits.p, fl);
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-    }
-    *total_out = total;
-    return KR_OK;
+    auto launch = [&](auto kernel, u32* bc, const u64* bo, kr_product_hit* out, u32* fl) {
+        hipLaunchKernelGGL(kernel, dim3((u32)nblocks), dim3(LOC_T), 0, c->stream, (const kr_product_site*)pr.sites.p, ns,
+                           (const u32*)pr.rec.p, pg, (const u64*)pr.pairkeys.p, (const u32*)pr.pairidx.p, (u32)pr.npairs, pr.max_product,
+                           bc, bo, out, fl);
+    };
+    return scan_two_pass(
+        c, nblocks, "kr_products_scan: 2^32 or more products in one genome (a smaller max_product or fewer mismatches)",
+        [&](u32* bc, u32* fl) { launch(k_prod_join<false>, bc, nullptr, nullptr, fl); },
+        [&](u64 total) {
+            const int rc = ensure(c, pr.hits, total * sizeof(kr_product_hit));
+            return rc ? fail(c, rc, "kr_products_scan: %llu products do not fit the device (%s)", (unsigned long long)total, c->err.c_str())
+                      : KR_OK;
+        },
+        [&](u32* bc, const u64* bo, u32* fl) { launch(k_prod_join<true>, bc, bo, (kr_product_hit*)pr.hits.p, fl); }, total_out);
 }
 
 int64_t kr_products_scan(kr_ctx* c, int id) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
+    const Genome* Gp;
+    int rc;
+    if ((rc = scan_genome(c, id, c && c->prod.slots, "kr_products_table first", &Gp))) return rc;
+    const Genome& G = *Gp;
     auto& pr = c->prod;
-    if (!pr.slots) return fail(c, KR_ERR_STATE, "kr_products_table first");
-    auto it = c->genomes.find(id);
-    if (it == c->genomes.end() || !it->second.uploaded) return fail(c, KR_ERR_STATE, "genome %d not uploaded", id);
-    const Genome& G = it->second;
-    HIPCHK(c, hipSetDevice(c->device));
     pr.nsites = pr.nhits = -1;
     ProdGeom pg;
     prod_geom(c, &pg);
-    const u64 n = G.n_bases, minlen = std::min(pg.len[0], pg.len[1]);
-    const u64 nw = n >= minlen ? n - minlen + 1 : 0;              // window starts of the shorter class
-    const u64 TP = (u64)LOC_T * LOC_S;
-    const u64 ntiles = (nw + TP - 1) / TP;
+    u64 nw;                                                       // window starts of the shorter class
+    const u64 ntiles = scan_tiles(G.n_bases, std::min(pg.len[0], pg.len[1]), &nw);
     if (!ntiles || !(pr.nleft + pr.nright)) {
         pr.nsites = pr.nhits = 0;
         return 0;
     }
-    int rc;
     u64 nseps = 0, ns = 0, np = 0;
-    if ((rc = prod_seps(c, G, &nseps))) return rc;
+    // (the pass's own list: k_prod_rec reads it, and a kr_locate_seps of the caller writes loc.seps)
+    if ((rc = scan_seps(c, G, "kr_products_scan", pr.seps, [&](u64 total) { return ensure(c, pr.seps, total * 8); }, &nseps))) return rc;
     if (nseps >= (1ull << 32)) return fail(c, KR_ERR_CAPACITY, "kr_products_scan: 2^32 or more records in one genome");
-    if ((rc = ensure(c, pr.tcount, (ntiles + 1) * 4)) || (rc = ensure(c, pr.toff, (ntiles + 1) * 8))) return rc;
     const bool one = pg.len[0] == pg.len[1];
     switch (pg.M + 1) {
     case 1: rc = one ? prod_sites_launch<1, 1>(c, G, pg, nw, ntiles, &ns) : prod_sites_launch<1, 2>(c, G, pg, nw, ntiles, &ns); break;
@@ -295,13 +189,9 @@ int64_t kr_products_scan(kr_ctx* c, int id) {
 }
 
 int64_t kr_products_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
-    const int64_t n = c->prod.nhits;
-    if (n < 0) return fail(c, KR_ERR_STATE, "kr_products_scan first");
-    if ((size_t)n > cap) return fail(c, KR_ERR_CAPACITY, "product buffer too small: %lld > %zu", (long long)n, cap);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!n) return 0;
-    HIPCHK(c, hipMemcpy(out, c->prod.hits.p, (size_t)n * sizeof(kr_product_hit), hipMemcpyDeviceToHost));
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
+    const int64_t n = scan_fetch(c, c->prod.nhits, "kr_products_scan first", "product", c->prod.hits, out, cap, sizeof(kr_product_hit));
     // the device lists them by opening site (position, then the sites' order there): positions ascend already, the
     // products of one position are put in (length, strand, pair) order here
     auto less = [](const kr_product_hit& a, const kr_product_hit& b) {
@@ -320,12 +210,9 @@ int64_t kr_products_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) {
 }
 
 int64_t kr_products_sites(kr_ctx* c, kr_product_site* out, size_t cap) {
-    if (!c || !c->loc.on) return fail(c, KR_ERR_STATE, "kr_set_params_locate first");
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
     const int64_t n = c->prod.nsites;
-    if (n < 0) return fail(c, KR_ERR_STATE, "kr_products_scan first");
-    if (!out || !n) return n;
-    if ((size_t)n > cap) return fail(c, KR_ERR_CAPACITY, "site buffer too small: %lld > %zu", (long long)n, cap);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(out, c->prod.sites.p, (size_t)n * sizeof(kr_product_site), hipMemcpyDeviceToHost));
-    return n;
+    if (n >= 0 && !out) return n;                   // (the count alone)
+    return scan_fetch(c, n, "kr_products_scan first", "site", c->prod.sites, out, cap, sizeof(kr_product_site));
 }

@@ -1,6 +1,7 @@
 // k_near.inc -- part of krisp_hip.hip (one translation unit): the near-match pass (--out_near): every window of a genome within
 // Hamming distance M of a target (an ingroup window of a diagnostic region), on both strands.  The host driver is h_near.inc;
-// the context, the genome on the device, the separator list and the tile layout are the locate pass's (k_locate.inc).
+// the context and the genome on the device are the locate pass's; the tile layout, the staging, the seed table's slots and
+// probe, the count / emit epilogue and the cut of the windows' text are k_scan.inc's.
 //
 // Pigeonhole seeds: the k columns are cut into NP = M + 1 pieces at fixed offsets (piece j = columns [off[j], off[j + 1])); a
 // window within distance M of a text equals it in at least one piece.  The host lists every target and its reverse complement
@@ -18,39 +19,12 @@
 // Pass 1 (EMIT = false) counts per tile, k_loc_offsets scans, pass 2 (EMIT = true) revisits the tiles with hits and writes
 // them at their tile's offset: position order, then piece, then the entry list's order.  No atomics: the same bytes on
 // every run.  (The host orders the table's rows by target and strand afterwards; a row is unique in (target, pos, strand).)
-#define NEAR_MAXP 4                 // pieces at most: M <= 3
-#define NEAR_EMPTY 0u               // a free slot has no entries
-
 struct NearGeom {
     u32 k, omit, np, M;
     u32 lo[2], hi[2];               // strand s: column c lies in a conserved flank when c < lo[s] or c >= hi[s]
     u32 off[NEAR_MAXP + 1];         // piece j = columns [off[j], off[j + 1])
     u32 pw[NEAR_MAXP];              // LOC_HB^(length of piece j - 1)
 };
-
-struct NearSlot {                   // the entries whose piece has this key: list[start, start + count)
-    u64 key;
-    u32 start, count;
-};
-
-__host__ __device__ inline u64 near_key(u32 piece, u32 h) { return loc_mix(piece * 0x85EBCA6Bu + 1u, h); }
-
-// exclusive prefix sum of one u64 per thread over the workgroup; *total = the sum
-__device__ inline u64 near_block_scan(u64 v, u64* sh, u64* total) {
-    const u32 t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (u32 d = 1; d < LOC_T; d <<= 1) {
-        const u64 a = t >= d ? sh[t - d] : 0ull;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    const u64 incl = sh[t];
-    *total = sh[LOC_T - 1];
-    __syncthreads();
-    return incl - v;
-}
 
 // window p of the tile against entry e, found through piece `via`: on_hit(entry, mismatches, flank mismatches) when the
 // distance is <= M and `via` is the first piece without a mismatch
@@ -77,22 +51,6 @@ __device__ inline void near_check(const NearGeom& ng, const uint8_t* tile, const
     on_hit(e, mm, fm);
 }
 
-template <u32 NP, typename F>
-__device__ inline void near_probe(const NearGeom& ng, const uint8_t* tile, const u32* bm, const NearSlot* __restrict__ table, u64 tmask,
-                                  const u32* __restrict__ list, const uint8_t* __restrict__ arena, u32 p, u32 piece, u32 h, F&& on_hit) {
-    const u64 key = near_key(piece, h);
-    const u32 b = (u32)(key >> (64 - LOC_BM_LOG));
-    if (!((bm[b >> 5] >> (b & 31)) & 1u)) return;
-    for (u64 i = key & tmask;; i = (i + 1) & tmask) {
-        const NearSlot s = table[i];
-        if (s.count == NEAR_EMPTY) return;
-        if (s.key != key) continue;
-        #pragma unroll 1
-        for (u32 q = 0; q < s.count; q++) near_check<NP>(ng, tile, arena, p, list[s.start + q], piece, on_hit);
-        return;                                     // (a key has one slot)
-    }
-}
-
 // one thread's window starts [s, e) of the staged tile: on_hit(p, entry, mismatches, flank mismatches)
 template <u32 NP, typename F>
 __device__ inline void near_roll(const NearGeom& ng, const uint8_t* tile, const u32* bm, const NearSlot* __restrict__ table, u64 tmask,
@@ -115,8 +73,9 @@ __device__ inline void near_roll(const NearGeom& ng, const uint8_t* tile, const 
         if (bad < (int)p) {
 #pragma unroll
             for (u32 j = 0; j < NP; j++)
-                near_probe<NP>(ng, tile, bm, table, tmask, list, arena, p, j, h[j],
-                               [&](u32 en, u32 mm, u32 fm) { on_hit(p, en, mm, fm); });
+                seed_probe(bm, table, tmask, list, near_key(j, h[j]), [&](u32 en) {
+                    near_check<NP>(ng, tile, arena, p, en, j, [&](u32 en, u32 mm, u32 fm) { on_hit(p, en, mm, fm); });
+                });
         }
         if (p + 1 >= e) break;
         // slide to p + 1: the byte that leaves piece j + 1 enters piece j
@@ -143,55 +102,19 @@ __global__ __launch_bounds__(LOC_T) void k_near_scan(const uint8_t* __restrict__
     u32* bm = near_lds;                                           // LOC_BM_WORDS
     u64* scan = (u64*)(bm + LOC_BM_WORDS);                        // LOC_T
     uint8_t* tile = (uint8_t*)(scan + LOC_T);                     // loc_at(LOC_T * LOC_S + k - 1) bytes
-    const u32 t = threadIdx.x;
-    for (u32 i = t; i < LOC_BM_WORDS / 4; i += LOC_T) ((uint4*)bm)[i] = ((const uint4*)bitmap)[i];
+    scan_load_bitmap(bm, bitmap);
     const u64 nw = n >= ng.k ? n - ng.k + 1 : 0;                  // window starts of the genome
     const u32 TP = LOC_T * LOC_S;
-    const u32 tb = TP + ng.k - 1;                                 // bytes a tile reads
-    u32* tile32 = (u32*)tile;
     for (u64 tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
         if (EMIT && tcount[tl] == 0) continue;                    // (workgroup-uniform)
         const u64 t0 = tl * TP;
-        __syncthreads();                                          // (the previous tile's readers are done)
-        for (u32 c = t; c * 16 < tb; c += LOC_T) {
-            const u64 g = t0 + (u64)c * 16;
-            u32 w[4];
-            if (g + 16 <= n) {
-                const uint4 v = *(const uint4*)(bases + g);
-                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            } else {
-#pragma unroll
-                for (u32 q = 0; q < 4; q++) {
-                    u32 x = 0;
-                    for (u32 b = 0; b < 4; b++) {
-                        const u64 i = g + 4 * q + b;
-                        x |= (u32)(i < n ? bases[i] : (uint8_t)'\n') << (8 * b);
-                    }
-                    w[q] = x;
-                }
-            }
-#pragma unroll
-            for (u32 q = 0; q < 4; q++) {
-                u32 x = 0;
-                for (u32 b = 0; b < 4; b++) x |= loc_stage_byte((w[q] >> (8 * b)) & 0xFFu, ng.omit) << (8 * b);
-                tile32[loc_at(c * 16 + 4 * q) >> 2] = x;
-            }
-        }
-        __syncthreads();
-        const u32 np = (u32)min((u64)TP, nw - t0);               // window starts of this tile
-        const u32 s = min(t * LOC_S, np), e = min(s + LOC_S, np);
+        scan_stage_tile(bases, n, t0, TP + ng.k - 1, ng.omit, tile);
+        u32 s, e;
+        scan_lane_starts(nw, t0, &s, &e);
         u64 cnt = 0;
         near_roll<NP>(ng, tile, bm, table, tmask, list, arena, s, e, [&](u32, u32, u32, u32) { cnt++; });
-        u64 total;
-        const u64 before = near_block_scan(cnt, scan, &total);
-        if (!EMIT) {
-            if (t == 0) {
-                if (total >> 32) *overflow = 1u;
-                tcount[tl] = (total >> 32) ? 0u : (u32)total;
-            }
-            continue;
-        }
-        kr_near_hit* o = out + toff[tl] + before;
+        kr_near_hit* o = out + scan_epilogue<EMIT>(cnt, scan, tl, tcount, toff, overflow);
+        if (!EMIT) continue;
         near_roll<NP>(ng, tile, bm, table, tmask, list, arena, s, e, [&](u32 p, u32 en, u32 mm, u32 fm) {
             kr_near_hit hit;
             hit.target = en >> 1;
@@ -202,19 +125,5 @@ __global__ __launch_bounds__(LOC_T) void k_near_scan(const uint8_t* __restrict__
             hit.pos = t0 + p;
             *o++ = hit;
         });
-    }
-}
-
-// the text of the hits' windows, a row of k bytes per hit: upper case, the reverse complement for strand 1 (k_loc_cut's rows)
-__global__ __launch_bounds__(256) void k_near_cut(const uint8_t* __restrict__ bases, const kr_near_hit* __restrict__ hits, u64 nhits,
-                                                  u32 k, uint8_t* __restrict__ rows) {
-    const u64 total = nhits * k;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += (u64)gridDim.x * 256) {
-        const u64 h = i / k;
-        const u32 j = (u32)(i - h * k);
-        const kr_near_hit e = hits[h];
-        u32 b = bases[e.pos + (e.strand ? k - 1 - j : j)];
-        if (b >= 'a' && b <= 'z') b -= 32;
-        rows[i] = e.strand ? loc_comp((uint8_t)b) : (uint8_t)b;
     }
 }

@@ -1,7 +1,7 @@
 // k_products.inc -- part of krisp_hip.hip (one translation unit): the product pass (--out_products): in-silico PCR of the
-// regions' conserved flanks against a genome.  The host driver is h_products.inc; the context, the genome on the device, the
-// separator kernels and the tile layout are the locate pass's (k_locate.inc), the seeds and the block scan the near pass's
-// (k_near.inc).
+// regions' conserved flanks against a genome.  The host driver is h_products.inc; the context and the genome on the device
+// are the locate pass's; the tile layout, the staging, the seed table's slots and probe, the count / emit epilogue and the
+// separator kernels are k_scan.inc's.
 //
 // Entries: every distinct left flank text A (len[0] letters) gives entry 2 i (A) and 2 i + 1 (rc(A)); every distinct right
 // flank text B (len[1] letters) gives entry nleft2 + 2 j (B) and nleft2 + 2 j + 1 (rc(B)), nleft2 = twice the left texts.
@@ -60,25 +60,6 @@ __device__ inline void prod_check(const ProdGeom& pg, const uint8_t* tile, const
     on_hit(e, mm, em);
 }
 
-// (class, piece, hash) -> the slot's entries, each checked; entries of another class under the key (NC == 1 lists both
-// kinds under class 0) are of the same length by construction
-template <u32 NP, typename F>
-__device__ inline void prod_probe(const ProdGeom& pg, const uint8_t* tile, const u32* bm, const NearSlot* __restrict__ table, u64 tmask,
-                                  const u32* __restrict__ list, const uint8_t* __restrict__ arena, u32 p, u32 cls, u32 piece, u32 h,
-                                  F&& on_hit) {
-    const u64 key = near_key(cls * NEAR_MAXP + piece, h);
-    const u32 b = (u32)(key >> (64 - LOC_BM_LOG));
-    if (!((bm[b >> 5] >> (b & 31)) & 1u)) return;
-    for (u64 i = key & tmask;; i = (i + 1) & tmask) {
-        const NearSlot s = table[i];
-        if (s.count == NEAR_EMPTY) return;
-        if (s.key != key) continue;
-        #pragma unroll 1
-        for (u32 q = 0; q < s.count; q++) prod_check<NP>(pg, tile, arena, p, list[s.start + q], piece, on_hit);
-        return;                                     // (a key has one slot)
-    }
-}
-
 // one thread's window starts [s, e) of the staged tile: on_hit(p, entry, mismatches, end mismatches), position order
 template <u32 NP, u32 NC, typename F>
 __device__ inline void prod_roll(const ProdGeom& pg, const uint8_t* tile, const u32* bm, const NearSlot* __restrict__ table, u64 tmask,
@@ -106,8 +87,11 @@ __device__ inline void prod_roll(const ProdGeom& pg, const uint8_t* tile, const 
             if (bad[c] < (int)p) {
 #pragma unroll
                 for (u32 j = 0; j < NP; j++)
-                    prod_probe<NP>(pg, tile, bm, table, tmask, list, arena, p, c, j, h[c][j],
-                                   [&](u32 en, u32 mm, u32 em) { on_hit(p, en, mm, em); });
+                    // (entries of another class under the key -- NC == 1 lists both kinds under class 0 -- are of the
+                    // same length by construction)
+                    seed_probe(bm, table, tmask, list, near_key(c * NEAR_MAXP + j, h[c][j]), [&](u32 en) {
+                        prod_check<NP>(pg, tile, arena, p, en, j, [&](u32 en, u32 mm, u32 em) { on_hit(p, en, mm, em); });
+                    });
             }
         }
         if (p + 1 >= e) break;
@@ -140,54 +124,18 @@ __global__ __launch_bounds__(LOC_T) void k_prod_scan(const uint8_t* __restrict__
     u32* bm = prod_lds;                                           // LOC_BM_WORDS
     u64* scan = (u64*)(bm + LOC_BM_WORDS);                        // LOC_T
     uint8_t* tile = (uint8_t*)(scan + LOC_T);                     // loc_at(LOC_T * LOC_S + maxlen - 1) bytes
-    const u32 t = threadIdx.x;
-    for (u32 i = t; i < LOC_BM_WORDS / 4; i += LOC_T) ((uint4*)bm)[i] = ((const uint4*)bitmap)[i];
+    scan_load_bitmap(bm, bitmap);
     const u32 TP = LOC_T * LOC_S;
-    const u32 tb = TP + pg.maxlen - 1;                            // bytes a tile reads
-    u32* tile32 = (u32*)tile;
     for (u64 tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
         if (EMIT && tcount[tl] == 0) continue;                    // (workgroup-uniform)
         const u64 t0 = tl * TP;
-        __syncthreads();                                          // (the previous tile's readers are done)
-        for (u32 c = t; c * 16 < tb; c += LOC_T) {
-            const u64 g = t0 + (u64)c * 16;
-            u32 w[4];
-            if (g + 16 <= n) {
-                const uint4 v = *(const uint4*)(bases + g);
-                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            } else {
-#pragma unroll
-                for (u32 q = 0; q < 4; q++) {
-                    u32 x = 0;
-                    for (u32 b = 0; b < 4; b++) {
-                        const u64 i = g + 4 * q + b;
-                        x |= (u32)(i < n ? bases[i] : (uint8_t)'\n') << (8 * b);
-                    }
-                    w[q] = x;
-                }
-            }
-#pragma unroll
-            for (u32 q = 0; q < 4; q++) {
-                u32 x = 0;
-                for (u32 b = 0; b < 4; b++) x |= loc_stage_byte((w[q] >> (8 * b)) & 0xFFu, pg.omit) << (8 * b);
-                tile32[loc_at(c * 16 + 4 * q) >> 2] = x;
-            }
-        }
-        __syncthreads();
-        const u32 np = (u32)min((u64)TP, nw - t0);               // window starts of this tile
-        const u32 s = min(t * LOC_S, np), e = min(s + LOC_S, np);
+        scan_stage_tile(bases, n, t0, TP + pg.maxlen - 1, pg.omit, tile);
+        u32 s, e;
+        scan_lane_starts(nw, t0, &s, &e);
         u64 cnt = 0;
         prod_roll<NP, NC>(pg, tile, bm, table, tmask, list, arena, s, e, [&](u32, u32, u32, u32) { cnt++; });
-        u64 total;
-        const u64 before = near_block_scan(cnt, scan, &total);
-        if (!EMIT) {
-            if (t == 0) {
-                if (total >> 32) *overflow = 1u;
-                tcount[tl] = (total >> 32) ? 0u : (u32)total;
-            }
-            continue;
-        }
-        kr_product_site* o = out + toff[tl] + before;
+        kr_product_site* o = out + scan_epilogue<EMIT>(cnt, scan, tl, tcount, toff, overflow);
+        if (!EMIT) continue;
         prod_roll<NP, NC>(pg, tile, bm, table, tmask, list, arena, s, e, [&](u32 p, u32 en, u32 mm, u32 em) {
             kr_product_site site;
             site.pos = t0 + p;
@@ -262,17 +210,8 @@ __global__ __launch_bounds__(LOC_T) void k_prod_join(const kr_product_site* __re
     u64 cnt = 0;
     if (i < ns)
         prod_walk(pg, sites, ns, rec, keys, idx, npairs, max_product, i, [&](const kr_product_site&, u32, bool, u32) { cnt++; });
-    u64 total;
-    const u64 before = near_block_scan(cnt, scan, &total);
-    if (!EMIT) {
-        if (threadIdx.x == 0) {
-            if (total >> 32) *overflow = 1u;
-            bcount[bl] = (total >> 32) ? 0u : (u32)total;
-        }
-        return;
-    }
-    if (i >= ns) return;
-    kr_product_hit* o = out + boff[bl] + before;
+    kr_product_hit* o = out + scan_epilogue<EMIT>(cnt, scan, bl, bcount, boff, overflow);
+    if (!EMIT || i >= ns) return;
     const kr_product_site a = sites[i];
     prod_walk(pg, sites, ns, rec, keys, idx, npairs, max_product, i, [&](const kr_product_site& b, u32 pr, bool plus, u32 n2) {
         const kr_product_site& lf = plus ? a : b;                 // the site of the left flank's text (A or rc(A))

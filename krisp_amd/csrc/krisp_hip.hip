@@ -43,13 +43,15 @@
 #include "k_inflate.inc"     // BGZF members inflated on the device, a lane per member (round 6)
 #include "k_gunzip.inc"      // one plain gzip member inflated on the device: chunks, block starts found by trial, windows
 #include "k_wide.inc"        // wide path kernels, copy kernel
-#include "k_locate.inc"      // the locate pass: flank-table scan of a genome's bases, separator list
+#include "k_scan.inc"        // what the three one-genome scans share: tile staging, block scan, two-pass epilogue, seed probe, separators
+#include "k_locate.inc"      // the locate pass: flank-table scan of a genome's bases
 #include "k_near.inc"        // the near-match pass: pigeonhole seeds of the targets, scan within Hamming distance M
 
 #include "k_products.inc"    // the product pass: sites of the flanks within M substitutions, joined into PCR products
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
 #include "h_intersect.inc"   // kr_intersect, candidate lists, kr_collect
 #include "h_wide.inc"        // kr_wide_run
+#include "h_scan.inc"        // ... and on the host: two-pass driver, separator list, seed table, launch geometry, fetches
 #include "h_locate.inc"      // kr_set_params_locate, kr_locate_*: where the surviving groups' windows lie
 #include "h_near.inc"        // kr_near_*: the windows of a genome within M substitutions of an ingroup window
 #include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome

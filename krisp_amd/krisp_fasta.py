@@ -1248,25 +1248,74 @@ def _group_flanks(groups, L, R):
     return np.frombuffer(text, dtype=np.uint8).reshape(-1, L + R)
 
 
-def _locate_genome(eng, path, read, k, omit_soft):
-    """one genome (its text as fasta.read_text gave it: `read`) on the device of the locate context -> (hits, its windows
-    as text rows, record starts, record IDs, RNA)"""
-    text, universal = read
-    while True:
-        try:
-            n, rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
-            break
-        except fasta.GzipTextLonger:
-            text, universal = fasta.read_text(path)     # (that file is read on the host from now on: read_text knows it)
-    hits = eng.locate(0)
-    rows = eng.locate_windows(k)
-    seps = eng.locate_seps(0)
-    # the record IDs: from the text the host holds, or -- a file the device inflated -- from the file read again
-    names = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
-    nrec = len(seps) + 1 if n else 0
-    if n and len(names) != nrec:
-        raise RuntimeError(f"{path}: {len(names)} record IDs, but the device's bases hold {nrec} records")
-    return hits, rows, seps, names, rna
+LOCATE_MAX_BASES = (1 << 33) - 65     # the packed path's limit (KR_MAX_BASES)
+
+
+def _scan_genomes(files, Le, De, Re, k, omit_soft, device, table):
+    """The per-file loop of the three passes that scan one genome at a time (locate_regions, near_matches,
+    predict_products): a locate context on `device`, table(eng) once, then every file uploaded alone as genome 0.
+    Yields (eng, file index, path, RNA, names): names() -> (the record separators, the record IDs), their count checked.
+    (The next file is read and inflated on a host thread while the device holds the current one: two texts at most.)"""
+    from concurrent.futures import ThreadPoolExecutor
+    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
+        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=LOCATE_MAX_BASES)
+        table(eng)
+        ahead = pool.submit(fasta.read_text, files[0]) if files else None
+        for fi, path in enumerate(files):
+            text, universal = ahead.result()
+            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
+            while True:
+                try:
+                    n, rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
+                    break
+                except fasta.GzipTextLonger:
+                    text, universal = fasta.read_text(path)     # (that file is read on the host from now on: read_text knows it)
+
+            def names():
+                seps = eng.locate_seps(0).astype(np.int64)
+                # the record IDs: from the text the host holds, or -- a file the device inflated -- from the file read again
+                ids = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
+                nrec = len(seps) + 1 if n else 0
+                if n and len(ids) != nrec:
+                    raise RuntimeError(f"{path}: {len(ids)} record IDs, but the device's bases hold {nrec} records")
+                return seps, ids
+
+            yield eng, fi, path, rna, names
+            del text, names
+
+
+def _record_coords(seps, pos):
+    """positions in the device's bases -> (index of the record, 0-based start in it); seps = the separators, ascending"""
+    ri = np.searchsorted(seps, pos)
+    rec_start = np.where(ri > 0, seps[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
+    return ri, pos - rec_start
+
+
+def _fill_shared(part, path, seps, ids, pos, strand):
+    """the columns every pass's dtype has: file, record, record_index, start, strand ('end' is the pass's own)"""
+    ri, start = _record_coords(seps, pos)
+    part["file"] = path
+    part["record"] = np.asarray(ids, dtype=object)[ri]
+    part["record_index"] = ri
+    part["start"] = start
+    part["strand"] = np.where(strand == 0, "+", "-")
+
+
+def _rows_text(rows, k, rna):
+    """(n, k) window bytes -> the n texts as objects, U for T in an RNA genome"""
+    if rna:
+        rows = np.where(rows == ord("T"), np.uint8(ord("U")), rows)
+    return np.ascontiguousarray(rows).view(f"S{k}").ravel().astype(f"U{k}").astype(object)
+
+
+def _sorted_parts(parts, dtype):
+    """parts = [(file index, the file's rows, their sort key)] -> one array ordered by the key, then the file's index
+    (stable: a file's rows of one key keep their order)"""
+    if not parts:
+        return np.empty(0, dtype=dtype)
+    out = np.concatenate([p for _, p, _ in parts])
+    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p, _ in parts])
+    return out[np.lexsort((fidx, np.concatenate([key for _, _, key in parts])))]
 
 
 def locate_regions(groups, ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=False, device=0):
@@ -1279,49 +1328,26 @@ def locate_regions(groups, ingroup_files, outgroup_files, L, R, amplicon_len, om
     forward strand, strand '+' (the window as written) or '-' (its reverse complement), sequence = the k-mer as the
     alignment lists it for that genome.  Rows in (region, file in command-line order, record_index, start, strand) order.
     For every group, genome label and sequence there are as many rows as the label occurs in that Amplicon's labels."""
-    from . import _native
     files = list(ingroup_files) + list(outgroup_files)
     k = amplicon_len
     Le, De, Re = codec.effective_geometry(L, k - L - R, R)
     flanks = _group_flanks(groups, Le, Re)
     if len(flanks) == 0:
         return np.empty(0, dtype=LOCATION)
-    from concurrent.futures import ThreadPoolExecutor
     parts = []
-    # (the next file is read and inflated on a host thread while the device holds the current one: two texts at most)
-    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
-        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=(1 << 33) - 65)   # (the packed path's limit, KR_MAX_BASES)
-        eng.locate_table(flanks)
-        ahead = pool.submit(fasta.read_text, files[0]) if files else None
-        for fi, path in enumerate(files):
-            read = ahead.result()
-            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
-            hits, rows, seps, names, rna = _locate_genome(eng, path, read, k, omit_soft)
-            del read
-            if len(hits) == 0:
-                continue
-            pos = hits["pos"].astype(np.int64)
-            ri = np.searchsorted(seps.astype(np.int64), pos)
-            rec_start = np.where(ri > 0, seps.astype(np.int64)[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
-            if rna:
-                rows = np.where(rows == ord("T"), np.uint8(ord("U")), rows)
-            part = np.empty(len(hits), dtype=LOCATION)
-            part["region"] = hits["group"]
-            part["file"] = path
-            part["record"] = np.asarray(names, dtype=object)[ri]
-            part["record_index"] = ri
-            part["start"] = pos - rec_start
-            part["end"] = part["start"] + k
-            part["strand"] = np.where(hits["strand"] == 0, "+", "-")
-            part["sequence"] = np.ascontiguousarray(rows).view(f"S{k}").ravel().astype(f"U{k}").astype(object)
-            parts.append((fi, part))
-    if not parts:
-        return np.empty(0, dtype=LOCATION)
-    out = np.concatenate([p for _, p in parts])
-    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p in parts])
-    # (a file's rows are in (position, strand) order already: a stable sort by (region, file) keeps it)
-    order = np.lexsort((fidx, out["region"]))
-    return out[order]
+    for eng, fi, path, rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device, lambda eng: eng.locate_table(flanks)):
+        hits = eng.locate(0)
+        rows = eng.locate_windows(k)
+        seps, ids = names()             # (checked for a genome without hits too)
+        if len(hits) == 0:
+            continue
+        part = np.empty(len(hits), dtype=LOCATION)
+        _fill_shared(part, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        part["region"] = hits["group"]
+        part["end"] = part["start"] + k
+        part["sequence"] = _rows_text(rows, k, rna)
+        parts.append((fi, part, part["region"]))       # (a file's rows are in (position, strand) order already)
+    return _sorted_parts(parts, LOCATION)
 
 
 def write_locations(path, locs):
@@ -1393,60 +1419,28 @@ def near_matches(groups, ingroup_files, outgroup_files, L, R, amplicon_len, mism
     t_region = np.array([i for i, _ in targets], dtype=np.uint32)
     t_text = np.array([t for _, t in targets], dtype=object)
     t_bytes = np.frombuffer("".join(t for _, t in targets).encode("ascii"), dtype=np.uint8).reshape(-1, k)
-    from concurrent.futures import ThreadPoolExecutor
     parts = []
-    # (the next file is read and inflated on a host thread while the device holds the current one: two texts at most)
-    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
-        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=(1 << 33) - 65)
-        eng.near_table(t_bytes, mismatches)
-        ahead = pool.submit(fasta.read_text, files[0]) if files else None
-        for fi, path in enumerate(files):
-            read = ahead.result()
-            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
-            text, universal = read
-            while True:
-                try:
-                    n, rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
-                    break
-                except fasta.GzipTextLonger:
-                    text, universal = fasta.read_text(path)
-            hits = eng.near(0)
-            if len(hits) == 0:
-                del read, text
-                continue
-            rows = eng.near_windows(k)
-            seps = eng.locate_seps(0).astype(np.int64)
-            names = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
-            del read, text
-            if len(names) != len(seps) + 1:
-                raise RuntimeError(f"{path}: {len(names)} record IDs, but the device's bases hold {len(seps) + 1} records")
-            pos = hits["pos"].astype(np.int64)
-            ri = np.searchsorted(seps, pos)
-            rec_start = np.where(ri > 0, seps[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
-            if rna:
-                rows = np.where(rows == ord("T"), np.uint8(ord("U")), rows)
-            tg = hits["target"].astype(np.int64)
-            # (a file's hits come in position order; within the table they go by target, then position, then strand)
-            order = np.lexsort((hits["strand"], pos, tg))
-            part = np.empty(len(hits), dtype=NEAR)
-            part["region"] = t_region[tg]
-            part["target"] = t_text[tg]
-            part["file"] = path
-            part["record"] = np.asarray(names, dtype=object)[ri]
-            part["record_index"] = ri
-            part["start"] = pos - rec_start
-            part["end"] = part["start"] + k
-            part["strand"] = np.where(hits["strand"] == 0, "+", "-")
-            part["mismatches"] = hits["mismatches"]
-            part["flank_mismatches"] = hits["flank_mismatches"]
-            part["sequence"] = np.ascontiguousarray(rows).view(f"S{k}").ravel().astype(f"U{k}").astype(object)
-            parts.append((fi, part[order], tg[order]))
-    if not parts:
-        return np.empty(0, dtype=NEAR)
-    out = np.concatenate([p for _, p, _ in parts])
-    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p, _ in parts])
-    tidx = np.concatenate([t for _, _, t in parts])
-    return out[np.lexsort((fidx, tidx))]       # (stable: a file's rows of one target keep their order)
+    for eng, fi, path, rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device,
+                                                   lambda eng: eng.near_table(t_bytes, mismatches)):
+        hits = eng.near(0)
+        if len(hits) == 0:
+            continue
+        rows = eng.near_windows(k)
+        seps, ids = names()
+        pos = hits["pos"].astype(np.int64)
+        tg = hits["target"].astype(np.int64)
+        part = np.empty(len(hits), dtype=NEAR)
+        _fill_shared(part, path, seps, ids, pos, hits["strand"])
+        part["region"] = t_region[tg]
+        part["target"] = t_text[tg]
+        part["end"] = part["start"] + k
+        part["mismatches"] = hits["mismatches"]
+        part["flank_mismatches"] = hits["flank_mismatches"]
+        part["sequence"] = _rows_text(rows, k, rna)
+        # (a file's hits come in position order; within the table they go by target, then position, then strand)
+        order = np.lexsort((hits["strand"], pos, tg))
+        parts.append((fi, part[order], tg[order]))
+    return _sorted_parts(parts, NEAR)
 
 
 def write_near(path, rows):
@@ -1516,56 +1510,25 @@ def predict_products(groups, ingroup_files, outgroup_files, L, R, amplicon_len, 
     left, li = np.unique(flanks[:, :Le], axis=0, return_inverse=True)
     right, ri_ = np.unique(flanks[:, Le:], axis=0, return_inverse=True)
     pairs = np.stack([li.ravel(), ri_.ravel()], axis=1).astype(np.uint32)
-    from concurrent.futures import ThreadPoolExecutor
     parts = []
-    # (the next file is read and inflated on a host thread while the device holds the current one: two texts at most)
-    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
-        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=(1 << 33) - 65)
-        eng.products_table(left, right, pairs, mismatches, max_product)
-        ahead = pool.submit(fasta.read_text, files[0]) if files else None
-        for fi, path in enumerate(files):
-            read = ahead.result()
-            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
-            text, universal = read
-            while True:
-                try:
-                    n, _rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
-                    break
-                except fasta.GzipTextLonger:
-                    text, universal = fasta.read_text(path)
-            hits = eng.products(0)
-            if len(hits) == 0:
-                del read, text
-                continue
-            seps = eng.locate_seps(0).astype(np.int64)
-            names = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
-            del read, text
-            if len(names) != len(seps) + 1:
-                raise RuntimeError(f"{path}: {len(names)} record IDs, but the device's bases hold {len(seps) + 1} records")
-            pos = hits["pos"].astype(np.int64)
-            ri = np.searchsorted(seps, pos)
-            rec_start = np.where(ri > 0, seps[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
-            part = np.empty(len(hits), dtype=PRODUCT)
-            part["region"] = hits["pair"]
-            part["file"] = path
-            part["record"] = np.asarray(names, dtype=object)[ri]
-            part["record_index"] = ri
-            part["start"] = pos - rec_start
-            part["length"] = hits["length"]
-            part["end"] = part["start"] + part["length"]
-            part["strand"] = np.where(hits["strand"] == 0, "+", "-")
-            part["left_mismatches"] = hits["left_mm"]
-            part["right_mismatches"] = hits["right_mm"]
-            part["left_end_mismatches"] = hits["left_end_mm"]
-            part["right_end_mismatches"] = hits["right_end_mm"]
-            parts.append((fi, part))
-    if not parts:
-        return np.empty(0, dtype=PRODUCT)
-    out = np.concatenate([p for _, p in parts])
-    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p in parts])
-    # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start) --:
-    # a stable sort by (region, file) keeps it)
-    return out[np.lexsort((fidx, out["region"]))]
+    for eng, fi, path, _rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device,
+                                                    lambda eng: eng.products_table(left, right, pairs, mismatches, max_product)):
+        hits = eng.products(0)
+        if len(hits) == 0:
+            continue
+        seps, ids = names()
+        part = np.empty(len(hits), dtype=PRODUCT)
+        _fill_shared(part, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        part["region"] = hits["pair"]
+        part["length"] = hits["length"]
+        part["end"] = part["start"] + part["length"]
+        part["left_mismatches"] = hits["left_mm"]
+        part["right_mismatches"] = hits["right_mm"]
+        part["left_end_mismatches"] = hits["left_end_mm"]
+        part["right_end_mismatches"] = hits["right_end_mm"]
+        # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start))
+        parts.append((fi, part, part["region"]))
+    return _sorted_parts(parts, PRODUCT)
 
 
 def write_products(path, rows):
