@@ -361,6 +361,43 @@ int64_t kr_products_fetch(kr_ctx*, kr_product_hit* out, size_t cap);
 /* the sites of the latest scan, as the device lists them.  Returns their number; out == NULL: the number only */
 int64_t kr_products_sites(kr_ctx*, kr_product_site* out, size_t cap);
 
+/* ---- a primer pair per region (krisp_fasta --design-primers) -----------------------------------------------------------
+ * Replaces no seam of the reference: it designs with the third-party Primer3.  This is a small designer of its own whose
+ * every figure is an integer (DESIGN §15 has the definition): nearest-neighbour melting temperatures in mK, the filters of
+ * the command line's primer options, a duplex figure over ungapped antiparallel alignments in the place of Primer3's *_TH
+ * values, the passing pair of least penalty with a fixed tie rule.  It runs on the device in csrc/k_design.inc, a
+ * wavefront per region, in any context (no genome, no parameters of another pass are needed).
+ *
+ * kr_design_table: the model's integers (krisp_amd/thermo.py holds them; the library has no copy) and the options.
+ * Bases are coded A C G T = 0 1 2 3; nn_*[4 x + y] is the step xy read 5'->3', term_*[x] a terminal base; dh in cal/mol,
+ * ds in 0.001 cal/(mol K), temperatures in mK, gc_lo / gc_hi in percent.  KR_ERR_PARAM unless 10 <= size_lo <= size_hi
+ * <= 60, every range is ordered, 0 <= gc_clamp <= size_lo, max_end_gc >= 0, and the model keeps every duplex's dH and dS
+ * negative (every step's dH + two terminals < 0, conc + two terminals <= -4000). */
+typedef struct {
+    int32_t nn_dh[16], nn_ds[16], term_dh[4], term_ds[4];
+    int32_t sym_ds, salt_ds, conc_ds, conc_self_ds;
+    int32_t size_lo, size_hi, tm_lo, tm_hi, tm_opt, gc_lo, gc_hi, amp_lo, amp_hi, max_sec, gc_clamp, max_end_gc;
+} kr_design_params;
+int kr_design_table(kr_ctx*, const kr_design_params* params);
+/* one region's answer, 64 bytes: found = 1 and the pair, or all zero.  Starts are template indices of the leftmost base
+ * (the right primer is the reverse complement of template[right_start, right_start + right_len)); temperatures and
+ * duplex figures in mK (0: no run of two pairs); *_gc = the number of G and C; penalties in 1/1000 */
+typedef struct {
+    uint32_t found, product_size, pair_penalty;
+    uint16_t left_start, left_len, right_start, right_len;
+    int32_t left_tm, right_tm;
+    uint16_t left_gc, right_gc;
+    uint32_t left_penalty, right_penalty;
+    int32_t left_self_any, left_self_end, right_self_any, right_self_end, pair_any, pair_end;
+} kr_design_record;
+/* nregions templates of L + D + R bytes each (upper case, U written as T; any other letter than A C G T removes the
+ * candidates that cover it), in batches so that any count fits.  Returns the number of regions with a pair.
+ * KR_ERR_PARAM for a flank above 1023 or a template above 2047 bytes; KR_ERR_CAPACITY when the candidate tables of one
+ * region (4 bytes per start and length of either flank) exceed the LDS of a workgroup. */
+int64_t kr_design_run(kr_ctx*, const uint8_t* templates, uint64_t nregions, int L, int D, int R);
+/* the records of the latest run, one per region in the order given */
+int64_t kr_design_fetch(kr_ctx*, kr_design_record* out, size_t cap);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

@@ -24,6 +24,11 @@ PRODUCT_SITE = np.dtype([("pos", "<u8"), ("entry", "<u4"), ("mismatches", "u1"),
                          ("pad", "<u2")])                                      # kr_product_site
 PRODUCT_HIT = np.dtype([("pos", "<u8"), ("length", "<u4"), ("pair", "<u4"), ("strand", "u1"), ("left_mm", "u1"),
                         ("right_mm", "u1"), ("left_end_mm", "u1"), ("right_end_mm", "u1"), ("pad", "u1", (3,))])   # kr_product_hit
+DESIGN_RECORD = np.dtype([("found", "<u4"), ("product_size", "<u4"), ("pair_penalty", "<u4"), ("left_start", "<u2"),
+                          ("left_len", "<u2"), ("right_start", "<u2"), ("right_len", "<u2"), ("left_tm", "<i4"), ("right_tm", "<i4"),
+                          ("left_gc", "<u2"), ("right_gc", "<u2"), ("left_penalty", "<u4"), ("right_penalty", "<u4"),
+                          ("left_self_any", "<i4"), ("left_self_end", "<i4"), ("right_self_any", "<i4"),
+                          ("right_self_end", "<i4"), ("pair_any", "<i4"), ("pair_end", "<i4")])             # kr_design_record
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -107,6 +112,9 @@ SYMBOLS = [
     ("kr_products_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_products_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_products_sites", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_design_table", _c.c_int, [_P, _P]),
+    ("kr_design_run", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
+    ("kr_design_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -723,6 +731,19 @@ class Engine:
         if n:
             self._check(self.lib.kr_products_sites(self.ctx, _ptr(out), n), "kr_products_sites")
         return out[:n]
+
+    def design_table(self, params):
+        """params: thermo.Params, the model's integers and the primer options (kr_design_table)"""
+        self._check(self.lib.kr_design_table(self.ctx, ctypes.byref(params)), "kr_design_table")
+
+    def design(self, templates, L, D, R):
+        """templates: uint8 [regions, L + D + R] (upper case, T for U) -> DESIGN_RECORD array, one per region
+        (kr_design_run, kr_design_fetch)"""
+        t = np.ascontiguousarray(templates, dtype=np.uint8).reshape(-1, L + D + R)
+        self._check(self.lib.kr_design_run(self.ctx, _ptr(t) if t.size else None, len(t), L, D, R), "kr_design_run")
+        out = np.empty(max(len(t), 1), dtype=DESIGN_RECORD)
+        self._check(self.lib.kr_design_fetch(self.ctx, _ptr(out), len(t)), "kr_design_fetch")
+        return out[:len(t)]
 
     # ---- timing
     def sync(self):

@@ -223,6 +223,14 @@ struct kr_ctx {
         int64_t nsites = -1, nhits = -1;
         DevBuf arena, table, list, bitmap, pairkeys, pairidx, seps, sites, rec, hits;
     } prod;
+    // the primer design pass (kr_design_*: h_design.inc): no genome, no geometry of another pass
+    struct Design {
+        bool on = false;
+        kr_design_params params{};
+        int64_t nrec = -1;
+        DevBuf par, tmpl, rec;
+        std::vector<kr_design_record> out;      // the records of the latest run, all batches
+    } design;
 };
 
 static int fail(kr_ctx* c, int code, const char* fmt, ...) {
@@ -524,6 +532,9 @@ void kr_destroy(kr_ctx* c) {
         auto& pr = c->prod;
         DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.pairkeys, &pr.pairidx, &pr.seps, &pr.sites, &pr.rec, &pr.hits};
         for (DevBuf* b : pb) release(c, *b);
+        auto& ds = c->design;
+        DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec};
+        for (DevBuf* b : db) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);
     for (auto e : c->pool) (void)hipEventDestroy(e);

@@ -1,0 +1,98 @@
+// h_design.inc -- part of krisp_hip.hip (one translation unit): host side of the primer design pass (k_design.inc): the
+// check and upload of the model and options, the run over the regions' templates in batches, the records.  The pass needs
+// no genome and no parameters of another pass: any context takes it.  On the device live the 224 bytes of the parameters
+// and, per batch, the templates (L + D + R bytes a region) and the records (64 bytes a region); the records of all batches
+// are kept on the host.
+#define DES_BATCH_BYTES ((size_t)64 << 20)      // template bytes of one batch
+#define DES_BATCH_REGIONS ((u64)1 << 20)        // ... and its regions at most (a workgroup each)
+
+int kr_design_table(kr_ctx* c, const kr_design_params* p) {
+    if (!c || !p) return fail(c, KR_ERR_PARAM, "kr_design_table: null argument");
+    auto& d = c->design;
+    d.on = false;
+    d.nrec = -1;
+    if (p->size_lo < 10 || p->size_hi > 60 || p->size_hi < p->size_lo)
+        return fail(c, KR_ERR_PARAM, "kr_design_table: 10 <= size_lo <= size_hi <= 60 (got %d .. %d)", p->size_lo, p->size_hi);
+    if (p->tm_hi < p->tm_lo || p->gc_hi < p->gc_lo || p->amp_hi < p->amp_lo)
+        return fail(c, KR_ERR_PARAM, "kr_design_table: a range whose upper bound lies below its lower (tm %d .. %d, gc %d .. %d, product %d .. %d)",
+                    p->tm_lo, p->tm_hi, p->gc_lo, p->gc_hi, p->amp_lo, p->amp_hi);
+    if (p->gc_clamp < 0 || p->gc_clamp > p->size_lo || p->max_end_gc < 0)
+        return fail(c, KR_ERR_PARAM, "kr_design_table: 0 <= gc_clamp <= size_lo and max_end_gc >= 0 (got %d, %d)", p->gc_clamp, p->max_end_gc);
+    // the kernel divides -dH 10^6 by -dS as unsigned numbers and keeps a Tm in an int: every duplex of two pairs or more has
+    // dH < 0 and dS <= -4000, and no entry is beyond 16 bits and a half
+    int max_term_dh = 0, max_term_ds = 0, max_nn_dh = INT32_MIN, max_nn_ds = INT32_MIN;
+    bool small = true;
+    for (int i = 0; i < 4; i++) {
+        max_term_dh = std::max(max_term_dh, p->term_dh[i]);
+        max_term_ds = std::max(max_term_ds, p->term_ds[i]);
+        small = small && std::abs((long long)p->term_dh[i]) < 100000 && std::abs((long long)p->term_ds[i]) < 100000;
+    }
+    for (int i = 0; i < 16; i++) {
+        max_nn_dh = std::max(max_nn_dh, p->nn_dh[i]);
+        max_nn_ds = std::max(max_nn_ds, p->nn_ds[i]);
+        small = small && std::abs((long long)p->nn_dh[i]) < 100000 && std::abs((long long)p->nn_ds[i]) < 100000;
+    }
+    const long long worst_ds = (long long)std::max(p->conc_ds, p->conc_self_ds + p->sym_ds) + 2ll * max_term_ds;
+    if (!small || (long long)max_nn_dh + 2ll * max_term_dh >= 0 || max_nn_ds > 0 || p->salt_ds > 0 || worst_ds > -4000)
+        return fail(c, KR_ERR_PARAM, "kr_design_table: the model does not keep every duplex's dH below 0 and dS at -4000 or below");
+    const long long worst_pen = 2 * (std::max(std::abs((long long)p->tm_lo - p->tm_opt), std::abs((long long)p->tm_hi - p->tm_opt)) +
+                                     500ll * (p->size_hi - p->size_lo));
+    if (worst_pen >= (1ll << 30) - 1)
+        return fail(c, KR_ERR_PARAM, "kr_design_table: a pair's penalty may reach %lld (the limit is 2^30 - 2)", worst_pen);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, d.par, sizeof *p))) return rc;
+    HIPCHK(c, hipMemcpy(d.par.p, p, sizeof *p, hipMemcpyHostToDevice));
+    d.params = *p;
+    d.on = true;
+    return KR_OK;
+}
+
+int64_t kr_design_run(kr_ctx* c, const uint8_t* templates, uint64_t nregions, int L, int D, int R) {
+    if (!c || !c->design.on) return fail(c, KR_ERR_STATE, "kr_design_table first");
+    auto& d = c->design;
+    d.nrec = -1;
+    if (L < 0 || D < 0 || R < 0 || L > DES_MAX_FLANK || R > DES_MAX_FLANK || L + D + R > DES_MAX_TEMPLATE || L + D + R < 1)
+        return fail(c, KR_ERR_PARAM, "kr_design_run: flanks of at most %d and a template of 1 .. %d bytes (got %d/%d/%d)", DES_MAX_FLANK,
+                    DES_MAX_TEMPLATE, L, D, R);
+    if (!templates && nregions) return fail(c, KR_ERR_PARAM, "kr_design_run: null templates");
+    HIPCHK(c, hipSetDevice(c->device));
+    DesignGeom g;
+    design_geom(L, D, R, d.params.size_lo, d.params.size_hi, &g);
+    int lds_max = 65536;
+    (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device);
+    if ((size_t)g.lds_bytes > (size_t)lds_max)
+        return fail(c, KR_ERR_CAPACITY, "kr_design_run: the candidate tables of a %d/%d/%d region with primers of %d .. %d bases take %u "
+                    "bytes of LDS (a workgroup has %d): a narrower --primer_size", L, D, R, d.params.size_lo, d.params.size_hi,
+                    g.lds_bytes, lds_max);
+    HIPCHK(c, hipFuncSetAttribute((const void*)k_design, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
+    try {
+        d.out.assign(nregions, kr_design_record{});
+    } catch (const std::bad_alloc&) {
+        return fail(c, KR_ERR_CAPACITY, "kr_design_run: no host memory for %llu records", (unsigned long long)nregions);
+    }
+    const u64 batch = std::max<u64>(1, std::min<u64>(DES_BATCH_REGIONS, DES_BATCH_BYTES / g.W));
+    int64_t found = 0;
+    for (u64 at = 0; at < nregions; at += batch) {
+        const u64 nb = std::min<u64>(batch, nregions - at);
+        int rc;
+        if ((rc = ensure(c, d.tmpl, nb * g.W)) || (rc = ensure(c, d.rec, nb * sizeof(kr_design_record)))) return rc;
+        HIPCHK(c, hipMemcpy(d.tmpl.p, templates + at * g.W, nb * g.W, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_design, dim3((u32)nb), dim3(DES_T), g.lds_bytes, c->stream, (const uint8_t*)d.tmpl.p, (u32)nb, g,
+                           (const kr_design_params*)d.par.p, (kr_design_record*)d.rec.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(d.out.data() + at, d.rec.p, nb * sizeof(kr_design_record), hipMemcpyDeviceToHost));
+        for (u64 i = 0; i < nb; i++) found += d.out[at + i].found;
+    }
+    d.nrec = (int64_t)nregions;
+    return found;
+}
+
+int64_t kr_design_fetch(kr_ctx* c, kr_design_record* out, size_t cap) {
+    if (!c || c->design.nrec < 0) return fail(c, KR_ERR_STATE, "kr_design_run first");
+    const auto& d = c->design;
+    if ((size_t)d.nrec > cap) return fail(c, KR_ERR_CAPACITY, "record buffer too small: %lld > %zu", (long long)d.nrec, cap);
+    if (d.nrec) memcpy(out, d.out.data(), (size_t)d.nrec * sizeof(kr_design_record));
+    return d.nrec;
+}

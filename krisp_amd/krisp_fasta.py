@@ -1544,6 +1544,52 @@ def write_products(path, rows):
 
 
 # ----------------------------------------------------------------------------
+# a primer pair per region, designed on the device (--design-primers)
+# ----------------------------------------------------------------------------
+def design_templates(groups, ingroup_labels):
+    """the templates of the groups (primers.design_template) -> (uint8 [groups, L + D + R], L, D, R)"""
+    from . import primers
+    ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
+    texts, geo = [], (0, 0, 0)
+    for g in groups:
+        geo = (len(g[0].left), len(g[0].diag), len(g[0].right))
+        texts.append(primers.design_template(g, ingroup))
+    k = sum(geo)
+    if any(len(t) != k for t in texts):
+        raise ValueError("design_templates: groups of more than one geometry")
+    rows = np.frombuffer("".join(texts).encode("ascii"), dtype=np.uint8).reshape(len(texts), k) if texts else \
+        np.empty((0, max(k, 1)), dtype=np.uint8)
+    return (rows,) + geo
+
+
+def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(70, 150), primer_size=(25, 35), max_sec_tm=40,
+                   gc_clamp=1, max_end_gc=4, device=0):
+    """A primer pair for every region, on the device (kr_design_*): on the consensus of the region's ingroup
+    Amplicons -- the template --primer3 designs on -- a left primer inside the left flank and a right primer inside the
+    right flank, lengths within `primer_size`; nearest-neighbour Tm within `tm` (degrees Celsius), GC percent within `gc`,
+    no run of five equal bases, the last `gc_clamp` 3' bases G or C, at most `max_end_gc` G or C among the last five; the
+    duplex figures (the highest Tm of a run of Watson-Crick pairs in an ungapped antiparallel alignment: self_any, self_end,
+    pair_any, pair_end) at most `max_sec_tm`; the product within `amp_size`; of the passing pairs the one of least
+    penalty, ties to the smallest (left_start, left_len, right_start, right_len).  Every figure is an integer
+    (krisp_amd/thermo.py holds the model); no hairpins, no gapped or mismatched duplexes: this is not Primer3.
+    `groups` as find_regions* returned them.  Returns a _native.DESIGN_RECORD array, one row per group (found = 0: no
+    pair).  ValueError for figures the pass does not take (thermo.refusal)."""
+    from . import thermo
+    opts = dict(tm=tuple(tm), gc=tuple(gc), amp_size=tuple(amp_size), primer_size=tuple(primer_size), max_sec_tm=max_sec_tm,
+                gc_clamp=gc_clamp, max_end_gc=max_end_gc)
+    why = thermo.refusal(**opts)
+    if why is not None:
+        raise ValueError(why)
+    rows, L, D, R = design_templates(groups, ingroup_labels)
+    if len(rows) == 0:
+        from . import _native
+        return np.empty(0, dtype=_native.DESIGN_RECORD)
+    with _engine(device) as eng:
+        eng.design_table(thermo.params(**opts))
+        return eng.design(rows, L, D, R)
+
+
+# ----------------------------------------------------------------------------
 # stage functions (reference signatures)
 # ----------------------------------------------------------------------------
 def _hit_windows(sel, text, k):
@@ -1944,6 +1990,11 @@ def build_parser():
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
+    p.add_argument("--design-primers", action="store_true",
+                   help="Design a primer pair for every region found on the GPU, with the options below (no third-party\n"
+                        "package): an integer nearest-neighbour model, ungapped duplex figures in the place of Primer3's\n"
+                        "thermodynamic alignments, no hairpins. Regions without a pair are left out; --primer_size within\n"
+                        "10 .. 60; not with --primer3, --out_locations, --out_near or --out_products.")
     p.add_argument("--tm", type=int, nargs=2, metavar="INT", default=[53, 68])
     p.add_argument("--gc", type=int, nargs=2, metavar="INT", default=[40, 70])
     p.add_argument("--amp_size", type=int, nargs=2, metavar="INT", default=[70, 150])
@@ -1994,6 +2045,21 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)
     args = deduce_geometry(args, parser)
+    if args.design_primers:
+        from . import thermo
+        why = None
+        if args.primer3:
+            why = "--design-primers cannot be combined with --primer3 (one designer at a time)"
+        for opt, val, verb in (("--out_locations", args.out_locations, "located"), ("--out_near", args.out_near, "searched"),
+                               ("--out_products", args.out_products, "searched")):
+            if why is None and val is not None:
+                why = f"{opt} cannot be combined with --design-primers (the regions the designer keeps are not {verb})"
+        if why is None:
+            why = thermo.refusal(args.tm, args.gc, args.amp_size, args.primer_size, args.max_sec_tm, args.gc_clamp,
+                                 args.max_end_gc)
+        if why is not None:
+            print("ERROR: " + why, file=sys.stderr)
+            sys.exit(2)
     if args.out_locations is not None and args.primer3:
         print("ERROR: --out_locations cannot be combined with --primer3 (the regions Primer3 keeps are not located)",
               file=sys.stderr)
@@ -2075,6 +2141,14 @@ def main(argv=None):
         p3 = primers.settings(**{k: getattr(args, k) for k in ("tm", "gc", "amp_size", "primer_size", "max_sec_tm",
                                                               "gc_clamp", "max_end_gc")})
         csv_text, align_text = primers.render(groups, ingroup, p3, dot=args.dot_alignment)
+    elif args.design_primers:
+        from . import primers
+        if args.verbose:
+            print("Designing a primer pair for every region ... ", file=sys.stderr)
+        records = design_primers(groups, ingroup, device=locate_device,
+                                 **{k: getattr(args, k) for k in ("tm", "gc", "amp_size", "primer_size", "max_sec_tm",
+                                                                  "gc_clamp", "max_end_gc")})
+        csv_text, align_text = primers.render_designed(groups, ingroup, records, dot=args.dot_alignment)
     else:
         csv_text, align_text = amplicon.render(groups, ingroup, dot=args.dot_alignment)
     if args.out_csv is not None:

@@ -109,3 +109,91 @@ def render(groups, ingroup_labels, global_settings, dot=False):
         blocks.append("\n".join(lines) + "\n\n")
         csv.append(amplicon.render_csv_row(g, ingroup) + "," + ",".join(str(p3[t]) for t in CSV_TAGS))
     return "\n".join(csv) + "\n", "".join(blocks)
+
+
+# ----------------------------------------------------------------------------
+# --design-primers: the pair comes from the device (krisp_fasta.design_primers), this renders it
+# ----------------------------------------------------------------------------
+DESIGN_COLUMNS = ["product_size", "pair_penalty", "left_sequence", "right_sequence", "left_start", "left_length", "right_start",
+                  "right_length", "left_tm", "right_tm", "left_gc_percent", "right_gc_percent", "left_self_any", "left_self_end",
+                  "right_self_any", "right_self_end", "pair_compl_any", "pair_compl_end"]
+_COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def design_template(group, ingroup):
+    """the template `design` hands to Primer3 -- the consensus of the ingroup's Amplicons -- upper case, U written as T
+    (before the consensus is taken: a column of T and U is a T, where the DNA table of the renderer has no entry)"""
+    amps = group if (len(group) == 1 or ingroup is None) else [a for a in group if set(a.labels) <= ingroup]
+    return "".join(amplicon.collapse_to_iupac([getattr(a, f).upper().replace("U", "T") for a in amps])
+                   for f in ("left", "diag", "right"))
+
+
+def design_fields(template, rec):
+    """one found record (a row of _native.DESIGN_RECORD, or a mapping with its fields) as text, column by column, plus the
+    keys `annotate` reads.  Temperatures in degrees Celsius and penalties with three decimals, formatted from the integers"""
+    from . import thermo
+    r = {k: int(rec[k]) for k in ("product_size", "pair_penalty", "left_start", "left_len", "right_start", "right_len", "left_tm",
+                                  "right_tm", "left_gc", "right_gc", "left_penalty", "right_penalty", "left_self_any",
+                                  "left_self_end", "right_self_any", "right_self_end", "pair_any", "pair_end")}
+    left = template[r["left_start"]:r["left_start"] + r["left_len"]]
+    right = template[r["right_start"]:r["right_start"] + r["right_len"]][::-1].translate(_COMPLEMENT)
+    return {
+        "product_size": str(r["product_size"]), "pair_penalty": thermo.milli(r["pair_penalty"]),
+        "left_sequence": left, "right_sequence": right,
+        "left_start": str(r["left_start"]), "left_length": str(r["left_len"]),
+        "right_start": str(r["right_start"]), "right_length": str(r["right_len"]),
+        "left_tm": thermo.celsius(r["left_tm"]), "right_tm": thermo.celsius(r["right_tm"]),
+        "left_gc_percent": thermo.gc_percent(r["left_gc"], r["left_len"]),
+        "right_gc_percent": thermo.gc_percent(r["right_gc"], r["right_len"]),
+        "left_self_any": thermo.celsius(r["left_self_any"]), "left_self_end": thermo.celsius(r["left_self_end"]),
+        "right_self_any": thermo.celsius(r["right_self_any"]), "right_self_end": thermo.celsius(r["right_self_end"]),
+        "pair_compl_any": thermo.celsius(r["pair_any"]), "pair_compl_end": thermo.celsius(r["pair_end"]),
+        "left_penalty": thermo.milli(r["left_penalty"]), "right_penalty": thermo.milli(r["right_penalty"]),
+        # (Primer3's convention: a right primer is named by its 5' base, the rightmost of its site)
+        "PRIMER_LEFT_0": (r["left_start"], r["left_len"]),
+        "PRIMER_RIGHT_0": (r["right_start"] + r["right_len"] - 1, r["right_len"]),
+        "PRIMER_LEFT_0_SEQUENCE": left, "PRIMER_RIGHT_0_SEQUENCE": right,
+    }
+
+
+def design_stats_text(f):
+    """the statistics tables under an alignment block of --design-primers"""
+    names = ["start", "length", "tm", "gc_percent", "self_any", "self_end", "penalty"]
+    head = ["Direction"] + [n.title().replace("_", " ") for n in names]
+    pair = ["product_size", "pair_penalty", "pair_compl_any", "pair_compl_end"]
+    return ("\nPrimer statistics:\n" + _table(head, [["Forward"] + [f["left_" + n] for n in names],
+                                                     ["Reverse"] + [f["right_" + n] for n in names]])
+            + "\n\nPair statistics:\n" + _table([n.title().replace("_", " ") for n in pair], [[f[n] for n in pair]]))
+
+
+def render_designed(groups, ingroup_labels, records, dot=False):
+    """-> (csv_text, alignment_text) of --design-primers: records[i] is group i's answer; groups without a pair are left
+    out, as under --primer3.  A group whose consensus has no IUPAC letter (a column holding U) stops the renderer as it
+    stops amplicon.render: the groups of the blocks of PRINT_BLOCK already written stay, the rest is lost"""
+    import sys
+    ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
+    csv = [amplicon.CSV_HEADER + "," + ",".join(DESIGN_COLUMNS)]
+    blocks = []
+    index = []                                  # the group each written row came from
+    for gi, (g, rec) in enumerate(zip(groups, records)):
+        try:
+            row = amplicon.render_csv_row(g, ingroup)
+        except KeyError as e:
+            kept = gi // amplicon.PRINT_BLOCK * amplicon.PRINT_BLOCK
+            print(f"krisp_fasta: the reference's renderer stops at group {gi + 1} (KeyError: {e.args[0]!r} has no IUPAC "
+                  f"consensus letter, Amplicon.py:65); as there, the {kept} groups of the blocks already written stay and "
+                  f"the rest is lost", file=sys.stderr)
+            nkeep = sum(1 for i in index if i < kept)
+            del csv[1 + nkeep:]
+            del blocks[nkeep:]
+            break
+        if not int(rec["found"]):
+            continue
+        f = design_fields(design_template(g, ingroup), rec)
+        lines = amplicon.render_alignment(g, ingroup, dot).rstrip("\n").split("\n")
+        lines = annotate(lines, f, dot)
+        lines.append(design_stats_text(f))
+        blocks.append("\n".join(lines) + "\n\n")
+        csv.append(row + "," + ",".join(f[c] for c in DESIGN_COLUMNS))
+        index.append(gi)
+    return "\n".join(csv) + "\n", "".join(blocks)
