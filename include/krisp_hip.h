@@ -361,6 +361,36 @@ int64_t kr_products_fetch(kr_ctx*, kr_product_hit* out, size_t cap);
 /* the sites of the latest scan, as the device lists them.  Returns their number; out == NULL: the number only */
 int64_t kr_products_sites(kr_ctx*, kr_product_site* out, size_t cap);
 
+/* ---- predicted PCR products of designed primer pairs (krisp_fasta --out_primer_products) ------------------------------
+ * The product pass above for texts that each have a length of their own, 10 .. 60 letters: the primers kr_design_run
+ * picks lie anywhere inside their flanks and are of every length in --primer_size.  The definition is the product pass's
+ * with the entry's own length in the place of L and R: a site of entry e is a window of len(e) bases (the locate pass's
+ * window rules) within Hamming distance M of its text, the end mismatches are counted in the 5 columns at the primer's
+ * 3' end, and a product of the pair (A, B) is a site of A at s1 and of B at s2 (strand 0) or of rc(B) at s1 and of rc(A)
+ * at s2 (strand 1) on one record with s2 >= s1 + len(first) and s2 + len(second) - s1 <= max_product.  With all left
+ * texts of one length and all right texts of one length the sites and products are kr_products_*'s, byte for byte.  It
+ * runs in the locate context (kr_set_params_locate: only the soft-mask mode plays a part), on the device in
+ * csrc/k_primers.inc: every entry is seeded by the first smin columns of its text as it reads on the forward strand
+ * (smin = the shortest text of the table), a byte comparison over the entry's whole length decides.
+ *
+ * kr_primers_table: the texts one after the other (upper case, U written as T; left texts first; a left text is the
+ * primer as it reads on the template, a right text the template's text under the right primer), text t =
+ * text[offsets[t] - offsets[0], offsets[t + 1] - offsets[0]), nleft + nright + 1 ascending offsets; npairs rows of two
+ * u32 (row of left, row of right).  KR_ERR_PARAM for a length outside 10 .. 60, mismatches outside 0 .. 3, a pair index
+ * out of range, a pair twice, a max_product shorter than some pair's two texts together, a null table.  Returns the
+ * number of slots of the seed table; KR_ERR_CAPACITY for 2^24 texts or more, or a table that does not fit. */
+int64_t kr_primers_table(kr_ctx*, const uint8_t* text, const uint32_t* offsets, uint64_t nleft, uint64_t nright,
+                         const uint32_t* pairs, uint64_t npairs, int mismatches, uint32_t max_product);
+/* scans uploaded genome `id` as kr_products_scan does: its separators, its sites (position order; at one position by
+ * seed piece and the table's entry order; an (entry, pos) occurs once), their records, the join.  Returns the number of
+ * products.  Counted, scanned, written: the same bytes on every run.  KR_ERR_STATE "kr_primers_table first" without a
+ * table; KR_ERR_CAPACITY for 2^32 sites or products or more, or lists that do not fit. */
+int64_t kr_primers_scan(kr_ctx*, int id);
+/* the products of the latest scan in (pos, length, strand, pair) order */
+int64_t kr_primers_fetch(kr_ctx*, kr_product_hit* out, size_t cap);
+/* the sites of the latest scan, as the device lists them.  Returns their number; out == NULL: the number only */
+int64_t kr_primers_sites(kr_ctx*, kr_product_site* out, size_t cap);
+
 /* ---- a primer pair per region (krisp_fasta --design-primers) -----------------------------------------------------------
  * Replaces no seam of the reference: it designs with the third-party Primer3.  This is a small designer of its own whose
  * every figure is an integer (DESIGN §15 has the definition): nearest-neighbour melting temperatures in mK, the filters of

@@ -112,6 +112,10 @@ SYMBOLS = [
     ("kr_products_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_products_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_products_sites", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_primers_table", _c.c_int64, [_P, _P, _P, _c.c_uint64, _c.c_uint64, _P, _c.c_uint64, _c.c_int, _c.c_uint32]),
+    ("kr_primers_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_primers_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_primers_sites", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_design_table", _c.c_int, [_P, _P]),
     ("kr_design_run", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
     ("kr_design_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
@@ -730,6 +734,35 @@ class Engine:
         out = np.empty(max(n, 1), dtype=PRODUCT_SITE)
         if n:
             self._check(self.lib.kr_products_sites(self.ctx, _ptr(out), n), "kr_products_sites")
+        return out[:n]
+
+    def primers_table(self, texts, nleft, pairs, mismatches, max_product):
+        """texts: a list of bytes (upper case, T for U), each of its own length 10 .. 60, the first nleft of them left
+        texts, the others right texts (the template's text under the right primer); pairs: [np, 2] rows of (left, right)
+        -> slots of the seed table (kr_primers_table)"""
+        texts = [bytes(t) for t in texts]
+        offsets = np.zeros(len(texts) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum([len(t) for t in texts], dtype=np.int64)
+        text = np.frombuffer(b"".join(texts) + b"\0", dtype=np.uint8)      # (never empty: a pointer to pass)
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        return self._check(self.lib.kr_primers_table(self.ctx, _ptr(text), _ptr(offsets), nleft, len(texts) - nleft,
+                                                     _ptr(pr) if pr.size else None, len(pr), mismatches, max_product),
+                           "kr_primers_table")
+
+    def primer_products(self, gid):
+        """PRODUCT_HIT array of uploaded genome gid in (pos, length, strand, pair) order (kr_primers_scan)"""
+        n = self._check(self.lib.kr_primers_scan(self.ctx, gid), "kr_primers_scan")
+        out = np.empty(max(n, 1), dtype=PRODUCT_HIT)
+        self._check(self.lib.kr_primers_fetch(self.ctx, _ptr(out), n), "kr_primers_fetch")
+        return out[:n]
+
+    def primer_sites(self):
+        """the latest primer_products()'s primer sites as the device lists them: PRODUCT_SITE, position order
+        (kr_primers_sites)"""
+        n = self._check(self.lib.kr_primers_sites(self.ctx, None, 0), "kr_primers_sites")
+        out = np.empty(max(n, 1), dtype=PRODUCT_SITE)
+        if n:
+            self._check(self.lib.kr_primers_sites(self.ctx, _ptr(out), n), "kr_primers_sites")
         return out[:n]
 
     def design_table(self, params):

@@ -223,6 +223,14 @@ struct kr_ctx {
         int64_t nsites = -1, nhits = -1;
         DevBuf arena, table, list, bitmap, pairkeys, pairidx, seps, sites, rec, hits;
     } prod;
+    // the primer-product pass (kr_primers_*: h_primers.inc), in the locate context: texts of mixed lengths, smin .. maxlen
+    struct Prim {
+        int M = 0;
+        u32 max_product = 0, smin = 0, maxlen = 0;
+        u64 nleft = 0, nright = 0, npairs = 0, slots = 0;
+        int64_t nsites = -1, nhits = -1;
+        DevBuf arena, eoff, table, list, bitmap, pairkeys, pairidx, seps, sites, rec, hits;
+    } prim;
     // the primer design pass (kr_design_*: h_design.inc): no genome, no geometry of another pass
     struct Design {
         bool on = false;
@@ -532,6 +540,9 @@ void kr_destroy(kr_ctx* c) {
         auto& pr = c->prod;
         DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.pairkeys, &pr.pairidx, &pr.seps, &pr.sites, &pr.rec, &pr.hits};
         for (DevBuf* b : pb) release(c, *b);
+        auto& pm = c->prim;
+        DevBuf* mb[] = {&pm.arena, &pm.eoff, &pm.table, &pm.list, &pm.bitmap, &pm.pairkeys, &pm.pairidx, &pm.seps, &pm.sites, &pm.rec, &pm.hits};
+        for (DevBuf* b : mb) release(c, *b);
         auto& ds = c->design;
         DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec};
         for (DevBuf* b : db) release(c, *b);

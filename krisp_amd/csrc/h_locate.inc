@@ -24,6 +24,8 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     c->near.nhits = -1;
     c->prod.slots = 0;                          // (likewise: kr_products_table again)
     c->prod.nsites = c->prod.nhits = -1;
+    c->prim.slots = 0;                          // (another soft-mask mode: kr_primers_table again)
+    c->prim.nsites = c->prim.nhits = -1;
     c->wide.on = false;
     c->max_bases = max_bases;
     c->have_params = true;

@@ -188,12 +188,9 @@ int64_t kr_products_scan(kr_ctx* c, int id) {
     return (int64_t)np;
 }
 
-int64_t kr_products_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) {
-    int rc;
-    if ((rc = scan_ctx(c))) return rc;
-    const int64_t n = scan_fetch(c, c->prod.nhits, "kr_products_scan first", "product", c->prod.hits, out, cap, sizeof(kr_product_hit));
-    // the device lists them by opening site (position, then the sites' order there): positions ascend already, the
-    // products of one position are put in (length, strand, pair) order here
+// the products of one position in (length, strand, pair) order (kr_products_fetch, kr_primers_fetch: the device lists
+// them by opening site -- position, then the sites' order there --, so positions ascend already)
+static void prod_sort_positions(kr_product_hit* out, int64_t n) {
     auto less = [](const kr_product_hit& a, const kr_product_hit& b) {
         if (a.pos != b.pos) return a.pos < b.pos;
         if (a.length != b.length) return a.length < b.length;
@@ -206,6 +203,13 @@ int64_t kr_products_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) {
         if (j - i > 1) std::sort(out + i, out + j, less);
         i = j;
     }
+}
+
+int64_t kr_products_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) {
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
+    const int64_t n = scan_fetch(c, c->prod.nhits, "kr_products_scan first", "product", c->prod.hits, out, cap, sizeof(kr_product_hit));
+    prod_sort_positions(out, n);
     return n;
 }
 

@@ -48,6 +48,7 @@
 #include "k_near.inc"        // the near-match pass: pigeonhole seeds of the targets, scan within Hamming distance M
 
 #include "k_products.inc"    // the product pass: sites of the flanks within M substitutions, joined into PCR products
+#include "k_primers.inc"     // the primer-product pass: sites of primer texts of mixed lengths, joined into PCR products
 #include "k_design.inc"      // the primer design pass: a wavefront per region, integer thermodynamics, the best pair
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
 #include "h_intersect.inc"   // kr_intersect, candidate lists, kr_collect
@@ -56,6 +57,7 @@
 #include "h_locate.inc"      // kr_set_params_locate, kr_locate_*: where the surviving groups' windows lie
 #include "h_near.inc"        // kr_near_*: the windows of a genome within M substitutions of an ingroup window
 #include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome
+#include "h_primers.inc"     // kr_primers_*: in-silico PCR of designed primer pairs against a genome
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options
 #include "h_pgzip.inc"       // one gzip member inflated on several threads (host only)
 #include "h_ingest.inc"      // file -> inflate -> parse -> pinned upload buffer (host side)

@@ -1252,8 +1252,8 @@ LOCATE_MAX_BASES = (1 << 33) - 65     # the packed path's limit (KR_MAX_BASES)
 
 
 def _scan_genomes(files, Le, De, Re, k, omit_soft, device, table):
-    """The per-file loop of the three passes that scan one genome at a time (locate_regions, near_matches,
-    predict_products): a locate context on `device`, table(eng) once, then every file uploaded alone as genome 0.
+    """The per-file loop of the passes that scan one genome at a time (locate_regions, near_matches, predict_products,
+    primer_products): a locate context on `device`, table(eng) once, then every file uploaded alone as genome 0.
     Yields (eng, file index, path, RNA, names): names() -> (the record separators, the record IDs), their count checked.
     (The next file is read and inflated on a host thread while the device holds the current one: two texts at most.)"""
     from concurrent.futures import ThreadPoolExecutor
@@ -1532,7 +1532,7 @@ def predict_products(groups, ingroup_files, outgroup_files, L, R, amplicon_len, 
 
 
 def write_products(path, rows):
-    """the TSV of --out_products: PRODUCT_HEADER, then a line per row"""
+    """the TSV of --out_products and of --out_primer_products: PRODUCT_HEADER, then a line per row"""
     with open(path, "w") as f:
         f.write(PRODUCT_HEADER + "\n")
         f.writelines(f"{r}\t{fn}\t{rec}\t{ri}\t{s}\t{e}\t{st}\t{n}\t{lm}\t{rm}\t{le}\t{re_}\n"
@@ -1587,6 +1587,105 @@ def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(7
     with _engine(device) as eng:
         eng.design_table(thermo.params(**opts))
         return eng.design(rows, L, D, R)
+
+
+# ----------------------------------------------------------------------------
+# predicted PCR products of the designed primer pairs in every genome (--design-primers --out_primer_products)
+# ----------------------------------------------------------------------------
+def primer_products_refusal(amp_size, mismatches, max_product):
+    """why the primer-product pass does not take this distance and product length (one line), or None"""
+    if mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES:
+        return f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    if amp_size is not None and max_product < amp_size[1]:
+        return (f"--max-product must be at least the upper bound of --amp_size, {amp_size[1]} bases (got {max_product}): the "
+                "designed product itself would not be found")
+    if max_product >= 1 << 31:
+        return f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    return None
+
+
+def primer_pairs(rows, records):
+    """The table of the primer-product pass from the templates (design_templates) and design_primers' records: the
+    regions with found = 0 take no part, a region's left text is template[left_start, left_start + left_len) and its
+    right text template[right_start, right_start + right_len) (the template's text under the right primer), equal texts
+    are listed once (ordered by their bytes), equal (left, right) pairs of different regions once.  -> (left texts, right
+    texts, pairs [np, 2], regions of pair p as a list of lists): a region is named by its rank among the regions with
+    a pair."""
+    lt, rt = [], []
+    for row, r in zip(rows, records):
+        if not int(r["found"]):
+            continue
+        ls, ll, rs, rl = (int(r[f]) for f in ("left_start", "left_len", "right_start", "right_len"))
+        lt.append(bytes(row[ls:ls + ll]))
+        rt.append(bytes(row[rs:rs + rl]))
+    left, right = sorted(set(lt)), sorted(set(rt))
+    li = {t: i for i, t in enumerate(left)}
+    ri = {t: i for i, t in enumerate(right)}
+    regions = {}
+    for rank, (a, b) in enumerate(zip(lt, rt)):
+        regions.setdefault((li[a], ri[b]), []).append(rank)
+    keys = sorted(regions)
+    return left, right, np.array(keys, dtype=np.uint32).reshape(-1, 2), [regions[k] for k in keys]
+
+
+def primer_products(groups, records, ingroup_labels, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1,
+                    max_product=1000, omit_soft=False, device=0):
+    """In-silico PCR of the primer pairs design_primers picked (`records`, one per group) against every input genome:
+    predict_products with the designed primers in the place of the flanks.  A primer lies anywhere inside its flank, has a
+    length of its own within --primer_size and its own 3' end: a site is a window of the PRIMER'S length within
+    `mismatches` substitutions of it, left / right_end_mismatches count the PRODUCT_END columns at the primer's own 3' end,
+    and a product is a left primer's site and a right primer's on one record, facing each other, not overlapping, at most
+    `max_product` bases from end to end.  The texts are cut from design_templates(groups, ingroup_labels); regions without
+    a pair take no part.  A separate pass over the inputs on one device in the manner of locate_regions (kr_primers_*).
+    Returns a PRODUCT array whose `region` is the region's rank among the regions with a pair -- its data row in the CSV
+    of --design-primers when the renderer was not stopped --, the other columns and the rows' order as predict_products
+    gives them.  Neighbouring regions that get the same pair each have their rows.  ValueError for figures the pass does
+    not take."""
+    why = primer_products_refusal(None, mismatches, max_product)
+    if why is None and len(records) != len(groups):
+        why = f"primer_products: {len(records)} records for {len(groups)} groups"
+    if why is not None:
+        raise ValueError(why)
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    rows, _, _, _ = design_templates(groups, ingroup_labels)
+    left, right, pairs, regions = primer_pairs(rows, records)
+    if len(pairs) == 0:
+        return np.empty(0, dtype=PRODUCT)
+    for i, j in pairs.tolist():
+        if max_product < len(left[i]) + len(right[j]):
+            raise ValueError(f"--max-product must be at least a pair's two primers together, {len(left[i]) + len(right[j])} "
+                             f"bases (got {max_product})")
+    # the regions of pair p: reg[start[p] : start[p + 1]]
+    count = np.array([len(r) for r in regions], dtype=np.int64)
+    start = np.concatenate([[0], np.cumsum(count)])
+    reg = np.array([x for r in regions for x in r], dtype=np.uint32)
+    parts = []
+    for eng, fi, path, _rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device,
+                                                    lambda eng: eng.primers_table(left + right, len(left), pairs, mismatches,
+                                                                                  max_product)):
+        hits = eng.primer_products(0)
+        if len(hits) == 0:
+            continue
+        seps, ids = names()
+        # a hit of pair p is a row for every region of p
+        pr = hits["pair"].astype(np.int64)
+        each = count[pr]
+        hits = np.repeat(hits, each)
+        within = np.arange(len(hits)) - np.repeat(np.cumsum(each) - each, each)
+        part = np.empty(len(hits), dtype=PRODUCT)
+        _fill_shared(part, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        part["region"] = reg[np.repeat(start[pr], each) + within]
+        part["length"] = hits["length"]
+        part["end"] = part["start"] + part["length"]
+        part["left_mismatches"] = hits["left_mm"]
+        part["right_mismatches"] = hits["right_mm"]
+        part["left_end_mismatches"] = hits["left_end_mm"]
+        part["right_end_mismatches"] = hits["right_end_mm"]
+        # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start))
+        parts.append((fi, part, part["region"]))
+    return _sorted_parts(parts, PRODUCT)
 
 
 # ----------------------------------------------------------------------------
@@ -1983,10 +2082,19 @@ def build_parser():
                         "right_mismatches, left_end_mismatches, right_end_mismatches (those in the five 3' bases).  A separate\n"
                         "pass that reads every input again; flanks of at least 10 bases; not with --primer3.\n"
                         "(default: no products, no extra pass)")
+    p.add_argument("--out_primer_products", type=str, metavar="PATH",
+                   help="With --design-primers: also write the predicted PCR products of the designed primer pairs in every\n"
+                        "genome, the outgroups included: a window within --primer-mismatches substitutions of the left primer\n"
+                        "and one of the right primer on one record, facing each other, at most --max-product bases from end to\n"
+                        "end (either strand), as a tab-separated file with the columns of --out_products; region = the pair's\n"
+                        "data row in the CSV, the end mismatches are those in the primer's own five 3' bases.  A separate pass\n"
+                        "that reads every input again.  (default: no products, no extra pass)")
     p.add_argument("--primer-mismatches", type=int, default=None, metavar="INT",
-                   help="substitutions allowed in each flank of --out_products: 0 .. 3 (default: 1)")
+                   help="substitutions allowed in each flank of --out_products, in each primer of --out_primer_products:\n"
+                        "0 .. 3 (default: 1)")
     p.add_argument("--max-product", type=int, default=None, metavar="INT",
-                   help="longest product of --out_products in bases, at least the two flanks together (default: 1000)")
+                   help="longest product of --out_products / --out_primer_products in bases, at least the two flanks together /\n"
+                        "the upper bound of --amp_size (default: 1000)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -1994,7 +2102,8 @@ def build_parser():
                    help="Design a primer pair for every region found on the GPU, with the options below (no third-party\n"
                         "package): an integer nearest-neighbour model, ungapped duplex figures in the place of Primer3's\n"
                         "thermodynamic alignments, no hairpins. Regions without a pair are left out; --primer_size within\n"
-                        "10 .. 60; not with --primer3, --out_locations, --out_near or --out_products.")
+                        "10 .. 60; not with --primer3, --out_locations, --out_near or --out_products (the designed pairs are\n"
+                        "searched by --out_primer_products).")
     p.add_argument("--tm", type=int, nargs=2, metavar="INT", default=[53, 68])
     p.add_argument("--gc", type=int, nargs=2, metavar="INT", default=[40, 70])
     p.add_argument("--amp_size", type=int, nargs=2, metavar="INT", default=[70, 150])
@@ -2080,9 +2189,21 @@ def main(argv=None):
     if args.out_products is not None and args.primer3:
         print("ERROR: --out_products cannot be combined with --primer3 (the primers Primer3 designs are not searched)", file=sys.stderr)
         sys.exit(2)
+    if args.out_primer_products is not None and not args.design_primers:
+        print("ERROR: --out_primer_products needs --design-primers", file=sys.stderr)
+        sys.exit(2)
     for opt, val in (("--primer-mismatches", args.primer_mismatches), ("--max-product", args.max_product)):
-        if val is not None and args.out_products is None:
-            print(f"ERROR: {opt} needs --out_products", file=sys.stderr)
+        if val is not None and args.out_products is None and args.out_primer_products is None:
+            print(f"ERROR: {opt} needs --out_products or --out_primer_products", file=sys.stderr)
+            sys.exit(2)
+    if args.out_primer_products is not None:
+        if args.primer_mismatches is None:
+            args.primer_mismatches = 1
+        if args.max_product is None:
+            args.max_product = 1000
+        why = primer_products_refusal(args.amp_size, args.primer_mismatches, args.max_product)
+        if why is not None:
+            print("ERROR: " + why, file=sys.stderr)
             sys.exit(2)
     if args.out_products is not None:
         if args.primer_mismatches is None:
@@ -2182,6 +2303,15 @@ def main(argv=None):
                        predict_products(groups, args.files, args.outgroup, args.conserved_left, args.conserved_right, args.amplicon,
                                         mismatches=args.primer_mismatches, max_product=args.max_product,
                                         omit_soft=args.omit_soft, device=locate_device))
+    if args.out_primer_products is not None:
+        # (as the locations: for every group with a pair, on one device, written by rank 0)
+        if args.verbose:
+            print(f"Predicting the products of the designed primers with up to {args.primer_mismatches} mismatches each ... ",
+                  file=sys.stderr)
+        write_products(args.out_primer_products,
+                       primer_products(groups, records, ingroup, args.files, args.outgroup, args.conserved_left,
+                                       args.conserved_right, args.amplicon, mismatches=args.primer_mismatches,
+                                       max_product=args.max_product, omit_soft=args.omit_soft, device=locate_device))
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
