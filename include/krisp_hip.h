@@ -427,6 +427,23 @@ typedef struct {
 int64_t kr_design_run(kr_ctx*, const uint8_t* templates, uint64_t nregions, int L, int D, int R);
 /* the records of the latest run, one per region in the order given */
 int64_t kr_design_fetch(kr_ctx*, kr_design_record* out, size_t cap);
+/* The hairpin check (krisp_fasta --design-primers --hairpins): with it a candidate whose hairpin figure lies
+ * above max_sec is no candidate, as one whose self_any does.  The figure: over every fold c = i + j of the primer read
+ * 5'->3' and every maximal run of at least two Watson-Crick pairs (i, c - i) with j - i >= 4, the Tm of the run's bases on
+ * the 5' arm as a duplex's -- steps, both terminals, salt per step -- with loop_ds[l] in the place of the concentration
+ * term and no symmetry term, l = the bases the innermost pair encloses, 3 .. 56; 0 without such a run.  loop_ds is indexed
+ * by l (krisp_amd/thermo.py holds the values; the library has no copy); the entries 3 .. 56 are read.
+ * kr_design_hairpins: after kr_design_table (KR_ERR_STATE before one); NULL switches the check off again, and so does every
+ * later kr_design_table.  KR_ERR_PARAM unless for every l in 3 .. 56 |loop_ds[l]| < 100000 and
+ * max(nn_ds) + salt_ds + 2 max(term_ds) + loop_ds[l] <= -4000 (the table's own: every stem's dS stays at -4000 or below). */
+typedef struct {
+    int32_t loop_ds[64];
+} kr_hairpin_params;
+int kr_design_hairpins(kr_ctx*, const kr_hairpin_params* params);
+/* the hairpin figures of the latest run's pairs in mK: out[2 r] the left and out[2 r + 1] the right primer's of region r,
+ * 0 and 0 for a region without a pair; cap counts int32.  Returns the number of int32 written, two per region.
+ * KR_ERR_STATE when that run had the check off.  kr_design_record does not change with the check. */
+int64_t kr_design_fetch_hairpins(kr_ctx*, int32_t* out, size_t cap);
 
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics

@@ -29,6 +29,8 @@ DESIGN_RECORD = np.dtype([("found", "<u4"), ("product_size", "<u4"), ("pair_pena
                           ("left_gc", "<u2"), ("right_gc", "<u2"), ("left_penalty", "<u4"), ("right_penalty", "<u4"),
                           ("left_self_any", "<i4"), ("left_self_end", "<i4"), ("right_self_any", "<i4"),
                           ("right_self_end", "<i4"), ("pair_any", "<i4"), ("pair_end", "<i4")])             # kr_design_record
+# ... and, behind it, the pair's two figures of kr_design_fetch_hairpins: what Engine.design returns with the check on
+DESIGN_RECORD_HP = np.dtype(DESIGN_RECORD.descr + [("left_hairpin", "<i4"), ("right_hairpin", "<i4")])
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -119,6 +121,8 @@ SYMBOLS = [
     ("kr_design_table", _c.c_int, [_P, _P]),
     ("kr_design_run", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
     ("kr_design_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_design_hairpins", _c.c_int, [_P, _P]),
+    ("kr_design_fetch_hairpins", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -767,16 +771,33 @@ class Engine:
 
     def design_table(self, params):
         """params: thermo.Params, the model's integers and the primer options (kr_design_table)"""
+        self._design_hairpins = False             # (kr_design_table switches the check off, whatever it returns)
         self._check(self.lib.kr_design_table(self.ctx, ctypes.byref(params)), "kr_design_table")
+
+    def design_hairpins(self, params):
+        """params: thermo.HairpinParams -- hold every candidate of design() to max_sec for its hairpin figure too -- or
+        None: the check off again (kr_design_hairpins).  After design_table; the next design_table switches it off"""
+        self._design_hairpins = False
+        self._check(self.lib.kr_design_hairpins(self.ctx, None if params is None else ctypes.byref(params)), "kr_design_hairpins")
+        self._design_hairpins = params is not None
 
     def design(self, templates, L, D, R):
         """templates: uint8 [regions, L + D + R] (upper case, T for U) -> DESIGN_RECORD array, one per region
-        (kr_design_run, kr_design_fetch)"""
+        (kr_design_run, kr_design_fetch); after design_hairpins(params) a DESIGN_RECORD_HP array: the same fields and
+        the pair's two hairpin figures (kr_design_fetch_hairpins)"""
         t = np.ascontiguousarray(templates, dtype=np.uint8).reshape(-1, L + D + R)
         self._check(self.lib.kr_design_run(self.ctx, _ptr(t) if t.size else None, len(t), L, D, R), "kr_design_run")
         out = np.empty(max(len(t), 1), dtype=DESIGN_RECORD)
         self._check(self.lib.kr_design_fetch(self.ctx, _ptr(out), len(t)), "kr_design_fetch")
-        return out[:len(t)]
+        if not getattr(self, "_design_hairpins", False):
+            return out[:len(t)]
+        hp = np.empty((max(len(t), 1), 2), dtype=np.int32)
+        self._check(self.lib.kr_design_fetch_hairpins(self.ctx, _ptr(hp), 2 * len(t)), "kr_design_fetch_hairpins")
+        both = np.empty(len(t), dtype=DESIGN_RECORD_HP)
+        for name in DESIGN_RECORD.names:
+            both[name] = out[name][:len(t)]
+        both["left_hairpin"], both["right_hairpin"] = hp[:len(t), 0], hp[:len(t), 1]
+        return both
 
     # ---- timing
     def sync(self):

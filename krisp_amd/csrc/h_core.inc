@@ -236,8 +236,10 @@ struct kr_ctx {
         bool on = false;
         kr_design_params params{};
         int64_t nrec = -1;
-        DevBuf par, tmpl, rec;
+        bool hp = false, hp_ran = false;        // kr_design_hairpins is on; the latest run had it on
+        DevBuf par, tmpl, rec, hprec;
         std::vector<kr_design_record> out;      // the records of the latest run, all batches
+        std::vector<int32_t> hp_out;            // ... and, with the hairpin check, its two figures a region
     } design;
 };
 
@@ -544,7 +546,7 @@ void kr_destroy(kr_ctx* c) {
         DevBuf* mb[] = {&pm.arena, &pm.eoff, &pm.table, &pm.list, &pm.bitmap, &pm.pairkeys, &pm.pairidx, &pm.seps, &pm.sites, &pm.rec, &pm.hits};
         for (DevBuf* b : mb) release(c, *b);
         auto& ds = c->design;
-        DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec};
+        DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec, &ds.hprec};
         for (DevBuf* b : db) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);

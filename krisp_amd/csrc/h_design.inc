@@ -1,8 +1,9 @@
 // h_design.inc -- part of krisp_hip.hip (one translation unit): host side of the primer design pass (k_design.inc): the
 // check and upload of the model and options, the run over the regions' templates in batches, the records.  The pass needs
-// no genome and no parameters of another pass: any context takes it.  On the device live the 224 bytes of the parameters
-// and, per batch, the templates (L + D + R bytes a region) and the records (64 bytes a region); the records of all batches
-// are kept on the host.
+// no genome and no parameters of another pass: any context takes it.  On the device live the 224 bytes of the parameters,
+// behind them the 256 bytes of the hairpin check's loop table (kr_design_hairpins), and, per batch, the templates (L + D + R
+// bytes a region), the records (64 bytes a region) and, with the hairpin check, the hairpin figures (8 bytes a region); the
+// records and figures of all batches are kept on the host.
 #define DES_BATCH_BYTES ((size_t)64 << 20)      // template bytes of one batch
 #define DES_BATCH_REGIONS ((u64)1 << 20)        // ... and its regions at most (a workgroup each)
 
@@ -10,6 +11,7 @@ int kr_design_table(kr_ctx* c, const kr_design_params* p) {
     if (!c || !p) return fail(c, KR_ERR_PARAM, "kr_design_table: null argument");
     auto& d = c->design;
     d.on = false;
+    d.hp = d.hp_ran = false;
     d.nrec = -1;
     if (p->size_lo < 10 || p->size_hi > 60 || p->size_hi < p->size_lo)
         return fail(c, KR_ERR_PARAM, "kr_design_table: 10 <= size_lo <= size_hi <= 60 (got %d .. %d)", p->size_lo, p->size_hi);
@@ -41,10 +43,31 @@ int kr_design_table(kr_ctx* c, const kr_design_params* p) {
         return fail(c, KR_ERR_PARAM, "kr_design_table: a pair's penalty may reach %lld (the limit is 2^30 - 2)", worst_pen);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, d.par, sizeof *p))) return rc;
+    if ((rc = ensure(c, d.par, sizeof *p + sizeof(kr_hairpin_params)))) return rc;
     HIPCHK(c, hipMemcpy(d.par.p, p, sizeof *p, hipMemcpyHostToDevice));
     d.params = *p;
     d.on = true;
+    return KR_OK;
+}
+
+int kr_design_hairpins(kr_ctx* c, const kr_hairpin_params* h) {
+    if (!c || !c->design.on) return fail(c, KR_ERR_STATE, "kr_design_table first");
+    auto& d = c->design;
+    d.hp = false;
+    if (!h) return KR_OK;
+    // a stem has a step at least and two terminal bases: as in kr_design_table, its dS stays at -4000 or below (its dH is
+    // a duplex's, the loop's is 0)
+    const kr_design_params& p = d.params;
+    const long long stem_ds = (long long)*std::max_element(p.nn_ds, p.nn_ds + 16) + p.salt_ds +
+                              2ll * *std::max_element(p.term_ds, p.term_ds + 4);
+    for (int l = DES_MIN_LOOP; l <= DES_MAX_LOOP; l++)
+        if (std::abs((long long)h->loop_ds[l]) >= 100000 || stem_ds + h->loop_ds[l] > -4000)
+            return fail(c, KR_ERR_PARAM, "kr_design_hairpins: loop_ds[%d] = %d does not keep every stem's dS at -4000 or below "
+                        "(the least negative step with its salt and two terminals come to %lld), or lies beyond +-99999", l,
+                        h->loop_ds[l], stem_ds);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy((char*)d.par.p + sizeof p, h, sizeof *h, hipMemcpyHostToDevice));
+    d.hp = true;
     return KR_OK;
 }
 
@@ -52,22 +75,26 @@ int64_t kr_design_run(kr_ctx* c, const uint8_t* templates, uint64_t nregions, in
     if (!c || !c->design.on) return fail(c, KR_ERR_STATE, "kr_design_table first");
     auto& d = c->design;
     d.nrec = -1;
+    d.hp_ran = false;
+    const bool hp = d.hp;
+    const void* const kernel = hp ? (const void*)k_design<true> : (const void*)k_design<false>;
     if (L < 0 || D < 0 || R < 0 || L > DES_MAX_FLANK || R > DES_MAX_FLANK || L + D + R > DES_MAX_TEMPLATE || L + D + R < 1)
         return fail(c, KR_ERR_PARAM, "kr_design_run: flanks of at most %d and a template of 1 .. %d bytes (got %d/%d/%d)", DES_MAX_FLANK,
                     DES_MAX_TEMPLATE, L, D, R);
     if (!templates && nregions) return fail(c, KR_ERR_PARAM, "kr_design_run: null templates");
     HIPCHK(c, hipSetDevice(c->device));
     DesignGeom g;
-    design_geom(L, D, R, d.params.size_lo, d.params.size_hi, &g);
+    design_geom(L, D, R, d.params.size_lo, d.params.size_hi, hp, &g);
     int lds_max = 65536;
     (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device);
     if ((size_t)g.lds_bytes > (size_t)lds_max)
         return fail(c, KR_ERR_CAPACITY, "kr_design_run: the candidate tables of a %d/%d/%d region with primers of %d .. %d bases take %u "
                     "bytes of LDS (a workgroup has %d): a narrower --primer_size", L, D, R, d.params.size_lo, d.params.size_hi,
                     g.lds_bytes, lds_max);
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_design, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
+    HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
     try {
         d.out.assign(nregions, kr_design_record{});
+        d.hp_out.assign(hp ? 2 * nregions : 0, 0);
     } catch (const std::bad_alloc&) {
         return fail(c, KR_ERR_CAPACITY, "kr_design_run: no host memory for %llu records", (unsigned long long)nregions);
     }
@@ -77,15 +104,22 @@ int64_t kr_design_run(kr_ctx* c, const uint8_t* templates, uint64_t nregions, in
         const u64 nb = std::min<u64>(batch, nregions - at);
         int rc;
         if ((rc = ensure(c, d.tmpl, nb * g.W)) || (rc = ensure(c, d.rec, nb * sizeof(kr_design_record)))) return rc;
+        if (hp && (rc = ensure(c, d.hprec, nb * sizeof(int2)))) return rc;
         HIPCHK(c, hipMemcpy(d.tmpl.p, templates + at * g.W, nb * g.W, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_design, dim3((u32)nb), dim3(DES_T), g.lds_bytes, c->stream, (const uint8_t*)d.tmpl.p, (u32)nb, g,
-                           (const kr_design_params*)d.par.p, (kr_design_record*)d.rec.p);
+        if (hp)
+            hipLaunchKernelGGL(k_design<true>, dim3((u32)nb), dim3(DES_T), g.lds_bytes, c->stream, (const uint8_t*)d.tmpl.p, (u32)nb, g,
+                               (const kr_design_params*)d.par.p, (kr_design_record*)d.rec.p, (int2*)d.hprec.p);
+        else
+            hipLaunchKernelGGL(k_design<false>, dim3((u32)nb), dim3(DES_T), g.lds_bytes, c->stream, (const uint8_t*)d.tmpl.p, (u32)nb, g,
+                               (const kr_design_params*)d.par.p, (kr_design_record*)d.rec.p, (int2*)nullptr);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipMemcpy(d.out.data() + at, d.rec.p, nb * sizeof(kr_design_record), hipMemcpyDeviceToHost));
+        if (hp) HIPCHK(c, hipMemcpy(d.hp_out.data() + 2 * at, d.hprec.p, nb * sizeof(int2), hipMemcpyDeviceToHost));
         for (u64 i = 0; i < nb; i++) found += d.out[at + i].found;
     }
     d.nrec = (int64_t)nregions;
+    d.hp_ran = hp;
     return found;
 }
 
@@ -95,4 +129,14 @@ int64_t kr_design_fetch(kr_ctx* c, kr_design_record* out, size_t cap) {
     if ((size_t)d.nrec > cap) return fail(c, KR_ERR_CAPACITY, "record buffer too small: %lld > %zu", (long long)d.nrec, cap);
     if (d.nrec) memcpy(out, d.out.data(), (size_t)d.nrec * sizeof(kr_design_record));
     return d.nrec;
+}
+
+int64_t kr_design_fetch_hairpins(kr_ctx* c, int32_t* out, size_t cap) {
+    if (!c || c->design.nrec < 0) return fail(c, KR_ERR_STATE, "kr_design_run first");
+    const auto& d = c->design;
+    if (!d.hp_ran) return fail(c, KR_ERR_STATE, "kr_design_fetch_hairpins: the latest run had the hairpin check off (kr_design_hairpins)");
+    const size_t n = 2 * (size_t)d.nrec;
+    if (n > cap) return fail(c, KR_ERR_CAPACITY, "hairpin buffer too small: %zu > %zu", n, cap);
+    if (n) memcpy(out, d.hp_out.data(), n * sizeof(int32_t));
+    return (int64_t)n;
 }

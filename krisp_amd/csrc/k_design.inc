@@ -14,11 +14,18 @@
 //       is run by the wave on the lanes that pass, lowest key of the step first.  best only ever takes a pair that passed
 //       everything, and a pair is only passed over when its key is not below best: the result is the definition's argmin.
 //   3   the winner's figures again, one 64-byte record by plain vector stores.  No atomics, no scratch buffer in memory.
+// k_design<true> (kr_design_hairpins, DESIGN §17) also holds every candidate to max_sec for its hairpin figure: the loop
+// table (54 ints, loop lengths 3 .. 56) lies in LDS behind the model's, 1b runs des_hairpin on a survivor of 1a before its
+// self duplex, and 3 stores the winner's two figures into a second array of 8 bytes a region.  k_design<false> is the
+// kernel without any of it.
 #define DES_T 64
 #define DES_DEAD 0xffffffffu
 #define DES_TAB 48                  // ints of the table in LDS: nn_dh 16, nn_ds 16, term_dh 4, term_ds 4 (40, padded)
 #define DES_MAX_FLANK 1023          // (10-bit prefix counts)
 #define DES_MAX_TEMPLATE 2047       // (11-bit starts in the key)
+#define DES_MIN_LOOP 3              // bases a hairpin's innermost pair encloses at least ...
+#define DES_MAX_LOOP 56             // ... and at most: 60 bases, two pairs
+#define DES_LOOP_TAB 56             // ints of the loop table in LDS: entry l - DES_MIN_LOOP, 54 used
 
 struct DesignGeom {
     u32 L, D, R, W;
@@ -36,10 +43,10 @@ struct DesSide {
     u32 len, nlen;
 };
 
-__host__ __device__ inline void design_geom(int L, int D, int R, int size_lo, int size_hi, DesignGeom* g) {
+__host__ __device__ inline void design_geom(int L, int D, int R, int size_lo, int size_hi, bool hairpins, DesignGeom* g) {
     g->L = (u32)L; g->D = (u32)D; g->R = (u32)R; g->W = (u32)(L + D + R);
     g->len[0] = (u32)L; g->len[1] = (u32)R;
-    u32 o = DES_TAB * 4;
+    u32 o = (DES_TAB + (hairpins ? DES_LOOP_TAB : 0)) * 4;
     for (int q = 0; q < 2; q++) {
         const int n = (int)g->len[q];
         const int top = size_hi < n ? size_hi : n;
@@ -121,17 +128,46 @@ __device__ __forceinline__ void des_duplex(const int* tab, const DesSide& X, u32
     *end_out = des_wave_max(end);
 }
 
+// the hairpin figure of the oligo X[u, u + n) (DESIGN §17), by the whole wave: a lane per fold c = i + j, 4 <= c <= 2 n - 6
+// (2 n - 9 folds: a second round of lanes from n = 37 on), a walk along i from the outermost pair inwards as far as j - i
+// >= 4 holds; every maximal run of >= 2 Watson-Crick pairs gives the Tm of its bases on the 5' arm with the loop's dS
+// (loop[l - DES_MIN_LOOP], l = the bases the innermost pair encloses) in the place of the concentration term.  The same in
+// every lane.
+__device__ __forceinline__ int des_hairpin(const int* tab, const int* loop, const DesSide& X, u32 u, u32 n, int salt, u32 lane) {
+    int hp = 0;
+    const int last = 2 * (int)n - 6;
+    for (int c = 4 + (int)lane; c <= last; c += DES_T) {
+        const int ilo = max(0, c - ((int)n - 1)), ihi = (c - 4) >> 1;
+        int run0 = -1;
+        for (int i = ilo; i <= ihi + 1; i++) {
+            const bool pair = i <= ihi && X.code[u + i] + X.code[u + c - i] == 3u;
+            if (pair) {
+                if (run0 < 0) run0 = i;
+            } else if (run0 >= 0) {
+                const int i1 = i - 1;
+                if (i1 > run0) hp = max(hp, des_tm(tab, X, u + run0, u + i1, salt, loop[c - 2 * i1 - 1 - DES_MIN_LOOP]));
+                run0 = -1;
+            }
+        }
+    }
+    return des_wave_max(hp);
+}
+
 __device__ __forceinline__ u64 des_key(u32 pen, u32 ls, u32 ln, u32 rs, u32 rn) {
     return ((u64)pen << 34) | ((u64)ls << 23) | ((u64)ln << 17) | ((u64)rs << 6) | rn;
 }
 
+// P: the kr_design_params and, for HP, behind them the 64 ints of a kr_hairpin_params; hp_out: HP only
+template <bool HP>
 __global__ __launch_bounds__(DES_T) void k_design(const uint8_t* __restrict__ templates, u32 nregions, DesignGeom g,
-                                                  const kr_design_params* __restrict__ P, kr_design_record* __restrict__ out) {
+                                                  const kr_design_params* __restrict__ P, kr_design_record* __restrict__ out,
+                                                  int2* __restrict__ hp_out) {
     extern __shared__ __align__(16) u32 des_lds[];
     const u32 region = blockIdx.x, lane = threadIdx.x;
     if (region >= nregions) return;
     unsigned char* const lds = (unsigned char*)des_lds;
     int* const tab = (int*)des_lds;
+    const int* const loop = tab + DES_TAB;
     uint8_t* codew[2];
     int* phw[2];
     int* psw[2];
@@ -151,6 +187,7 @@ __global__ __launch_bounds__(DES_T) void k_design(const uint8_t* __restrict__ te
 
     // ---- the table, the codes of both sides
     if (lane < 40) tab[lane] = ((const int*)P)[lane];
+    if (HP && lane < DES_MAX_LOOP - DES_MIN_LOOP + 1) tab[DES_TAB + lane] = ((const int*)(P + 1))[DES_MIN_LOOP + lane];
     const uint8_t* T = templates + (u64)region * g.W;
     for (u32 i = lane; i < g.L; i += DES_T) codew[0][i] = (uint8_t)des_code(T[i]);
     for (u32 i = lane; i < g.R; i += DES_T) {
@@ -213,7 +250,7 @@ __global__ __launch_bounds__(DES_T) void k_design(const uint8_t* __restrict__ te
     }
     __syncthreads();
 
-    // ---- 1b: the wave per survivor: self_any and self_end
+    // ---- 1b: the wave per survivor: (its hairpin figure,) self_any and self_end
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         const DesSide& X = S[q];
@@ -225,6 +262,10 @@ __global__ __launch_bounds__(DES_T) void k_design(const uint8_t* __restrict__ te
                 const u32 e2 = base + (u32)__ffsll((long long)mask) - 1;
                 mask &= mask - 1;
                 const u32 n = (u32)lo + e2 / X.len, u = e2 % X.len;
+                if (HP && des_hairpin(tab, loop, X, u, n, salt, lane) > max_sec) {
+                    if (lane == 0) X.pen[e2] = DES_DEAD;
+                    continue;
+                }
                 int any, end;
                 des_duplex(tab, X, u, n, X, u, n, salt, conc, lane, &any, &end);
                 if ((any > max_sec || end > max_sec) && lane == 0) X.pen[e2] = DES_DEAD;
@@ -296,5 +337,10 @@ __global__ __launch_bounds__(DES_T) void k_design(const uint8_t* __restrict__ te
         o[1] = w1;
         o[2] = found ? make_uint4(A.pen[(ln - (u32)lo) * A.len + ls], B.pen[(rn - (u32)lo) * B.len + ur], (u32)lsa, (u32)lse) : w0;
         o[3] = make_uint4((u32)rsa, (u32)rse, (u32)pa, (u32)pe);
+    }
+    if (HP) {
+        int2 hp = make_int2(0, 0);
+        if (found) hp = make_int2(des_hairpin(tab, loop, A, ls, ln, salt, lane), des_hairpin(tab, loop, B, ur, rn, salt, lane));
+        if (lane == 0) hp_out[region] = hp;
     }
 }

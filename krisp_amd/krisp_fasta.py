@@ -1563,7 +1563,7 @@ def design_templates(groups, ingroup_labels):
 
 
 def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(70, 150), primer_size=(25, 35), max_sec_tm=40,
-                   gc_clamp=1, max_end_gc=4, device=0):
+                   gc_clamp=1, max_end_gc=4, device=0, hairpins=False):
     """A primer pair for every region, on the device (kr_design_*): on the consensus of the region's ingroup
     Amplicons -- the template --primer3 designs on -- a left primer inside the left flank and a right primer inside the
     right flank, lengths within `primer_size`; nearest-neighbour Tm within `tm` (degrees Celsius), GC percent within `gc`,
@@ -1571,9 +1571,12 @@ def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(7
     duplex figures (the highest Tm of a run of Watson-Crick pairs in an ungapped antiparallel alignment: self_any, self_end,
     pair_any, pair_end) at most `max_sec_tm`; the product within `amp_size`; of the passing pairs the one of least
     penalty, ties to the smallest (left_start, left_len, right_start, right_len).  Every figure is an integer
-    (krisp_amd/thermo.py holds the model); no hairpins, no gapped or mismatched duplexes: this is not Primer3.
+    (krisp_amd/thermo.py holds the model); no gapped or mismatched duplexes: this is not Primer3.  hairpins=True holds
+    every primer to `max_sec_tm` for its hairpin figure too (the highest Tm of a stem of two or more pairs
+    around a loop of three or more bases) and returns it.
     `groups` as find_regions* returned them.  Returns a _native.DESIGN_RECORD array, one row per group (found = 0: no
-    pair).  ValueError for figures the pass does not take (thermo.refusal)."""
+    pair); with hairpins a DESIGN_RECORD_HP array, the same fields and left_hairpin, right_hairpin.  ValueError for figures
+    the pass does not take (thermo.refusal)."""
     from . import thermo
     opts = dict(tm=tuple(tm), gc=tuple(gc), amp_size=tuple(amp_size), primer_size=tuple(primer_size), max_sec_tm=max_sec_tm,
                 gc_clamp=gc_clamp, max_end_gc=max_end_gc)
@@ -1583,9 +1586,11 @@ def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(7
     rows, L, D, R = design_templates(groups, ingroup_labels)
     if len(rows) == 0:
         from . import _native
-        return np.empty(0, dtype=_native.DESIGN_RECORD)
+        return np.empty(0, dtype=_native.DESIGN_RECORD_HP if hairpins else _native.DESIGN_RECORD)
     with _engine(device) as eng:
         eng.design_table(thermo.params(**opts))
+        if hairpins:
+            eng.design_hairpins(thermo.hairpin_params())
         return eng.design(rows, L, D, R)
 
 
@@ -2101,9 +2106,13 @@ def build_parser():
     p.add_argument("--design-primers", action="store_true",
                    help="Design a primer pair for every region found on the GPU, with the options below (no third-party\n"
                         "package): an integer nearest-neighbour model, ungapped duplex figures in the place of Primer3's\n"
-                        "thermodynamic alignments, no hairpins. Regions without a pair are left out; --primer_size within\n"
+                        "thermodynamic alignments, hairpins with --hairpins. Regions without a pair are left out; --primer_size within\n"
                         "10 .. 60; not with --primer3, --out_locations, --out_near or --out_products (the designed pairs are\n"
                         "searched by --out_primer_products).")
+    p.add_argument("--hairpins", action="store_true",
+                   help="With --design-primers: hold every primer to --max_sec_tm for hairpins too (the highest melting\n"
+                        "temperature of a stem of two or more pairs around a loop of three or more bases, the project's own\n"
+                        "integer model) and append left_hairpin and right_hairpin to the CSV. (default: hairpins are not looked at)")
     p.add_argument("--tm", type=int, nargs=2, metavar="INT", default=[53, 68])
     p.add_argument("--gc", type=int, nargs=2, metavar="INT", default=[40, 70])
     p.add_argument("--amp_size", type=int, nargs=2, metavar="INT", default=[70, 150])
@@ -2169,6 +2178,10 @@ def main(argv=None):
         if why is not None:
             print("ERROR: " + why, file=sys.stderr)
             sys.exit(2)
+    if args.hairpins and not args.design_primers:
+        print("ERROR: --hairpins needs --design-primers (it is the designer's own check; Primer3 has PRIMER_MAX_HAIRPIN_TH)",
+              file=sys.stderr)
+        sys.exit(2)
     if args.out_locations is not None and args.primer3:
         print("ERROR: --out_locations cannot be combined with --primer3 (the regions Primer3 keeps are not located)",
               file=sys.stderr)
@@ -2266,7 +2279,7 @@ def main(argv=None):
         from . import primers
         if args.verbose:
             print("Designing a primer pair for every region ... ", file=sys.stderr)
-        records = design_primers(groups, ingroup, device=locate_device,
+        records = design_primers(groups, ingroup, device=locate_device, hairpins=args.hairpins,
                                  **{k: getattr(args, k) for k in ("tm", "gc", "amp_size", "primer_size", "max_sec_tm",
                                                                   "gc_clamp", "max_end_gc")})
         csv_text, align_text = primers.render_designed(groups, ingroup, records, dot=args.dot_alignment)

@@ -117,7 +117,14 @@ def render(groups, ingroup_labels, global_settings, dot=False):
 DESIGN_COLUMNS = ["product_size", "pair_penalty", "left_sequence", "right_sequence", "left_start", "left_length", "right_start",
                   "right_length", "left_tm", "right_tm", "left_gc_percent", "right_gc_percent", "left_self_any", "left_self_end",
                   "right_self_any", "right_self_end", "pair_compl_any", "pair_compl_end"]
+HAIRPIN_COLUMNS = ["left_hairpin", "right_hairpin"]       # --hairpins: behind DESIGN_COLUMNS
 _COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def _has_hairpins(rec):
+    """a record or an array of _native.DESIGN_RECORD_HP, or a mapping with its fields"""
+    names = rec.dtype.names or () if hasattr(rec, "dtype") else rec if hasattr(rec, "keys") else ()
+    return "left_hairpin" in names
 
 
 def design_template(group, ingroup):
@@ -130,8 +137,10 @@ def design_template(group, ingroup):
 
 def design_fields(template, rec):
     """one found record (a row of _native.DESIGN_RECORD, or a mapping with its fields) as text, column by column, plus the
-    keys `annotate` reads.  Temperatures in degrees Celsius and penalties with three decimals, formatted from the integers"""
+    keys `annotate` reads.  Temperatures in degrees Celsius and penalties with three decimals, formatted from the integers.
+    A record with the hairpin figures (DESIGN_RECORD_HP) gives HAIRPIN_COLUMNS too"""
     from . import thermo
+    hairpins = {c: thermo.celsius(int(rec[c])) for c in HAIRPIN_COLUMNS} if _has_hairpins(rec) else {}
     r = {k: int(rec[k]) for k in ("product_size", "pair_penalty", "left_start", "left_len", "right_start", "right_len", "left_tm",
                                   "right_tm", "left_gc", "right_gc", "left_penalty", "right_penalty", "left_self_any",
                                   "left_self_end", "right_self_any", "right_self_end", "pair_any", "pair_end")}
@@ -153,12 +162,13 @@ def design_fields(template, rec):
         "PRIMER_LEFT_0": (r["left_start"], r["left_len"]),
         "PRIMER_RIGHT_0": (r["right_start"] + r["right_len"] - 1, r["right_len"]),
         "PRIMER_LEFT_0_SEQUENCE": left, "PRIMER_RIGHT_0_SEQUENCE": right,
+        **hairpins,
     }
 
 
 def design_stats_text(f):
-    """the statistics tables under an alignment block of --design-primers"""
-    names = ["start", "length", "tm", "gc_percent", "self_any", "self_end", "penalty"]
+    """the statistics tables under an alignment block of --design-primers (with the hairpin figures: a Hairpin column)"""
+    names = ["start", "length", "tm", "gc_percent", "self_any", "self_end"] + (["hairpin"] if "left_hairpin" in f else []) + ["penalty"]
     head = ["Direction"] + [n.title().replace("_", " ") for n in names]
     pair = ["product_size", "pair_penalty", "pair_compl_any", "pair_compl_end"]
     return ("\nPrimer statistics:\n" + _table(head, [["Forward"] + [f["left_" + n] for n in names],
@@ -169,10 +179,12 @@ def design_stats_text(f):
 def render_designed(groups, ingroup_labels, records, dot=False):
     """-> (csv_text, alignment_text) of --design-primers: records[i] is group i's answer; groups without a pair are left
     out, as under --primer3.  A group whose consensus has no IUPAC letter (a column holding U) stops the renderer as it
-    stops amplicon.render: the groups of the blocks of PRINT_BLOCK already written stay, the rest is lost"""
+    stops amplicon.render: the groups of the blocks of PRINT_BLOCK already written stay, the rest is lost.  Records with the
+    hairpin figures (--hairpins: _native.DESIGN_RECORD_HP) add HAIRPIN_COLUMNS behind DESIGN_COLUMNS"""
     import sys
     ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
-    csv = [amplicon.CSV_HEADER + "," + ",".join(DESIGN_COLUMNS)]
+    columns = DESIGN_COLUMNS + (HAIRPIN_COLUMNS if _has_hairpins(records) else [])
+    csv = [amplicon.CSV_HEADER + "," + ",".join(columns)]
     blocks = []
     index = []                                  # the group each written row came from
     for gi, (g, rec) in enumerate(zip(groups, records)):
@@ -194,6 +206,6 @@ def render_designed(groups, ingroup_labels, records, dot=False):
         lines = annotate(lines, f, dot)
         lines.append(design_stats_text(f))
         blocks.append("\n".join(lines) + "\n\n")
-        csv.append(row + "," + ",".join(f[c] for c in DESIGN_COLUMNS))
+        csv.append(row + "," + ",".join(f[c] for c in columns))
         index.append(gi)
     return "\n".join(csv) + "\n", "".join(blocks)

@@ -3,7 +3,8 @@ integers in kr_design_table, the brute-force reference of the tests imports the 
 
 Enthalpy in cal/mol, entropy in 0.001 cal/(mol K), temperatures in mK.  Nearest-neighbour steps: SantaLucia 1998 unified,
 read 5'->3' on the oligo.  Tm_mK = (dH * 10^6) // dS_total, both negative, int64, floor division.  This is NOT Primer3's
-model: no `thal` alignment, no hairpins, no gapped or mismatched duplexes.
+model: no `thal` alignment, no gapped or mismatched duplexes; the hairpin figure of --hairpins (LOOP_DS below)
+is a model of this project's own too.
 """
 import ctypes
 import math
@@ -28,6 +29,28 @@ SALT_DS = round(368 * math.log(0.05))            # per step: 50 mM monovalent
 CONC_DS = round(1000 * 1.987 * math.log(50e-9 / 4))      # 50 nM, two different strands
 CONC_SELF_DS = round(1000 * 1.987 * math.log(50e-9))     # ... a self-complementary one
 
+
+# --hairpins: a hairpin loop's free energy at 37 degrees C in cal/mol by the number of bases the innermost
+# pair encloses.  THESE NUMBERS ARE THE DEFINITION: they follow SantaLucia & Hicks 2004 as remembered and were not checked
+# against the paper.  Between two listed lengths: linear, in integers, floor; above 30: 40 per base.  The loop's enthalpy is
+# 0, so its entropy is -dG / 310.15 K, here in 0.001 cal/(mol K), rounded.
+LOOP_DG37 = {3: 3500, 4: 3500, 5: 3300, 6: 4000, 7: 4200, 8: 4300, 9: 4500, 10: 4600, 12: 5000, 14: 5100, 16: 5300, 18: 5500,
+             20: 5700, 25: 6100, 30: 6300}
+HAIRPIN_MIN_LOOP = 3
+HAIRPIN_MAX_LOOP = 56                            # a primer of 60 bases (MAX_SIZE), two pairs
+
+
+def loop_dg37(l):
+    if l >= 30:
+        return LOOP_DG37[30] + 40 * (l - 30)
+    a = max(k for k in LOOP_DG37 if k <= l)
+    b = min(k for k in LOOP_DG37 if k >= l)
+    return LOOP_DG37[a] if a == b else LOOP_DG37[a] + (LOOP_DG37[b] - LOOP_DG37[a]) * (l - a) // (b - a)
+
+
+# [loop length] of kr_hairpin_params: 64 entries, 3 .. 56 are read
+LOOP_DS = [-((loop_dg37(l) * 100000 + 15507) // 31015) if HAIRPIN_MIN_LOOP <= l <= HAIRPIN_MAX_LOOP else 0 for l in range(64)]
+
 ZERO_C_MK = 273150
 SIZE_WEIGHT = 500                                # penalty per half base off the middle length = 1 per base, as 1000 per K
 MIN_SIZE, MAX_SIZE = 10, 60                      # --primer_size the pass takes
@@ -47,6 +70,18 @@ class Params(ctypes.Structure):
                 + [(n, ctypes.c_int32) for n in ("sym_ds", "salt_ds", "conc_ds", "conc_self_ds", "size_lo", "size_hi", "tm_lo",
                                                  "tm_hi", "tm_opt", "gc_lo", "gc_hi", "amp_lo", "amp_hi", "max_sec", "gc_clamp",
                                                  "max_end_gc")])
+
+
+class HairpinParams(ctypes.Structure):
+    """kr_hairpin_params of include/krisp_hip.h"""
+    _fields_ = [("loop_ds", ctypes.c_int32 * 64)]
+
+
+def hairpin_params():
+    """-> HairpinParams: LOOP_DS"""
+    h = HairpinParams()
+    h.loop_ds[:] = LOOP_DS
+    return h
 
 
 def options(tm=(53, 68), gc=(40, 70), amp_size=(70, 150), primer_size=(25, 35), max_sec_tm=40, gc_clamp=1, max_end_gc=4):

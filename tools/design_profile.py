@@ -1,6 +1,6 @@
 """Time the primer design pass (krisp_fasta --design-primers: KF.design_primers, kr_design_*).
 
-  python tools/design_profile.py [--length 50000000] [--kernel] [--files] [--reference 40] [--out FILE.json]
+  python tools/design_profile.py [--length 50000000] [--kernel] [--hairpins] [--files] [--reference 40] [--out FILE.json]
 
 Four synthetic genomes (krisp_amd/synth.py, 8 records each, 2 ingroup / 2 outgroup, the files of tools/products_profile.py)
 at 30/40/30 with the command line's default primer options except --primer_size 18 24 and --amp_size 70 100 (the defaults,
@@ -9,6 +9,8 @@ at 30/40/30 with the command line's default primer options except --primer_size 
 calls, the host clock around a call that ends in a synchronise, and the same over the templates repeated to a million
 regions.  Run it under `rocprofv3 --kernel-trace --stats -- python tools/design_profile.py --kernel` for k_design's own
 time.
+--hairpins: with --kernel, the same calls again with the hairpin check on (kr_design_hairpins: k_design<true>), after the
+plain ones, so that a kernel trace holds k_design<false> and k_design<true> beside each other.
 --files: the command line end to end without --design-primers and with it, each in five fresh processes (a process per
 run, each under its own time limit; a failing run ends the tool): medians.
 --reference N: the brute-force reference of the tests (tests/design_reference.py) over the first N regions on the CPU:
@@ -64,7 +66,7 @@ def _timed(call):
     return min(times), out
 
 
-def kernel_part(paths, nref):
+def kernel_part(paths, nref, hairpins=False):
     groups, _ = KF.find_regions(paths[:2], paths[2:], 30, 30, 100)
     ingroup = [KF.simplename(f) for f in paths[:2]]
     t0 = time.time()
@@ -81,6 +83,13 @@ def kernel_part(paths, nref):
         res["design_million_s"], recs_m = _timed(lambda: eng.design(many, L, D, R))
         res["million_regions_per_s"] = len(many) / res["design_million_s"]
         assert recs_m[:len(rows)].tobytes() == recs.tobytes()
+        if hairpins:
+            eng.design_hairpins(thermo.hairpin_params())
+            res["design_hairpins_s"], recs_h = _timed(lambda: eng.design(rows, L, D, R))
+            res["with_a_pair_hairpins"] = int(recs_h["found"].sum())
+            res["winners_changed_by_hairpins"] = int(np.any([recs_h[n] != recs[n] for n in recs.dtype.names], axis=0).sum())
+            res["design_hairpins_million_s"], _ = _timed(lambda: eng.design(many, L, D, R))
+            eng.design_hairpins(None)
     if nref:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from design_reference import design as ref_design
@@ -114,6 +123,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--length", type=int, default=50_000_000)
     ap.add_argument("--kernel", action="store_true", help="kr_design_run over the regions' templates")
+    ap.add_argument("--hairpins", action="store_true", help="with --kernel: the timed calls again with the hairpin check on")
     ap.add_argument("--files", action="store_true", help="the end-to-end part from .fasta.gz files")
     ap.add_argument("--reference", type=int, default=0, metavar="N", help="with --kernel: the CPU reference over N regions")
     ap.add_argument("--out", type=str, default=None)
@@ -122,7 +132,7 @@ def main():
     with tempfile.TemporaryDirectory(prefix="krisp_design_") as td:
         paths = write_genomes(args.length, td)
         if args.kernel:
-            res.update(kernel_part(paths, args.reference))
+            res.update(kernel_part(paths, args.reference, args.hairpins))
         if args.files:
             res.update(files_part(paths, td))
     line = json.dumps(res)
