@@ -445,6 +445,41 @@ int kr_design_hairpins(kr_ctx*, const kr_hairpin_params* params);
  * KR_ERR_STATE when that run had the check off.  kr_design_record does not change with the check. */
 int64_t kr_design_fetch_hairpins(kr_ctx*, int32_t* out, size_t cap);
 
+/* ---- a CRISPR guide per region (krisp_fasta --out_guides) ---------------------------------------------------------------
+ * Replaces no seam of the reference, which picks no guide.  For every region the protospacer window of guide_size columns
+ * of the region's template that lies next to the enzyme's PAM / PFS, passes the GC and poly-X filters and differs most
+ * from the region's outgroup rows (DESIGN §18 has the definition, every figure an integer).  It runs on the device in
+ * csrc/k_guides.inc, a wavefront per region, in any context (no genome, no parameters of another pass are needed).
+ *
+ * kr_guides_table: the options.  pam5 / pam3 hold one 4-bit IUPAC mask per motif letter, read 5'->3' on the guide's
+ * strand (A = 1, C = 2, G = 4, T = 8; N = 15), pam5_len / pam3_len letters of them count (0: no motif on that side);
+ * gc_lo / gc_hi in percent.  KR_ERR_PARAM unless 12 <= guide_size <= 40, both lengths lie in 0 .. 8 and every mask that
+ * counts in 1 .. 15. */
+typedef struct {
+    int32_t guide_size, pam5_len, pam3_len;
+    uint8_t pam5[8], pam3[8];
+    int32_t gc_lo, gc_hi, min_mismatches;
+} kr_guide_params;
+int kr_guides_table(kr_ctx*, const kr_guide_params* params);
+/* one region's answer, 32 bytes: found = 1 and the guide, or all zero but `candidates`.  strand 0: the protospacer reads
+ * template[start, start + guide_size), 1: its reverse complement; min / sum_mismatches = the least and the total number of
+ * protospacer columns at which an outgroup row holds another of A C G T than the template (guide_size and 0 without
+ * outgroup rows); gc = the number of G and C; candidates = the windows and strands that passed every filter */
+typedef struct {
+    uint32_t found, strand, start, min_mismatches, sum_mismatches, gc, candidates, pad;
+} kr_guide_record;
+/* rows: byte rows of K letters each (upper case, U written as T); the rows row_off[r] .. row_off[r + 1] - 1 are region r's,
+ * the first of them its template and the others its outgroup rows (any number, none included); bounds[2 r], bounds[2 r + 1]
+ * = the columns [lo, hi) the guide with its PAM must lie in; L, D = the template's left flank and diagnostic stretch (the
+ * tie rule prefers the window centred on column L + D / 2).  In batches so that any count fits.  Returns the number of
+ * regions with a guide.  KR_ERR_STATE before kr_guides_table; KR_ERR_PARAM for K < guide_size, K > 2047, L + D > K, a null
+ * pointer, lo > hi, hi > K, row_off[0] != 0, a region without a row or with more than 2^26 of them; KR_ERR_CAPACITY when
+ * one region's tables exceed the LDS of a workgroup. */
+int64_t kr_guides_run(kr_ctx*, const uint8_t* rows, const uint64_t* row_off, const uint32_t* bounds, uint64_t nregions, int K,
+                      int L, int D);
+/* the records of the latest run, one per region in the order given (KR_ERR_STATE before a run) */
+int64_t kr_guides_fetch(kr_ctx*, kr_guide_record* out, size_t cap);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

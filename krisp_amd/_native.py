@@ -31,6 +31,8 @@ DESIGN_RECORD = np.dtype([("found", "<u4"), ("product_size", "<u4"), ("pair_pena
                           ("right_self_end", "<i4"), ("pair_any", "<i4"), ("pair_end", "<i4")])             # kr_design_record
 # ... and, behind it, the pair's two figures of kr_design_fetch_hairpins: what Engine.design returns with the check on
 DESIGN_RECORD_HP = np.dtype(DESIGN_RECORD.descr + [("left_hairpin", "<i4"), ("right_hairpin", "<i4")])
+GUIDE_RECORD = np.dtype([("found", "<u4"), ("strand", "<u4"), ("start", "<u4"), ("min_mismatches", "<u4"),
+                         ("sum_mismatches", "<u4"), ("gc", "<u4"), ("candidates", "<u4"), ("pad", "<u4")])    # kr_guide_record
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -123,6 +125,9 @@ SYMBOLS = [
     ("kr_design_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_design_hairpins", _c.c_int, [_P, _P]),
     ("kr_design_fetch_hairpins", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_guides_table", _c.c_int, [_P, _P]),
+    ("kr_guides_run", _c.c_int64, [_P, _P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
+    ("kr_guides_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -168,6 +173,12 @@ SYMBOLS = [
     ("kr_debug_budget_left", _c.c_int64, [_P]),
     ("kr_debug_budget_set", _c.c_int, [_P, _c.c_int64]),
 ]
+
+
+class GuideParams(ctypes.Structure):
+    """kr_guide_params: pam5 / pam3 hold a 4-bit IUPAC mask per motif letter (A = 1, C = 2, G = 4, T = 8)"""
+    _fields_ = [("guide_size", _c.c_int32), ("pam5_len", _c.c_int32), ("pam3_len", _c.c_int32), ("pam5", _c.c_uint8 * 8),
+                ("pam3", _c.c_uint8 * 8), ("gc_lo", _c.c_int32), ("gc_hi", _c.c_int32), ("min_mismatches", _c.c_int32)]
 
 
 class KrispHipError(RuntimeError):
@@ -798,6 +809,35 @@ class Engine:
             both[name] = out[name][:len(t)]
         both["left_hairpin"], both["right_hairpin"] = hp[:len(t), 0], hp[:len(t), 1]
         return both
+
+    def guides_table(self, guide_size, pam5=(), pam3=(), gc=(30, 70), min_mismatches=1):
+        """the options of guides(): pam5 / pam3 = the motifs as sequences of 4-bit IUPAC masks, read 5'->3' on the guide's
+        strand (kr_guides_table)"""
+        p = GuideParams(guide_size=guide_size, pam5_len=len(pam5), pam3_len=len(pam3), gc_lo=gc[0], gc_hi=gc[1],
+                        min_mismatches=min_mismatches)
+        for j, m in enumerate(pam5[:8]):
+            p.pam5[j] = m
+        for j, m in enumerate(pam3[:8]):
+            p.pam3[j] = m
+        self._check(self.lib.kr_guides_table(self.ctx, ctypes.byref(p)), "kr_guides_table")
+
+    def guides(self, rows, row_off, bounds, L, D):
+        """rows: uint8 [n, K] (upper case, T for U), row_off: [regions + 1] counted in rows -- a region's first row is its
+        template, the others its outgroup rows --, bounds: [regions, 2] columns [lo, hi) -> GUIDE_RECORD array, one per
+        region (kr_guides_run, kr_guides_fetch)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        if rows.ndim != 2:
+            raise ValueError("guides: rows is a matrix, a row of K letters each")
+        off = np.ascontiguousarray(row_off, dtype=np.uint64).ravel()
+        bnd = np.ascontiguousarray(bounds, dtype=np.uint32).reshape(-1, 2)
+        n = len(off) - 1
+        if n < 0 or len(bnd) != n or (n and int(off[-1]) > len(rows)):
+            raise ValueError(f"guides: {len(off)} row offsets up to {int(off[-1]) if len(off) else 0}, {len(bnd)} bounds, {len(rows)} rows")
+        self._check(self.lib.kr_guides_run(self.ctx, _ptr(rows) if rows.size else None, _ptr(off), _ptr(bnd) if n else None, n,
+                                           rows.shape[1], L, D), "kr_guides_run")
+        out = np.empty(max(n, 1), dtype=GUIDE_RECORD)
+        self._check(self.lib.kr_guides_fetch(self.ctx, _ptr(out), n), "kr_guides_fetch")
+        return out[:n]
 
     # ---- timing
     def sync(self):

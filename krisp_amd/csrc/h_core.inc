@@ -241,6 +241,14 @@ struct kr_ctx {
         std::vector<kr_design_record> out;      // the records of the latest run, all batches
         std::vector<int32_t> hp_out;            // ... and, with the hairpin check, its two figures a region
     } design;
+    // the guide pass (kr_guides_*: h_guides.inc): no genome, no geometry of another pass
+    struct Guides {
+        bool on = false;
+        kr_guide_params params{};
+        int64_t nrec = -1;
+        DevBuf rows, off, bnd, rec;
+        std::vector<kr_guide_record> out;       // the records of the latest run, all batches
+    } guides;
 };
 
 static int fail(kr_ctx* c, int code, const char* fmt, ...) {
@@ -548,6 +556,9 @@ void kr_destroy(kr_ctx* c) {
         auto& ds = c->design;
         DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec, &ds.hprec};
         for (DevBuf* b : db) release(c, *b);
+        auto& gu = c->guides;
+        DevBuf* gb[] = {&gu.rows, &gu.off, &gu.bnd, &gu.rec};
+        for (DevBuf* b : gb) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);
     for (auto e : c->pool) (void)hipEventDestroy(e);

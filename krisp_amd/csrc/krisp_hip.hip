@@ -50,6 +50,7 @@
 #include "k_products.inc"    // the product pass: sites of the flanks within M substitutions, joined into PCR products
 #include "k_primers.inc"     // the primer-product pass: sites of primer texts of mixed lengths, joined into PCR products
 #include "k_design.inc"      // the primer design pass: a wavefront per region, integer thermodynamics, the best pair
+#include "k_guides.inc"      // the guide pass: a wavefront per region, the window next to a PAM that differs most from the outgroup rows
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
 #include "h_intersect.inc"   // kr_intersect, candidate lists, kr_collect
 #include "h_wide.inc"        // kr_wide_run
@@ -59,6 +60,7 @@
 #include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome
 #include "h_primers.inc"     // kr_primers_*: in-silico PCR of designed primer pairs against a genome
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options
+#include "h_guides.inc"      // kr_guides_*: a CRISPR guide per region from its template, its outgroup rows and the guide options
 #include "h_pgzip.inc"       // one gzip member inflated on several threads (host only)
 #include "h_ingest.inc"      // file -> inflate -> parse -> pinned upload buffer (host side)
 #include "h_gunzip.inc"      // kr_genome_upload_gzip: the host side of k_gunzip.inc

@@ -1563,7 +1563,7 @@ def design_templates(groups, ingroup_labels):
 
 
 def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(70, 150), primer_size=(25, 35), max_sec_tm=40,
-                   gc_clamp=1, max_end_gc=4, device=0, hairpins=False):
+                   gc_clamp=1, max_end_gc=4, device=0, hairpins=False, templates=None):
     """A primer pair for every region, on the device (kr_design_*): on the consensus of the region's ingroup
     Amplicons -- the template --primer3 designs on -- a left primer inside the left flank and a right primer inside the
     right flank, lengths within `primer_size`; nearest-neighbour Tm within `tm` (degrees Celsius), GC percent within `gc`,
@@ -1576,14 +1576,15 @@ def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(7
     around a loop of three or more bases) and returns it.
     `groups` as find_regions* returned them.  Returns a _native.DESIGN_RECORD array, one row per group (found = 0: no
     pair); with hairpins a DESIGN_RECORD_HP array, the same fields and left_hairpin, right_hairpin.  ValueError for figures
-    the pass does not take (thermo.refusal)."""
+    the pass does not take (thermo.refusal).  templates = design_templates(groups, ingroup_labels) where the caller has them
+    already."""
     from . import thermo
     opts = dict(tm=tuple(tm), gc=tuple(gc), amp_size=tuple(amp_size), primer_size=tuple(primer_size), max_sec_tm=max_sec_tm,
                 gc_clamp=gc_clamp, max_end_gc=max_end_gc)
     why = thermo.refusal(**opts)
     if why is not None:
         raise ValueError(why)
-    rows, L, D, R = design_templates(groups, ingroup_labels)
+    rows, L, D, R = design_templates(groups, ingroup_labels) if templates is None else templates
     if len(rows) == 0:
         from . import _native
         return np.empty(0, dtype=_native.DESIGN_RECORD_HP if hairpins else _native.DESIGN_RECORD)
@@ -1691,6 +1692,129 @@ def primer_products(groups, records, ingroup_labels, ingroup_files, outgroup_fil
         # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start))
         parts.append((fi, part, part["region"]))
     return _sorted_parts(parts, PRODUCT)
+
+
+# ----------------------------------------------------------------------------
+# a CRISPR guide per region, picked on the device (--out_guides)
+# ----------------------------------------------------------------------------
+GUIDE_HEADER = "region\tstrand\tstart\tend\tpam5\tpam3\tprotospacer\tgc_percent\tmin_mismatches\tsum_mismatches\tcandidates"
+GUIDE_MIN_SIZE, GUIDE_MAX_SIZE, GUIDE_MAX_MOTIF = 12, 40, 8
+# the IUPAC code as 4-bit sets: A = 1, C = 2, G = 4, T = 8
+IUPAC_MASK = {"A": 1, "C": 2, "G": 4, "T": 8, "U": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11,
+              "V": 7, "N": 15}
+_GUIDE_COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def motif_masks(motif):
+    """a PAM / PFS motif in IUPAC letters (either case, U as T) -> its 4-bit masks, one per letter; ValueError for a
+    letter outside the code"""
+    out = []
+    for ch in motif.upper():
+        if ch not in IUPAC_MASK:
+            raise ValueError(f"{ch!r} in the motif {motif!r} is no letter of the IUPAC code")
+        out.append(IUPAC_MASK[ch])
+    return out
+
+
+def guides_refusal(amplicon_len, guide_size, pam5, pam3, gc, min_mismatches):
+    """why the guide pass does not take these figures (one line), or None"""
+    if guide_size < GUIDE_MIN_SIZE or guide_size > GUIDE_MAX_SIZE:
+        return f"--guide-size must lie between {GUIDE_MIN_SIZE} and {GUIDE_MAX_SIZE} (got {guide_size})"
+    if amplicon_len is not None and guide_size > amplicon_len:
+        return f"--guide-size must not exceed the amplicon length {amplicon_len} (got {guide_size})"
+    for opt, motif in (("--pam5", pam5), ("--pam3", pam3)):
+        if len(motif) > GUIDE_MAX_MOTIF:
+            return f"{opt} takes at most {GUIDE_MAX_MOTIF} letters (got {motif!r})"
+        try:
+            motif_masks(motif)
+        except ValueError as e:
+            return f"{opt}: {e}"
+    if gc[0] > gc[1]:
+        return f"--guide-gc: the upper bound lies below the lower ({gc[0]} .. {gc[1]})"
+    if min_mismatches < 0 or min_mismatches > guide_size:
+        return f"--guide-min-mismatches must lie between 0 and --guide-size, {guide_size} (got {min_mismatches})"
+    return None
+
+
+def guide_rows(groups, ingroup_labels, templates=None):
+    """The rows of the guide pass: per group its template (primers.design_template), then one row per
+    Amplicon of the group the template leaves out -- the outgroup rows, left + diag + right, upper case, U written as T.
+    No ingroup_labels (a run without --outgroup): no outgroup rows.  templates = design_templates(groups, ingroup_labels)
+    where the caller has them already.  -> (uint8 [rows, L + D + R], uint64 [groups + 1] row offsets, L, D, R)"""
+    trows, L, D, R = design_templates(groups, ingroup_labels) if templates is None else templates
+    ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
+    k = L + D + R
+    parts, off = [], [0]
+    for gi, g in enumerate(groups):
+        texts = []
+        if ingroup is not None and len(g) > 1:
+            texts = [(a.left + a.diag + a.right).upper().replace("U", "T") for a in g if not set(a.labels) <= ingroup]
+        if any(len(t) != k for t in texts):
+            raise ValueError("guide_rows: groups of more than one geometry")
+        parts.append(bytes(trows[gi]))
+        parts.extend(t.encode("ascii") for t in texts)
+        off.append(off[-1] + 1 + len(texts))
+    if len(off) - 1 != len(trows):
+        raise ValueError(f"guide_rows: {len(trows)} templates for {len(off) - 1} groups")
+    rows = np.frombuffer(b"".join(parts), dtype=np.uint8).reshape(off[-1], k) if parts else np.empty((0, max(k, 1)), dtype=np.uint8)
+    return rows, np.array(off, dtype=np.uint64), L, D, R
+
+
+def design_guides(groups, ingroup_labels, guide_size=28, pam5="", pam3="", gc=(30, 70), min_mismatches=1, bounds=None, device=0,
+                  templates=None):
+    """A CRISPR guide for every region, on the device (kr_guides_*): the window of `guide_size` columns of the
+    region's template -- on either strand -- whose 5' neighbours match the motif `pam5` and whose 3' neighbours match `pam3`
+    (IUPAC letters, read 5'->3' on the guide's strand; "" = none), that holds only bases, has a GC percent within `gc` and
+    no run of five equal bases, and that differs from every outgroup row of the region (guide_rows) in at least
+    `min_mismatches` columns; of those the one whose least number of differences to an outgroup row is greatest, then
+    whose sum over the outgroup rows is greatest, then the best centred on the diagnostic stretch, '+' before '-', the
+    leftmost.  bounds: [groups, 2] columns [lo, hi) that window and motifs must lie in (default: the whole template).
+    Every figure is an integer: no seed weights, no folding of the guide, no gapped matches, no off-target search.
+    Returns a _native.GUIDE_RECORD array, one row per group (found = 0: no guide).  ValueError for figures the pass does
+    not take (guides_refusal)."""
+    from . import _native
+    why = guides_refusal(None, guide_size, pam5, pam3, tuple(gc), min_mismatches)
+    if why is not None:
+        raise ValueError(why)
+    rows, off, L, D, R = guide_rows(groups, ingroup_labels, templates)
+    n = len(off) - 1
+    if n == 0:
+        return np.empty(0, dtype=_native.GUIDE_RECORD)
+    k = L + D + R
+    if guide_size > k:
+        raise ValueError(f"--guide-size must not exceed the amplicon length {k} (got {guide_size})")
+    if bounds is None:
+        bounds = np.tile(np.array([0, k], dtype=np.uint32), (n, 1))
+    with _engine(device) as eng:
+        eng.guides_table(guide_size, motif_masks(pam5), motif_masks(pam3), tuple(gc), min_mismatches)
+        return eng.guides(rows, off, bounds, L, D)
+
+
+def _guide_rc(text):
+    return text[::-1].translate(_GUIDE_COMPLEMENT)
+
+
+def write_guides(path, templates, records, guide_size, pam5_len=0, pam3_len=0, regions=None):
+    """the TSV of --out_guides: GUIDE_HEADER, then a line per region with a guide.  templates: the regions' template rows
+    (design_templates), records: theirs (design_guides, or any array with GUIDE_RECORD's fields), regions: the number each
+    region is listed under (default: its index).  start / end = the window's template columns, 0-based and half-open;
+    pam5, pam3 and protospacer as read 5'->3' on the guide's strand"""
+    from . import thermo
+    g, a, b = guide_size, pam5_len, pam3_len
+    with open(path, "w") as f:
+        f.write(GUIDE_HEADER + "\n")
+        for i, (row, r) in enumerate(zip(templates, records)):
+            if not int(r["found"]):
+                continue
+            t = bytes(row).decode("ascii")
+            p = int(r["start"])
+            if int(r["strand"]) == 0:
+                strand, proto, m5, m3 = "+", t[p:p + g], t[p - a:p], t[p + g:p + g + b]
+            else:
+                strand, proto, m5, m3 = "-", _guide_rc(t[p:p + g]), _guide_rc(t[p + g:p + g + a]), _guide_rc(t[p - b:p])
+            region = i if regions is None else int(regions[i])
+            f.write(f"{region}\t{strand}\t{p}\t{p + g}\t{m5}\t{m3}\t{proto}\t{thermo.gc_percent(int(r['gc']), g)}\t"
+                    f"{int(r['min_mismatches'])}\t{int(r['sum_mismatches'])}\t{int(r['candidates'])}\n")
 
 
 # ----------------------------------------------------------------------------
@@ -2100,6 +2224,25 @@ def build_parser():
     p.add_argument("--max-product", type=int, default=None, metavar="INT",
                    help="longest product of --out_products / --out_primer_products in bases, at least the two flanks together /\n"
                         "the upper bound of --amp_size (default: 1000)")
+    p.add_argument("--out_guides", type=str, metavar="PATH",
+                   help="Also write a CRISPR guide for every region that can carry one, as a tab-separated file: region, strand,\n"
+                        "start, end (template columns, 0-based, half-open), pam5, pam3, protospacer (as read 5'->3' on the guide's\n"
+                        "strand), gc_percent, min_mismatches, sum_mismatches, candidates.  The guide is the window of --guide-size\n"
+                        "columns of the ingroup's consensus, next to --pam5 / --pam3, within --guide-gc and without a run of five\n"
+                        "equal bases, that differs most from the region's outgroup sequences; with --design-primers it lies\n"
+                        "between the designed primers and region = the pair's data row in the CSV.  No extra pass over the\n"
+                        "inputs; not with --primer3.  (default: no guides)")
+    p.add_argument("--guide-size", type=int, default=None, metavar="INT",
+                   help="protospacer length of --out_guides: 12 .. 40, at most the amplicon length (default: 28)")
+    p.add_argument("--pam5", type=str, default=None, metavar="MOTIF",
+                   help="motif 5' of the protospacer in IUPAC letters, at most 8, e.g. TTTV for Cas12a (default: none)")
+    p.add_argument("--pam3", type=str, default=None, metavar="MOTIF",
+                   help="motif 3' of the protospacer in IUPAC letters, at most 8, e.g. H for LwaCas13a's PFS (default: none)")
+    p.add_argument("--guide-gc", type=int, nargs=2, default=None, metavar="INT",
+                   help="GC percent of the protospacer, lower and upper bound (default: 30 70)")
+    p.add_argument("--guide-min-mismatches", type=int, default=None, metavar="INT",
+                   help="columns in which the protospacer differs from EVERY outgroup sequence of its region at least:\n"
+                        "0 .. --guide-size (default: 1)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -2227,6 +2370,24 @@ def main(argv=None):
         if why is not None:
             print("ERROR: " + why, file=sys.stderr)
             sys.exit(2)
+    for opt, val in (("--guide-size", args.guide_size), ("--pam5", args.pam5), ("--pam3", args.pam3), ("--guide-gc", args.guide_gc),
+                     ("--guide-min-mismatches", args.guide_min_mismatches)):
+        if val is not None and args.out_guides is None:
+            print(f"ERROR: {opt} needs --out_guides", file=sys.stderr)
+            sys.exit(2)
+    if args.out_guides is not None:
+        if args.guide_size is None:
+            args.guide_size = 28
+        if args.guide_gc is None:
+            args.guide_gc = [30, 70]
+        if args.guide_min_mismatches is None:
+            args.guide_min_mismatches = 1
+        args.pam5, args.pam3 = args.pam5 or "", args.pam3 or ""
+        why = "--out_guides cannot be combined with --primer3 (the regions Primer3 keeps get no guide)" if args.primer3 else \
+            guides_refusal(args.amplicon, args.guide_size, args.pam5, args.pam3, args.guide_gc, args.guide_min_mismatches)
+        if why is not None:
+            print("ERROR: " + why, file=sys.stderr)
+            sys.exit(2)
     if args.primer3:
         from . import primers
         if not primers.available():
@@ -2279,7 +2440,9 @@ def main(argv=None):
         from . import primers
         if args.verbose:
             print("Designing a primer pair for every region ... ", file=sys.stderr)
-        records = design_primers(groups, ingroup, device=locate_device, hairpins=args.hairpins,
+        # (the templates are built once: the guide pass takes them too)
+        templates = design_templates(groups, ingroup) if args.out_guides is not None else None
+        records = design_primers(groups, ingroup, device=locate_device, hairpins=args.hairpins, templates=templates,
                                  **{k: getattr(args, k) for k in ("tm", "gc", "amp_size", "primer_size", "max_sec_tm",
                                                                   "gc_clamp", "max_end_gc")})
         csv_text, align_text = primers.render_designed(groups, ingroup, records, dot=args.dot_alignment)
@@ -2325,6 +2488,23 @@ def main(argv=None):
                        primer_products(groups, records, ingroup, args.files, args.outgroup, args.conserved_left,
                                        args.conserved_right, args.amplicon, mismatches=args.primer_mismatches,
                                        max_product=args.max_product, omit_soft=args.omit_soft, device=locate_device))
+    if args.out_guides is not None:
+        # (on one device, written by rank 0; for every group -- with --design-primers every group with a pair --, also
+        # those a stopped renderer left out of the CSV)
+        if args.verbose:
+            print("Picking a guide for every region ... ", file=sys.stderr)
+        bounds = regions = None
+        if args.design_primers:
+            found = records["found"] != 0
+            lo = records["left_start"].astype(np.int64) + records["left_len"]
+            # (a region without a pair gets the empty bounds [0, 0): it takes no part)
+            bounds = np.where(found[:, None], np.stack([lo, records["right_start"].astype(np.int64)], axis=1), 0).astype(np.uint32)
+            regions = np.cumsum(found) - 1
+        else:
+            templates = design_templates(groups, ingroup)
+        guides = design_guides(groups, ingroup, args.guide_size, args.pam5, args.pam3, tuple(args.guide_gc),
+                               args.guide_min_mismatches, bounds=bounds, device=locate_device, templates=templates)
+        write_guides(args.out_guides, templates[0], guides, args.guide_size, len(args.pam5), len(args.pam3), regions=regions)
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
