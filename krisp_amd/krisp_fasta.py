@@ -1818,6 +1818,52 @@ def write_guides(path, templates, records, guide_size, pam5_len=0, pam3_len=0, r
 
 
 # ----------------------------------------------------------------------------
+# the picked guides searched in every genome: the table's texts and the result file; the pass itself is not built
+# ----------------------------------------------------------------------------
+GUIDE_HIT_HEADER = ("region\tfile\trecord\trecord_index\tstart\tend\tstrand\tmismatches\tmismatch_columns\tpam5_match\t"
+                    "pam3_match\tsequence")
+GUIDE_HIT = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"),
+                      ("end", "<i8"), ("strand", "U1"), ("mismatches", "<u4"), ("mismatch_columns", "O"), ("pam5_match", "<u4"),
+                      ("pam3_match", "<u4"), ("sequence", "O")])
+
+
+def guide_texts(templates, records, guide_size, regions=None):
+    """The table of a guide-hit pass from the regions' template rows (design_templates) and design_guides' records: the
+    regions with found = 0 take no part; a region's text is its protospacer as read 5'->3' on the guide's strand
+    (template[start, start + guide_size), its reverse complement for strand 1); equal texts are listed once, ordered by
+    their bytes.  regions: the number each region is listed under in the --out_guides file (default: its index).
+    -> (the distinct texts as bytes, the regions of text t as a list of lists, ascending)"""
+    g = guide_size
+    by_text = {}
+    for i, (row, r) in enumerate(zip(templates, records)):
+        if not int(r["found"]):
+            continue
+        p = int(r["start"])
+        t = bytes(row[p:p + g]).decode("ascii")
+        if int(r["strand"]):
+            t = _guide_rc(t)
+        by_text.setdefault(t.encode("ascii"), []).append(i if regions is None else int(regions[i]))
+    texts = sorted(by_text)
+    return texts, [sorted(by_text[t]) for t in texts]
+
+
+def _mask_columns(mask):
+    """a column mask -> the 1-based columns that differ, ascending and comma-separated; '-' for none"""
+    return ",".join(str(c + 1) for c in range(64) if (mask >> c) & 1) or "-"
+
+
+def write_guide_hits(path, rows):
+    """the TSV of the guide hits: GUIDE_HIT_HEADER, then a line per row"""
+    with open(path, "w") as f:
+        f.write(GUIDE_HIT_HEADER + "\n")
+        f.writelines(f"{r}\t{fn}\t{rec}\t{ri}\t{s}\t{e}\t{st}\t{mm}\t{cols}\t{p5}\t{p3}\t{seq}\n"
+                     for r, fn, rec, ri, s, e, st, mm, cols, p5, p3, seq in zip(
+                         rows["region"].tolist(), rows["file"], rows["record"], rows["record_index"].tolist(),
+                         rows["start"].tolist(), rows["end"].tolist(), rows["strand"], rows["mismatches"].tolist(),
+                         rows["mismatch_columns"], rows["pam5_match"].tolist(), rows["pam3_match"].tolist(), rows["sequence"]))
+
+
+# ----------------------------------------------------------------------------
 # stage functions (reference signatures)
 # ----------------------------------------------------------------------------
 def _hit_windows(sel, text, k):
