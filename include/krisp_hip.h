@@ -127,6 +127,14 @@ int kr_genome_upload(kr_ctx*, int genome_id, const uint8_t* bases, size_t n_base
  * anchor genome only (the other genomes' keys are looked up by hashing inside a bucket, in whatever order they lie),
  * kr_collect for the buckets its candidates touch.  Every call returns what it returns with the option off. */
 int kr_genome_sort(kr_ctx*, int genome_id);
+/* The sort up to its first partition pass only (256 buckets by the key's top byte).  Asynchronous, on a sort lane like a
+ * sort.  Such a "coarse" genome can be counted and be an argument of kr_intersect / kr_collect beside at least one sorted ingroup
+ * and one sorted outgroup genome with the filter on (one diagnostic column, at most 24 genomes): it then answers
+ * the short filtered list of the sorted genomes in one streaming read instead of being partitioned fine and hashed whole.
+ * Every other reader of the genome (its keys, the candidate probe, an intersection the route does not take) sorts it fine
+ * first, from its resident bases.  Contexts the route does not serve (wide windows, single strands, a custom field order,
+ * key-space slices, at most 256 fine buckets) and KR_OPT_COARSE_REST = 0: the call is the full sort. */
+int kr_genome_partition(kr_ctx*, int genome_id);
 /* upload + sort + sync; returns the number of k-mer records (>= 0). */
 int64_t kr_genome_add(kr_ctx*, int genome_id, const uint8_t* bases, size_t n_bases);
 int64_t kr_genome_count(kr_ctx*, int genome_id);               /* syncs */
@@ -605,6 +613,7 @@ enum { KR_OPT_SLICE_BASES = 1,       /* -1 automatic; 0..4: sort every genome in
                                         whatever the setting, kr_wide_run two when more than one is asked for.  May be set at any time */
        KR_OPT_LAZY_ORDER = 10,       /* 1 (default): kr_genome_sort stops at the fine buckets, the LDS sort runs where a reader needs
                                         the order (see kr_genome_sort); 0: every sort ends with it (rounds 1-5) */
+       KR_OPT_COARSE_REST = 11,      /* 1 (default; KR_COARSE_REST in the environment): kr_genome_partition stops behind pass 1; 0: it is the full sort */
        KR_OPT_WIDE_ORDERED = 6 };    /* wide path: 0 (default) flanks of >= 20 bases are numbered through minimizer buckets (look-ups
                                         of neighbouring windows share memory sectors): the same groups and hits, but `cand` no longer
                                         ascends with (left, right); 1: order-preserving ranks, groups in the reference's order */
@@ -651,7 +660,8 @@ const char* kr_debug_copy_which(kr_ctx*);
 int     kr_build_experiments(void);
 /* KR_OPT_LAZY_ORDER's counters: out[0] LDS sorts of whole slices kr_genome_sort left out, [1] made later (anchor, fetch, probe),
  * [2] kr_collect calls that read only the buckets their candidates touch, [3] the option's value, [4] intersection launches whose
- * anchor genome stayed in bucket order as well (k_intersect3t<., UA>), [5] 1 unless KR_FUSE_ANCHOR=0, [6..7] 0 */
+ * anchor genome stayed in bucket order as well (k_intersect3t<., UA>), [5] 1 unless KR_FUSE_ANCHOR=0,
+ * [6] genomes an intersection took in the coarse state (kr_genome_partition), [7] coarse genomes sorted fine after all */
 int     kr_debug_lazy(kr_ctx*, int64_t* out8);
 int     kr_debug_isect(kr_ctx*, int64_t* out8);
 /* the latest placement search of the pass-1 output buffers: out8[0] candidates probed, [1] buffers handed to the sort lanes,

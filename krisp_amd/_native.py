@@ -43,6 +43,7 @@ OPT_SLICE_BASES, OPT_GENERIC_INTERSECT, OPT_ISECT_FORMAT, OPT_ABLATE, OPT_WIDE_S
 OPT_ISECT_KERNEL = 8
 OPT_LANES = 9
 OPT_LAZY_ORDER = 10
+OPT_COARSE_REST = 11
 ERR_KEY, ERR_HOST = -5, -6
 STRANDS_BOTH, STRANDS_FORWARD, STRANDS_CANONICAL = 0, 1, 2
 STAGES = ["pack", "hist8", "reduce8", "scatter1", "hist2", "scan2", "scatter2", "chunks", "localsort",
@@ -68,6 +69,7 @@ SYMBOLS = [
     ("kr_set_strands", _c.c_int, [_P, _c.c_int]),
     ("kr_genome_upload", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t]),
     ("kr_genome_sort", _c.c_int, [_P, _c.c_int]),
+    ("kr_genome_partition", _c.c_int, [_P, _c.c_int]),
     ("kr_genome_add", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t]),
     ("kr_genome_count", _c.c_int64, [_P, _c.c_int]),
     ("kr_genome_load_sorted", _c.c_int64, [_P, _c.c_int, _P, _c.c_size_t]),
@@ -495,8 +497,18 @@ class Engine:
         self._check(self.lib.kr_genome_upload(self.ctx, gid, _ptr(buf) if len(buf) else None, len(buf)),
                     "kr_genome_upload")
 
-    def sort(self, gid):
-        self._check(self.lib.kr_genome_sort(self.ctx, gid), "kr_genome_sort")
+    def sort(self, gid, coarse=False):
+        """kr_genome_sort; coarse=True: the sort may stop behind its first pass (kr_genome_partition) -- enough for a genome
+        that joins an intersection beside a sorted ingroup and a sorted outgroup genome with the filter on; any other
+        reader sorts it fine by itself"""
+        if coarse:
+            self._check(self.lib.kr_genome_partition(self.ctx, gid), "kr_genome_partition")
+        else:
+            self._check(self.lib.kr_genome_sort(self.ctx, gid), "kr_genome_sort")
+
+    def partition(self, gid):
+        """sort(gid, coarse=True)"""
+        self.sort(gid, coarse=True)
 
     def add(self, gid, bases):
         self.upload(gid, bases)
@@ -888,7 +900,7 @@ class Engine:
         o = np.zeros(8, dtype=np.int64)
         self.lib.kr_debug_lazy(self.ctx, _ptr(o))
         return dict(skipped=int(o[0]), ordered_later=int(o[1]), touch_collects=int(o[2]), on=int(o[3]),
-                    anchor_in_bucket_order=int(o[4]), fuse_anchor=int(o[5]))
+                    anchor_in_bucket_order=int(o[4]), fuse_anchor=int(o[5]), coarse=int(o[6]), coarse_promoted=int(o[7]))
 
     def copy_gbps(self, nbytes=1 << 30, reps=10):
         v = self.lib.kr_debug_copy_gbps(self.ctx, nbytes, reps)

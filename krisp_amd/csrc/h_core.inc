@@ -28,6 +28,12 @@ struct Genome {
     bool uploaded = false, sorted = false, finalized = false;
     bool ordered = false;    // the keys are in order INSIDE their fine buckets too (k_localsort2 has run): what kr_genome_sort leaves
                              // undone under KR_OPT_LAZY_ORDER until somebody needs it (order_genome)
+    bool coarse = false;     // kr_genome_partition: the sort stopped behind pass 1 -- sl[0].keys holds the keys in 256 buckets by their top byte,
+                             // sl[0].off[0 .. 256] the buckets' bases, sl[0].off[2^b] the key count; `sorted` is false: whoever needs the fine
+                             // buckets calls ensure_fine() first.  kr_intersect takes such a genome by k_coarse_probe (h_intersect.inc)
+    DevBuf hits;             // ... and leaves its keys under the candidates' prefixes here (u32 count, keys from byte 16) for kr_collect
+    u32 hitcap = 0;
+    bool hits_valid = false; // `hits` belongs to the context's current candidate list (or to a list the current one is a part of)
     bool was_anchor = false; // the latest kr_intersect over this genome took it as its anchor: its next sort ends with the LDS sort
                              // on its own lane, beside the other genomes' passes, instead of in front of the intersection
     int64_t count = -1;
@@ -130,6 +136,13 @@ struct kr_ctx {
                                 // again -- on their lanes, beside each other -- instead of in front of the collect
     int64_t lazy_skipped = 0, lazy_ordered = 0, lazy_touch = 0;    // LDS sorts of whole slices left out / made later; bucket lists sorted for kr_collect
     DevBuf touchdesc, touchovf;   // kr_collect over genomes in bucket order: chunk descriptors of the touched buckets, their oversized list
+    int coarse_rest = 1;        // KR_OPT_COARSE_REST / KR_COARSE_REST env: 1 = kr_genome_partition stops behind pass 1 where the context is
+                                // eligible; 0 = it is kr_genome_sort
+    int64_t coarse_done = 0, coarse_promoted = 0;   // genomes kr_intersect took in the coarse state; coarse genomes sorted fine after all
+    DevBuf co_state, co_tab;    // k_coarse_probe: the candidates' state words; cb[257] + ust[257] per genome
+    u32 co_tcap = CO_TCAP;      // KR_COARSE_TCAP env (tests: several rounds per top byte at small sizes)
+    u32 co_hitcap = 0;          // KR_COARSE_HITCAP env (tests: a hit list that overflows; 0 = sized from the candidate list)
+    int co_occ = 0;             // resident k_coarse_probe workgroups per CU (occupancy query, cached)
     int slice_route = 1;        // KR_SLICE_ROUTE env (A/B, tests): 0 = every slice counts its keys again before its pass 1 (k_hist8k / k_scatter1kp)
     // wide windows (kr_set_params_wide / kr_wide_run)
     struct Wide {
@@ -344,6 +357,7 @@ static void release_genome(kr_ctx* c, Genome& G) {
     release(c, G.bases);
     release(c, G.wkeys);
     release(c, G.wlcnt);
+    release(c, G.hits);
     for (Slice& S : G.sl) {
         release(c, S.keys);
         release(c, S.off);
@@ -464,6 +478,12 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         c->fuse_anchor = e16 ? atoi(e16) != 0 : 1;
         const char* e15 = getenv("KR_LAZY_ORDER");
         c->lazy_order = e15 ? atoi(e15) != 0 : 1;
+        const char* e17 = getenv("KR_COARSE_REST");
+        c->coarse_rest = e17 ? atoi(e17) != 0 : 1;
+        const char* e18 = getenv("KR_COARSE_TCAP");
+        if (e18) c->co_tcap = (u32)std::max(1, std::min((int)CO_TCAP, atoi(e18)));
+        const char* e19 = getenv("KR_COARSE_HITCAP");
+        if (e19) c->co_hitcap = (u32)std::max(1, atoi(e19));
         const char* e13 = getenv("KR_SLICE_ROUTE");
         c->slice_route = e13 ? atoi(e13) != 0 : 1;
         const char* e8 = getenv("KR_PLACE_TRIES");
@@ -527,7 +547,7 @@ void kr_destroy(kr_ctx* c) {
                      &c->chunkpos, &c->flags, &c->blockcnt, &c->blockpos, &c->other, &c->records, &c->nrec, &c->fbdesc, &c->fbsegs,
                      &c->coltab, &c->collo, &c->colcnt, &c->colpos, &c->coltsum, &c->coltpos, &c->colfirst, &c->colfm, &c->isovf,
                      &c->bgz_in, &c->bgz_tab, &c->bgz_stat, &c->tx_scan, &c->tx_text, &c->tx_tile, &c->tx_tilepos, &c->tx_lines, &c->tx_ls, &c->tx_ll, &c->tx_op, &c->tx_outpos, &c->tx_state,
-                     &c->tx_tsum, &c->tx_tpos, &c->candP, &c->touchdesc, &c->touchovf};
+                     &c->tx_tsum, &c->tx_tpos, &c->candP, &c->touchdesc, &c->touchovf, &c->co_state, &c->co_tab};
     for (DevBuf* b : all) release(c, *b);
     {
         auto& w = c->wide;
@@ -707,6 +727,10 @@ int kr_set_option(kr_ctx* c, int option, int64_t value) {
     case KR_OPT_LAZY_ORDER:
         if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_LAZY_ORDER: 0 or 1");
         c->lazy_order = (int)value;
+        return KR_OK;
+    case KR_OPT_COARSE_REST:
+        if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_COARSE_REST: 0 or 1");
+        c->coarse_rest = (int)value;
         return KR_OK;
     case KR_OPT_ABLATE:
 #ifdef KR_ABLATE
@@ -1094,7 +1118,7 @@ static int count_slices(kr_ctx* c, Genome& G) {
     std::vector<u32> tot(256);
     u64 maxcount = 0;
     G.nmax = 0;
-    G.sorted = G.finalized = G.ordered = false;
+    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
     G.count = -1;
     // ONE histogram of the top byte of the absolute keys: a slice is 2^(8 - sbits) of its buckets
     Geom g0 = c->g;
@@ -1154,7 +1178,7 @@ int kr_genome_upload(kr_ctx* c, int id, const uint8_t* bases, size_t n) {
     G.id = id;
     G.n_bases = n;
     G.nwords = (n + 31) / 32;
-    G.sorted = G.finalized = G.ordered = false;
+    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
     G.count = -1;
     int rc;
     if ((rc = ensure(c, G.bases, n + 64))) return rc;
@@ -1266,13 +1290,26 @@ int kr_reserve(kr_ctx* c, const int* ids, int n, size_t n_bases, int with_text) 
     return KR_OK;
 }
 
-static int genome_sort(kr_ctx* c, int id, bool reuse_count);
+static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse = false);
 int kr_genome_sort(kr_ctx* c, int id) { return genome_sort(c, id, false); }
+
+// The sort up to pass 1 only (pack, top-byte histogram, its reduction, k_scatter1p -- on a sort lane, as a sort): what a
+// genome needs to answer a short candidate list (k_coarse.inc).  For the contexts the coarse route of kr_intersect takes:
+// packed windows of both strands, one sort unit, the standard field order, more than 256 fine buckets; any other
+// context, or KR_OPT_COARSE_REST = 0: kr_genome_sort.
+static bool coarse_eligible(const kr_ctx* c) {
+    return c->coarse_rest && c->have_params && !c->wide.on && c->g.wmode == 0 && c->g.strands == 0 && !c->custom_layout &&
+           c->nslices == 1 && c->g.b > 8;
+}
+int kr_genome_partition(kr_ctx* c, int id) {
+    if (!c) return KR_ERR_PARAM;
+    return genome_sort(c, id, false, coarse_eligible(c));
+}
 
 // reuse_count: count_slices(G) has just run on this lane (single lane): the codes, the bad
 // bits and the workgroup histograms of the absolute top byte (already prefix-summed by
 // k_reduce8a) are still in the lane's scratch
-static int genome_sort(kr_ctx* c, int id, bool reuse_count) {
+static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
     if (!c) return KR_ERR_PARAM;
     auto it = c->genomes.find(id);
     if (it == c->genomes.end() || !it->second.uploaded) return fail(c, KR_ERR_STATE, "genome %d not uploaded", id);
@@ -1308,7 +1345,7 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count) {
     if (it->second.up_done && st != c->stream) HIPCHK(c, hipStreamWaitEvent(st, it->second.up_done, 0));
     u64* codes = (u64*)ln.codes.p;
     u32* bad = (u32*)ln.bad.p;
-    G.sorted = G.finalized = G.ordered = false;
+    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
     G.count = -1;
     const bool cached_keys = reuse_count && c->g.wmode == 2 && c->g.wcache;
     const int cached_mode = c->g.wlcnt ? 4 : 2;         // (the key list, Geom.wlcnt, or 16 bytes per window start)
@@ -1424,7 +1461,7 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count) {
         const u64* src = (const u64*)ln.pass0.p + region;
         region += S.nmax;
         const u32 tile2 = 2 * P2_TILE;
-        u64* pass1_dst = g.b > 8 ? (u64*)ls.tmpkeys.p : (u64*)S.keys.p;
+        u64* pass1_dst = (g.b > 8 && !coarse) ? (u64*)ls.tmpkeys.p : (u64*)S.keys.p;
         if (route2) {
             const u32 ntA = (u32)((S.nmax + tile2 - 1) / tile2);
             if (ntA) {
@@ -1451,9 +1488,9 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count) {
             StageScope sc(c, KR_ST_REDUCE8, ss);
             if (sliced || !reuse_count)
                 hipLaunchKernelGGL(k_reduce8a, dim3(256), dim3(256), 0, ss, (u32*)ln.partial8.p, (u32*)ls.base1.p + 260);
-            const u32 ntmax = g.b > 8 ? (u32)(S.nmax / tile2) + 257 : 0u;
+            const u32 ntmax = (g.b > 8 && !coarse) ? (u32)(S.nmax / tile2) + 257 : 0u;
             hipLaunchKernelGGL(k_reduce8b, dim3(std::max(1u, (ntmax + 255) / 256)), dim3(256), 0, ss,
-                               (const u32*)ls.base1.p + 260, (u32*)ls.base1.p, (u32*)ls.tp.p, g.b > 8 ? tile2 : 0u, ntmax,
+                               (const u32*)ls.base1.p + 260, (u32*)ls.base1.p, (u32*)ls.tp.p, ntmax ? tile2 : 0u, ntmax,
                                (uint2*)ls.tiledesc.p, (const u32*)nullptr, 0u);
         }
         {
@@ -1465,6 +1502,12 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count) {
                 launch_scatter1(g, ss, (const u64*)codes, (const u32*)bad, G.nwords, (const u32*)ls.base1.p,
                                 (const u64*)nullptr, (const u32*)ln.partial8.p, pass1_dst, S.nmax);
         }
+        }
+        if (coarse) {
+            // (the buckets' bases leave the lane's scratch; the words finalize() reads: no oversized bucket, the key count)
+            StageScope sc(c, KR_ST_REDUCE8, ss);
+            hipLaunchKernelGGL(k_coarse_keep, dim3(1), dim3(320), 0, ss, (const u32*)ls.base1.p, (u32*)S.off.p, nb, (u32*)S.ovf.p);
+            continue;
         }
         // fine offsets straight from the codes when the top b bits of a key lie inside `left`
         const bool fine16 = USE_HIST16 && g.b > 8 && !sliced && g.wmode == 0 && g.strands == 0 && 2 * g.L >= g.b;
@@ -1526,8 +1569,9 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count) {
             c->lazy_skipped++;
         }
     }
-    G.ordered = !lazy;
-    G.sorted = true;      // enqueued; oversized buckets (if any) are resolved by finalize()
+    G.ordered = !lazy && !coarse;
+    G.sorted = !coarse;   // enqueued; oversized buckets (if any) are resolved by finalize()
+    G.coarse = coarse;
     G.sort_seq = c->sorts_done;
     if (!sliced) {
         if (!G.sort_ev) HIPCHK(c, hipEventCreateWithFlags(&G.sort_ev, hipEventDisableTiming));
@@ -1538,6 +1582,18 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count) {
 
 // The two words finalize() reads of each listed slice, into the host mailbox (n <= PUB_CAP; the caller synchronises
 // `st` before the next call of this function: the table is one).
+// a coarse genome (kr_genome_partition) sorted whole after all, from its resident bases: pass 1 runs again -- the price of
+// the rare path (a reader of its keys, a candidate list the coarse route does not take)
+static int ensure_fine(kr_ctx* c, Genome& G) {
+    if (!G.coarse) return KR_OK;
+    c->coarse_promoted++;
+    return genome_sort(c, G.id, false);
+}
+static int ensure_fine_id(kr_ctx* c, int id) {
+    auto it = c->genomes.find(id);
+    return (it == c->genomes.end()) ? KR_OK : ensure_fine(c, it->second);
+}
+
 static void publish_slices(kr_ctx* c, Slice* const* sl, size_t n, hipStream_t st) {
     PubEnt* tab = (PubEnt*)(c->mbox + MB_WORDS);
     const u32 nb = 1u << c->g.b;
@@ -1593,7 +1649,7 @@ static int finalize(kr_ctx* c, const std::vector<Genome*>& gs, bool already_sync
     std::vector<Slice*> todo;
     std::vector<Genome*> tg;
     for (Genome* G : gs)
-        if (G->sorted && !G->finalized) {
+        if ((G->sorted || G->coarse) && !G->finalized) {
             tg.push_back(G);
             for (Slice& S : G->sl) todo.push_back(&S);
         }
@@ -1732,6 +1788,7 @@ int64_t kr_genome_load_sorted(kr_ctx* c, int id, const uint64_t* keys, size_t n)
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     G.uploaded = false;
+    G.coarse = G.hits_valid = false;
     G.sorted = true;
     G.ordered = true;
     G.finalized = true;
@@ -1742,9 +1799,9 @@ int64_t kr_genome_load_sorted(kr_ctx* c, int id, const uint64_t* keys, size_t n)
 int64_t kr_genome_count(kr_ctx* c, int id) {
     if (!c) return KR_ERR_PARAM;
     auto it = c->genomes.find(id);
-    if (it == c->genomes.end() || !it->second.sorted) return fail(c, KR_ERR_STATE, "genome %d not sorted", id);
+    if (it == c->genomes.end() || !(it->second.sorted || it->second.coarse)) return fail(c, KR_ERR_STATE, "genome %d not sorted", id);
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = finalize(c, {&it->second});
+    int rc = finalize(c, {&it->second});          // (a coarse genome stays coarse: its count comes from pass 1's histogram)
     if (rc) return rc;
     return it->second.count;
 }
@@ -1761,6 +1818,11 @@ int64_t kr_genome_fetch_keys(kr_ctx* c, int id, uint64_t* out, size_t cap) {
     if (!c) return KR_ERR_PARAM;
     {
         auto it = c->genomes.find(id);
+        if (it != c->genomes.end() && it->second.coarse) {
+            HIPCHK(c, hipSetDevice(c->device));
+            int rcf = ensure_fine(c, it->second);
+            if (rcf) return rcf;
+        }
         if (it != c->genomes.end() && it->second.sorted) {
             HIPCHK(c, hipSetDevice(c->device));
             int rco = ensure_ordered(c, {&it->second});

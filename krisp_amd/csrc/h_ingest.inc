@@ -155,7 +155,7 @@ static int64_t upload_text_impl(kr_ctx* c, int id, const uint8_t* text, size_t n
     if (known) HIPCHK(c, hipDeviceSynchronize());
     Genome& G = c->genomes[id];
     G.id = id;
-    G.sorted = G.finalized = G.ordered = false;
+    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
     G.uploaded = false;
     G.count = -1;
     int rc;

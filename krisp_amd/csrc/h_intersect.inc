@@ -33,9 +33,133 @@ static int64_t intersect_batch(kr_ctx* c, const int* ids, int n, const uint8_t* 
 // More than MAXG genomes (the presence word of a prefix has 32 bits): batches of MAXG, each batch's candidates
 // intersected with the running list ON THE DEVICE (k_cands_flag / k_cands_compact: list (x) list, masks OR-ed) -- the
 // running list never leaves HBM --, the diagnostic filter once at the end (it needs every genome's masks).
+// Coarse genomes among the arguments (kr_genome_partition).  The sorted genomes of the call -- the "pillars": at least one
+// ingroup and one outgroup genome -- are intersected as ever, filter on: the list C, about 1 % of a genome's prefixes (those
+// the pillars share and whose diagnostic base differs; the filter is monotone on partial masks, DESIGN 2).  Every coarse
+// genome then streams its pass-1 output past C once (k_coarse_probe): presence and diagnostic bases into a state word per
+// candidate, its keys under a candidate's prefix into its hit list; k_coarse_flag applies the presence test and the filter
+// to the completed masks.  Needs filter mode 1, one diagnostic column, at most CO_MAXG genomes; else, or when a hit list
+// overflows, the coarse genomes are sorted fine and the call is today's.  Returns KR_COARSE_PASS for "not taken".
+#define KR_COARSE_PASS (-1001)       // internal
+static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t* is_in, int apply_filter) {
+    std::vector<Genome*> cg;
+    std::vector<int> pid, cpos;
+    std::vector<uint8_t> pin;
+    bool has_in = false, has_out = false;
+    for (int i = 0; i < n; i++) {
+        auto it = c->genomes.find(ids[i]);
+        if (it == c->genomes.end()) return KR_COARSE_PASS;          // (the usual path reports it)
+        if (it->second.coarse) { cg.push_back(&it->second); cpos.push_back(i); }
+        else {
+            pid.push_back(ids[i]);
+            pin.push_back(is_in[i]);
+            (is_in[i] ? has_in : has_out) = true;
+        }
+    }
+    if (cg.empty()) return KR_COARSE_PASS;
+    const bool ok = apply_filter && fmode(c, apply_filter) == 1 && c->g.D == 1 && n <= CO_MAXG && has_in && has_out &&
+                    c->nslices == 1 && !c->wide.on && !c->custom_layout;
+    if (!ok) return KR_COARSE_PASS;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t nC64 = intersect_batch(c, pid.data(), (int)pid.size(), pin.data(), 1);
+    if (nC64 <= 0) {
+        if (nC64 == 0) c->coarse_done += (int64_t)cg.size();
+        return nC64;
+    }
+    int rc;
+    if ((rc = cands_fit(c, (uint64_t)nC64, "kr_intersect"))) return rc;
+    const u32 nC = (u32)nC64, nblk = (nC + 255) / 256;
+    const Geom g = slice_geom(c, 0);
+    hipStream_t st = c->stream;
+    // (a hit list holds the genome's keys under ANY candidate of C: at the reference's divergences about 0.8 per candidate)
+    const u32 hitcap = c->co_hitcap ? c->co_hitcap : (u32)std::min<u64>(2ull * nC + 65536, 0x7FFFFFF0ull);
+    if ((rc = ensure(c, c->co_state, (size_t)nC * 4))) return rc;
+    if ((rc = ensure(c, c->co_tab, (size_t)(1 + cg.size()) * 260 * 4))) return rc;
+    if ((rc = ensure(c, c->flags, (size_t)nC * 4))) return rc;
+    if ((rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4))) return rc;
+    if ((rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4))) return rc;
+    if ((rc = ensure(c, c->candA, ((size_t)nC + 2) * sizeof(kr_cand)))) return rc;
+    for (Genome* G : cg) {
+        if (G->hitcap < hitcap || !G->hits.p) {
+            if ((rc = ensure(c, G->hits, (size_t)hitcap * 8 + 16))) return rc;
+        }
+        G->hitcap = hitcap;
+        G->hits_valid = false;
+    }
+    if (c->co_occ == 0) {
+        int per = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_coarse_probe, CO_T, 0);
+        c->co_occ = (e == hipSuccess && per >= 1) ? per : 1;
+    }
+    if ((rc = join_lanes(c))) return rc;                // (the partitions ran on the sort lanes)
+    HIPCHK(c, hipMemsetAsync(c->co_state.p, 0, (size_t)nC * 4, st));
+    u32* cb = (u32*)c->co_tab.p;
+    u32 need = 0;
+    CoarsePub pub{};
+    pub.n = (int)cg.size();
+    {
+        StageScope sc(c, KR_ST_INTERSECT, st);
+        for (size_t j = 0; j < cg.size(); j++) {
+            Genome& G = *cg[j];
+            Slice& S = G.sl[0];
+            u32* ust = cb + 260 * (j + 1);
+            HIPCHK(c, hipMemsetAsync(G.hits.p, 0, 16, st));
+            hipLaunchKernelGGL(k_coarse_tables, dim3(1), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC, (const u32*)S.off.p,
+                               c->co_tcap, cb, ust);
+            hipLaunchKernelGGL(k_coarse_probe, dim3((u32)(c->co_occ * c->ncu)), dim3(CO_T), 0, st, (const u64*)S.keys.p,
+                               (const u32*)S.off.p, (const u32*)cb, (const u32*)ust, (const kr_cand*)c->candB.p,
+                               (u32*)c->co_state.p, (u32*)G.hits.p, hitcap, c->co_tcap, (u32)j, is_in[cpos[j]] ? 0u : 4u,
+                               g.pmask, g.LRrel);
+            need |= 1u << (8 + j);
+            pub.cnt[j] = (const u32*)G.hits.p;
+        }
+    }
+    {
+        StageScope sc(c, KR_ST_MERGE, st);
+        hipLaunchKernelGGL(k_coarse_flag, dim3(nblk), dim3(256), 0, st, (kr_cand*)c->candB.p, nC, (const u32*)c->co_state.p, need,
+                           fmode(c, 1), (u32*)c->flags.p, (u32*)c->blockcnt.p);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
+        hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC,
+                           (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
+        hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, (const u32*)c->blockpos.p + nblk, (const u32*)nullptr,
+                           (const u32*)nullptr, c->mbox + 16);
+        hipLaunchKernelGGL(k_coarse_publish, dim3(1), dim3(64), 0, st, pub, c->mbox + 32);
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    for (size_t j = 0; j < cg.size(); j++)
+        if (((volatile u32*)c->mbox)[32 + j] > hitcap) {
+            // a hit list that overflowed (a genome that repeats the candidates' prefixes many times over): nothing is
+            // truncated -- the coarse genomes are sorted fine and the caller runs the call over all of them
+            c->ncand = -1;
+            return KR_COARSE_PASS;
+        }
+    const u32 total = ((volatile u32*)c->mbox)[16];
+    std::swap(c->candA, c->candB);
+    c->ncand = total;
+    for (Genome* G : cg) G->hits_valid = true;
+    c->coarse_done += (int64_t)cg.size();
+    return total;
+}
+
 int64_t kr_intersect(kr_ctx* c, const int* ids, int n, const uint8_t* is_in, int apply_filter) {
     if (!c || n < 1) return fail(c, KR_ERR_PARAM, "kr_intersect: need at least one genome");
     if (c->custom_layout) return fail(c, KR_ERR_STATE, "kr_intersect: this context sorts by a custom field order (kr_set_field_order)");
+    {
+        bool any_coarse = false;
+        for (auto& kv : c->genomes) kv.second.hits_valid = false;      // (hit lists belong to ONE candidate list: the one made below)
+        for (int i = 0; i < n; i++) {
+            auto it = c->genomes.find(ids[i]);
+            any_coarse = any_coarse || (it != c->genomes.end() && it->second.coarse);
+        }
+        if (any_coarse) {
+            const int64_t r = intersect_coarse(c, ids, n, is_in, apply_filter);
+            if (r != KR_COARSE_PASS) return r;
+            int rcf;
+            for (int i = 0; i < n; i++)
+                if ((rcf = ensure_fine_id(c, ids[i]))) return rcf;
+        }
+    }
     if (n <= MAXG) return intersect_batch(c, ids, n, is_in, apply_filter);
     HIPCHK(c, hipSetDevice(c->device));
     int64_t cur = -1, nprev = 0;
@@ -451,6 +575,7 @@ int64_t kr_cands_load(kr_ctx* c, const kr_cand* cands, size_t n) {
     if ((rc = ensure(c, c->candB, (n + 2) * sizeof(kr_cand)))) return rc;
     if ((rc = ensure(c, c->candA, (n + 2) * sizeof(kr_cand)))) return rc;
     if (n) HIPCHK(c, hipMemcpy(c->candB.p, cands, n * sizeof(kr_cand), hipMemcpyHostToDevice));
+    for (auto& kv : c->genomes) kv.second.hits_valid = false;      // (a list from outside: no coarse genome has its hits)
     c->ncand = (int64_t)n;
     return c->ncand;
 }
@@ -543,6 +668,7 @@ static int64_t cands_probe_impl(kr_ctx* c, const int* ids, int n, const uint8_t*
         std::vector<Genome*> gs;
         u32 bits = 0;
         for (int i = 0; i < m; i++) {
+            if ((rc = ensure_fine_id(c, ids[o + i]))) return rc;
             auto it = c->genomes.find(ids[o + i]);
             if (it == c->genomes.end() || !it->second.sorted) return fail(c, KR_ERR_STATE, "genome %d not sorted", ids[o + i]);
             gs.push_back(&it->second);
@@ -621,10 +747,28 @@ static int64_t collect_impl(kr_ctx* c, const int* ids, int n, bool force_order) 
     const u32 nc = (u32)c->ncand;
     c->nrecords = 0;
     if (nc == 0 || n == 0) return 0;
+    // coarse genomes (kr_genome_partition): the rows of their (candidate, genome) pairs come from the hit lists the coarse
+    // route of kr_intersect left -- where the list is short enough for the arena (a row per pair) and every such genome's
+    // hits belong to this list; else they are sorted fine first
+    bool any_coarse = false;
+    {
+        bool hits_ok = !force_order && (u64)nc * (u64)n <= ((u64)1 << 22);
+        for (int i = 0; i < n; i++) {
+            auto it = c->genomes.find(ids[i]);
+            if (it == c->genomes.end() || !it->second.coarse) continue;
+            any_coarse = true;
+            hits_ok = hits_ok && it->second.hits_valid;
+        }
+        if (any_coarse && !hits_ok) {
+            for (int i = 0; i < n; i++)
+                if ((rc = ensure_fine_id(c, ids[i]))) return rc;
+            any_coarse = false;
+        }
+    }
     std::vector<Genome*> gs;
     for (int i = 0; i < n; i++) {
         auto it = c->genomes.find(ids[i]);
-        if (it == c->genomes.end() || !it->second.sorted)
+        if (it == c->genomes.end() || !(it->second.sorted || it->second.coarse))
             return fail(c, KR_ERR_STATE, "genome %d not sorted", ids[i]);
         gs.push_back(&it->second);
     }
@@ -640,10 +784,11 @@ static int64_t collect_impl(kr_ctx* c, const int* ids, int n, bool force_order) 
             const u64 nbk = (u64)1 << c->g.b;
             touch = !force_order && 2 * c->g.LRrel >= c->g.b && (u64)nc * 4 <= nbk * (u64)c->nslices &&
                     (u64)nc * (u64)n <= ((u64)1 << 22);
-            if (!touch && (rc = ensure_ordered(c, gs))) return rc;
+            if (!touch && (rc = ensure_ordered(c, gs))) return rc;          // (a coarse genome is left as it is)
             c->order_wanted = !touch;
         }
     }
+    const bool arena_on = touch || any_coarse;          // (rows of the pairs: read from buckets, or filled from hit lists)
     if ((rc = finalize(c, gs))) return rc;
     // pointer tables [genome][slice] + the genome ids (+ which genomes lie in bucket order), one upload
     const size_t np = (size_t)n * c->nslices;
@@ -656,7 +801,7 @@ static int64_t collect_impl(kr_ctx* c, const int* ids, int n, bool force_order) 
     u32* gid_host = (u32*)&tab[2 * np];
     for (int i = 0; i < n; i++) gid_host[i] = (u32)ids[i];
     u32* ibo_host = (u32*)&tab[2 * np + (n + 1) / 2];
-    for (int i = 0; i < n; i++) ibo_host[i] = (touch && !gs[i]->ordered) ? 1u : 0u;
+    for (int i = 0; i < n; i++) ibo_host[i] = gs[i]->coarse ? 2u : ((touch && !gs[i]->ordered) ? 1u : 0u);   // (2: the row from the hit list)
     if (c->coltab.bytes < tab.size() * 8) c->coltab_host.clear();
     if ((rc = ensure(c, c->coltab, tab.size() * 8))) return rc;
     // a thread, a count and a place per (candidate, genome) pair -- in chunks of candidates, so that neither the pair
@@ -694,7 +839,7 @@ static int64_t collect_impl(kr_ctx* c, const int* ids, int n, bool force_order) 
     a.arena = nullptr;
     a.mcnt = nullptr;
     const Geom g = slice_geom(c, 0);
-    if (touch) {
+    if (arena_on) {
         // (the arena rows and counts of the pairs; ordered genomes' rows stay unused)
         const size_t npairs = (size_t)nc * (size_t)n;
         if ((rc = ensure(c, c->touchdesc, npairs * COL_CAPM * 8 + npairs * 4 + 64))) return rc;
@@ -706,19 +851,29 @@ static int64_t collect_impl(kr_ctx* c, const int* ids, int n, bool force_order) 
         a.arena = arena;
         a.mcnt = mcnt;
         StageScope sc(c, KR_ST_COLLECT);
-        hipLaunchKernelGGL(k_collect_scan, dim3((u32)((npairs + 3) / 4)), dim3(256), 0, st, (const kr_cand*)c->candB.p, (u32)npairs, a, g,
-                           arena, mcnt, (u32*)c->touchovf.p);
+        if (any_coarse) HIPCHK(c, hipMemsetAsync(mcnt, 0, npairs * 4, st));      // (the hits take their places in a row by counting)
+        if (touch)
+            hipLaunchKernelGGL(k_collect_scan, dim3((u32)((npairs + 3) / 4)), dim3(256), 0, st, (const kr_cand*)c->candB.p, (u32)npairs, a, g,
+                               arena, mcnt, (u32*)c->touchovf.p);
+        if (any_coarse) {
+            for (int i = 0; i < n; i++)
+                if (gs[i]->coarse)
+                    hipLaunchKernelGGL(k_coarse_rows, dim3(1024), dim3(256), 0, st, (const u32*)gs[i]->hits.p, gs[i]->hitcap,
+                                       (const kr_cand*)c->candB.p, nc, (u32)n, (u32)i, g.pmask, arena, mcnt);
+            hipLaunchKernelGGL(k_coarse_rowsort, dim3((u32)((npairs + 255) / 256)), dim3(256), 0, st, (u32)npairs, (u32)n, a.ibo, arena,
+                               mcnt, (u32*)c->touchovf.p);
+        }
         // (a pair with more keys than an arena row holds: looked at behind the first synchronisation below)
         hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, (const u32*)c->touchovf.p, (const u32*)nullptr,
                            (const u32*)nullptr, c->mbox + 20);
-        c->lazy_touch++;
+        if (touch) c->lazy_touch++;
     }
     u64 done = 0;                           // records of the chunks so far
     for (u32 c0 = 0; c0 < nc; c0 += per) {
         const u32 cc = std::min(per, nc - c0), np2 = cc * (u32)n;
         const kr_cand* cand = (const kr_cand*)c->candB.p + c0;
         CollectArgs ac = a;             // (this chunk's rows of the arena: the kernels index pairs from the chunk's first)
-        if (touch) {
+        if (arena_on) {
             ac.arena = a.arena + (size_t)c0 * n * COL_CAPM;
             ac.mcnt = a.mcnt + (size_t)c0 * n;
         }
@@ -754,7 +909,7 @@ static int64_t collect_impl(kr_ctx* c, const int* ids, int n, bool force_order) 
         }
         HIPCHK(c, hipStreamSynchronize(st));         // (also: `tab` may go out of scope now)
         HIPCHK(c, hipGetLastError());
-        if (touch && ((volatile u32*)c->mbox)[20] != 0)     // a pair with more keys than its arena row: the genomes sorted
+        if (arena_on && ((volatile u32*)c->mbox)[20] != 0)     // a pair with more keys than its arena row: the genomes sorted
             return collect_impl(c, ids, n, true);           // whole, and once more
         total = ((volatile u32*)c->mbox)[4];
         if (total > cap) {

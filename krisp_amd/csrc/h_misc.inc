@@ -4,6 +4,7 @@
 double kr_debug_localsort(kr_ctx* c, int id, int reps, int mode) {
     if (!c || mode != 0) return -1.0;
     auto it = c->genomes.find(id);
+    if (it != c->genomes.end() && ensure_fine(c, it->second)) return -1.0;
     if (it == c->genomes.end() || !it->second.sorted || it->second.sl.empty()) return -1.0;
     if (ensure_ordered(c, {&it->second}) || finalize(c, {&it->second})) return -1.0;
     Slice& S = it->second.sl[0];
@@ -179,6 +180,7 @@ int64_t kr_debug_fetch(kr_ctx* c, int id, int what, void* out, size_t cap_bytes)
     if (it == c->genomes.end()) return fail(c, KR_ERR_PARAM, "unknown genome %d", id);
     Genome& G = it->second;
     HIPCHK(c, hipSetDevice(c->device));
+    { int rcf = ensure_fine(c, G); if (rcf) return rcf; }
     if (what == 5 && G.sorted && !G.ordered) {      // (KR_OPT_LAZY_ORDER: selector 5 has always meant the sorted keys)
         int rco = ensure_ordered(c, {&G});
         if (!rco) rco = finalize(c, {&G});
@@ -210,6 +212,7 @@ int64_t kr_debug_fetch(kr_ctx* c, int id, int what, void* out, size_t cap_bytes)
 int64_t kr_debug_inversions(kr_ctx* c, int id) {
     if (!c) return KR_ERR_PARAM;
     auto it = c->genomes.find(id);
+    if (it != c->genomes.end()) { int rcf = ensure_fine(c, it->second); if (rcf) return rcf; }
     if (it == c->genomes.end() || !it->second.sorted) return fail(c, KR_ERR_STATE, "genome %d not sorted", id);
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_ordered(c, {&it->second});
@@ -309,7 +312,8 @@ int kr_debug_lazy(kr_ctx* c, int64_t* o) {
     o[3] = c->lazy_order;
     o[4] = c->isect_ua;
     o[5] = c->fuse_anchor;
-    o[6] = o[7] = 0;
+    o[6] = c->coarse_done;
+    o[7] = c->coarse_promoted;
     return KR_OK;
 }
 

@@ -457,7 +457,7 @@ struct CollectArgs {
     const u32* const* off;      // [genome * nslices + slice]: fine bucket offsets
     const u32* gid;             // genome ids of the call, in the caller's order
     int n, nslices;
-    // KR_OPT_LAZY_ORDER: genomes still in bucket order (ibo[genome] != 0; null = none).  k_collect_scan has left the keys of
+    // KR_OPT_LAZY_ORDER: genomes still in bucket order (ibo[genome] != 0; null = none; 2 = a coarse genome, k_coarse.inc).  k_collect_scan has left the keys of
     // every (candidate, such genome) pair -- found by reading the pair's fine bucket once -- sorted at arena[pair * COL_CAPM ...],
     // mcnt[pair] of them: k_collect_count / k_collect_emit read a pair's run from there instead of the genome
     const u32* ibo;
@@ -632,7 +632,7 @@ __global__ __launch_bounds__(256) void k_collect_scan(const kr_cand* __restrict_
     const u32 idx = blockIdx.x * 4 + wave;
     if (idx >= npairs) return;
     const u32 c = idx / (u32)a.n, gi = idx - c * (u32)a.n;
-    if (!a.ibo[gi]) return;
+    if (a.ibo[gi] != 1u) return;                        // (0: a sorted genome; 2: a coarse one, its rows come from its hit list: k_coarse_rows)
     u64 pre = cands[c].prefix;                          // absolute
     const u32 s = g.sbits ? (u32)(pre >> (64 - g.sbits)) : 0u;
     pre <<= g.sbits;

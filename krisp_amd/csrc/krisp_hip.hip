@@ -50,6 +50,7 @@
 #include "k_products.inc"    // the product pass: sites of the flanks within M substitutions, joined into PCR products
 #include "k_primers.inc"     // the primer-product pass: sites of primer texts of mixed lengths, joined into PCR products
 #include "k_design.inc"      // the primer design pass: a wavefront per region, integer thermodynamics, the best pair
+#include "k_coarse.inc"      // a genome that stopped behind pass 1 against a short candidate list: LDS table per top byte, hit list
 #include "k_guides.inc"      // the guide pass: a wavefront per region, the window next to a PAM that differs most from the outgroup rows
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
 #include "h_intersect.inc"   // kr_intersect, candidate lists, kr_collect

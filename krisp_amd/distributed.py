@@ -192,8 +192,20 @@ def sharded_step(eng, ids, flags, world, apply_filter=True, collect=True):
     csrc/h_comm.inc; the survivors broadcast) and the local collect of the survivors' records.
     bench.py --gpus N times exactly this function, tests/test_gpu_fullsize.py runs it at world 8.
     Returns (candidates after the reduction -- on rank 0 --, this rank's record count)."""
-    for g in ids:
-        eng.sort(g)
+    # the first ingroup and the first outgroup genome are sorted; with the filter on the others only need the first
+    # partition pass (Engine.sort(g, coarse=True): they answer the two sorted genomes' short filtered list in one streaming read;
+    # KR_OPT_COARSE_REST / KR_COARSE_REST = 0, or a context the route does not serve: partition is sort)
+    flags = [bool(f) for f in flags]
+    pillars = set()
+    # (the route takes one diagnostic column and at most 24 genomes: beyond that the library would sort the rest fine after all)
+    if apply_filter and any(flags) and not all(flags) and len(ids) <= 24 and getattr(eng, "params", (0, 0, 0))[1] == 1:
+        pillars = {flags.index(True), flags.index(False)}
+    # (one entry point per genome on every rank, as ever: sort -- which may stop early for the genomes beside the pillars)
+    for i, g in enumerate(ids):
+        if pillars and i not in pillars:
+            eng.sort(g, coarse=True)
+        else:
+            eng.sort(g)
     n = eng.intersect(ids, flags, apply_filter=apply_filter)
     if world > 1:
         n = eng.cands_reduce(apply_filter=apply_filter)
