@@ -143,6 +143,7 @@ struct kr_ctx {
     u32 co_tcap = CO_TCAP;      // KR_COARSE_TCAP env (tests: several rounds per top byte at small sizes)
     u32 co_hitcap = 0;          // KR_COARSE_HITCAP env (tests: a hit list that overflows; 0 = sized from the candidate list)
     int co_occ = 0;             // resident k_coarse_probe workgroups per CU (occupancy query, cached)
+    u32 co_grid = 0;            // KR_COARSE_GRID env (tests: a few workgroups walk many work units; 0 = co_occ x the CUs)
     int slice_route = 1;        // KR_SLICE_ROUTE env (A/B, tests): 0 = every slice counts its keys again before its pass 1 (k_hist8k / k_scatter1kp)
     // wide windows (kr_set_params_wide / kr_wide_run)
     struct Wide {
@@ -484,6 +485,8 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         if (e18) c->co_tcap = (u32)std::max(1, std::min((int)CO_TCAP, atoi(e18)));
         const char* e19 = getenv("KR_COARSE_HITCAP");
         if (e19) c->co_hitcap = (u32)std::max(1, atoi(e19));
+        const char* e20 = getenv("KR_COARSE_GRID");
+        if (e20) c->co_grid = (u32)std::max(0, std::min(65536, atoi(e20)));
         const char* e13 = getenv("KR_SLICE_ROUTE");
         c->slice_route = e13 ? atoi(e13) != 0 : 1;
         const char* e8 = getenv("KR_PLACE_TRIES");

@@ -91,6 +91,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
         const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_coarse_probe, CO_T, 0);
         c->co_occ = (e == hipSuccess && per >= 1) ? per : 1;
     }
+    const u32 grid = c->co_grid ? c->co_grid : (u32)(c->co_occ * c->ncu);
     if ((rc = join_lanes(c))) return rc;                // (the partitions ran on the sort lanes)
     HIPCHK(c, hipMemsetAsync(c->co_state.p, 0, (size_t)nC * 4, st));
     u32* cb = (u32*)c->co_tab.p;
@@ -106,7 +107,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
             HIPCHK(c, hipMemsetAsync(G.hits.p, 0, 16, st));
             hipLaunchKernelGGL(k_coarse_tables, dim3(1), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC, (const u32*)S.off.p,
                                c->co_tcap, cb, ust);
-            hipLaunchKernelGGL(k_coarse_probe, dim3((u32)(c->co_occ * c->ncu)), dim3(CO_T), 0, st, (const u64*)S.keys.p,
+            hipLaunchKernelGGL(k_coarse_probe, dim3(grid), dim3(CO_T), 0, st, (const u64*)S.keys.p,
                                (const u32*)S.off.p, (const u32*)cb, (const u32*)ust, (const kr_cand*)c->candB.p,
                                (u32*)c->co_state.p, (u32*)G.hits.p, hitcap, c->co_tcap, (u32)j, is_in[cpos[j]] ? 0u : 4u,
                                g.pmask, g.LRrel);
