@@ -488,6 +488,42 @@ int64_t kr_guides_run(kr_ctx*, const uint8_t* rows, const uint64_t* row_off, con
 /* the records of the latest run, one per region in the order given (KR_ERR_STATE before a run) */
 int64_t kr_guides_fetch(kr_ctx*, kr_guide_record* out, size_t cap);
 
+/* ---- the picked guides searched in every genome (krisp_fasta --out_guide_hits) -----------------------------------------
+ * No seam in the reference.  The specificity pass of the guides: for every genome, every window (the locate pass's window
+ * rules, both strands) that differs from a guide's protospacer in at most M columns, with the columns that differ and
+ * whether the PAM / PFS motifs lie beside it.  DESIGN §19 holds the definition (entries, staging, the column mask's
+ * orientation, the motifs' index rules on both strands, need_pam); tests/guide_hits_reference.py restates it.  It runs in
+ * the locate context (kr_set_params_locate with L+D+R = the protospacer length G: only the sum and the soft-mask mode play
+ * a part; the genome is uploaded by the same entry points, kr_locate_seps lists its records), with a state of its own:
+ * a near-match table of the same context is not disturbed.  On the device it is the near pass's scan itself (k_near_scan
+ * over the guides' table: pigeonhole seeds filter, a byte comparison decides), then csrc/k_guide_hits.inc: a per-hit step
+ * (csrc/ghit_step.inc), a thread per hit, that reads the window and the motifs' neighbours from the genome's bytes, every
+ * index bounds-checked, and under need_pam an order-keeping selection of the hits with both motifs.
+ *
+ * The table: nguides rows of G bytes, each of A, C, G, T, row i = guide i (equal rows stay guides of their own);
+ * 0 <= mismatches <= 3; pam5 / pam3 = the motifs in IUPAC letters (either case, U as T), read 5'->3' on the guide's strand,
+ * at most 8 letters, NULL or "" = none; need_pam != 0: a hit counts only where both motifs match.  Returns the number of
+ * slots of the seed table.  KR_ERR_PARAM for G outside 12 .. 40, mismatches outside 0 .. 3, a text byte other than A, C,
+ * G, T, a motif of more than 8 letters or with a letter outside the IUPAC code, null texts with nguides != 0 (an earlier
+ * table stays as it was); KR_ERR_CAPACITY for 2^24 guides or more, or a table that does not fit. */
+int64_t kr_guide_hits_table(kr_ctx*, const uint8_t* texts, uint64_t nguides, int mismatches, const char* pam5, const char* pam3,
+                            int need_pam);
+/* one hit, 24 bytes: the guide (row of the table), strand 0 = the window as written ('+'), 1 = its reverse complement
+ * ('-'), the number of columns that differ, pam bit 0 = the 5' motif matches and bit 1 = the 3' motif (an empty motif
+ * matches), pos = the window's first base in the uploaded bases (separators counted), columns bit c = guide column c
+ * differs, counted 5'->3' on the protospacer (window column G - 1 - c on '-') */
+typedef struct { uint32_t guide; uint8_t strand, mismatches, pam, pad; uint64_t pos; uint64_t columns; } kr_guide_hit;
+/* scans uploaded genome `id` against the table: returns the number of hits, kept on the device for the fetch, in position
+ * order (at one position: by seed piece, then by the table's entry order; a (guide, strand, pos) occurs once).  Counted,
+ * scanned, written: the same bytes on every run.  No guides, or a genome shorter than G: 0 without a launch.  KR_ERR_PARAM
+ * before a table; KR_ERR_CAPACITY for 2^32 hits or more (counted before need_pam's selection), or hits that do not fit. */
+int64_t kr_guide_hits_scan(kr_ctx*, int id);
+int64_t kr_guide_hits_fetch(kr_ctx*, kr_guide_hit* out, size_t cap);
+/* the hits' windows as text, as kr_near_windows gives the near pass's: row i = the G letters of hit i, upper case, the
+ * reverse complement for strand 1 -- the window as the guide's strand reads it.  Returns the number of rows; rows == NULL:
+ * size query */
+int64_t kr_guide_hits_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

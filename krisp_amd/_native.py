@@ -33,6 +33,8 @@ DESIGN_RECORD = np.dtype([("found", "<u4"), ("product_size", "<u4"), ("pair_pena
 DESIGN_RECORD_HP = np.dtype(DESIGN_RECORD.descr + [("left_hairpin", "<i4"), ("right_hairpin", "<i4")])
 GUIDE_RECORD = np.dtype([("found", "<u4"), ("strand", "<u4"), ("start", "<u4"), ("min_mismatches", "<u4"),
                          ("sum_mismatches", "<u4"), ("gc", "<u4"), ("candidates", "<u4"), ("pad", "<u4")])    # kr_guide_record
+GUIDE_HIT_RAW = np.dtype([("guide", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("pam", "u1"), ("pad", "u1"), ("pos", "<u8"),
+                          ("columns", "<u8")])                                 # kr_guide_hit
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -130,6 +132,10 @@ SYMBOLS = [
     ("kr_guides_table", _c.c_int, [_P, _P]),
     ("kr_guides_run", _c.c_int64, [_P, _P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
     ("kr_guides_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_guide_hits_table", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_char_p, _c.c_char_p, _c.c_int]),
+    ("kr_guide_hits_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_guide_hits_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_guide_hits_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -736,6 +742,34 @@ class Engine:
         out = np.empty((max(n, 1), k), dtype=np.uint8)
         if n:
             self._check(self.lib.kr_near_windows(self.ctx, _ptr(out), out.nbytes), "kr_near_windows")
+        return out[:n]
+
+    def guide_hits_table(self, texts, mismatches, pam5="", pam3="", need_pam=False):
+        """texts: uint8 [n, G] protospacers in A, C, G, T, in a locate context with L+D+R = G; pam5 / pam3: the motifs in
+        IUPAC letters, read 5'->3' on the guide's strand -> slots of the seed table (kr_guide_hits_table)"""
+        t = np.ascontiguousarray(texts, dtype=np.uint8)
+        # (the library reads len(t) rows of L+D+R bytes: another shape would be read past its end)
+        k = sum(self.params) if self.params is not None else None
+        if t.size and (t.ndim != 2 or (k is not None and t.shape[1] != k)):
+            raise ValueError(f"guide_hits_table: texts is a matrix with a row of L+D+R = {k} letters per guide (got shape {t.shape})")
+        as_bytes = lambda m: m if isinstance(m, bytes) else str(m).encode("ascii", "replace")      # noqa: E731
+        return self._check(self.lib.kr_guide_hits_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches, as_bytes(pam5),
+                                                        as_bytes(pam3), 1 if need_pam else 0), "kr_guide_hits_table")
+
+    def guide_hits(self, gid):
+        """GUIDE_HIT_RAW array of uploaded genome gid against the guides' table, in position order (kr_guide_hits_scan)"""
+        n = self._check(self.lib.kr_guide_hits_scan(self.ctx, gid), "kr_guide_hits_scan")
+        out = np.empty(max(n, 1), dtype=GUIDE_HIT_RAW)
+        self._check(self.lib.kr_guide_hits_fetch(self.ctx, _ptr(out), n), "kr_guide_hits_fetch")
+        return out[:n]
+
+    def guide_hit_windows(self, G):
+        """the latest guide_hits()'s windows as the guide's strand reads them, cut on the device: uint8 [nhits, G]
+        (kr_guide_hits_windows)"""
+        n = self._check(self.lib.kr_guide_hits_windows(self.ctx, None, 0), "kr_guide_hits_windows")
+        out = np.empty((max(n, 1), G), dtype=np.uint8)
+        if n:
+            self._check(self.lib.kr_guide_hits_windows(self.ctx, _ptr(out), out.nbytes), "kr_guide_hits_windows")
         return out[:n]
 
     def products_table(self, left, right, pairs, mismatches, max_product):

@@ -229,6 +229,16 @@ struct kr_ctx {
         int gid = -1;                   // the genome of the latest kr_near_scan
         DevBuf arena, table, list, bitmap, hits, rows;
     } near;
+    // the guide-hit pass (kr_guide_hits_*: h_guide_hits.inc), in the locate context with loc.k = the protospacer length:
+    // a state of its own beside the near pass's, loc's scratch
+    struct Ghit {
+        int M = 0;
+        u32 sets5 = 0, a = 0, sets3 = 0, b = 0, need = 0;      // the motifs (GhitMotifs), need_pam
+        u64 nguides = 0, slots = 0;
+        int64_t nhits = -1;
+        int gid = -1;                   // the genome of the latest kr_guide_hits_scan
+        DevBuf arena, table, list, bitmap, pairs, hits, kept, rows;    // pairs: the scan's list; kept: what need_pam leaves (it changes places with hits)
+    } ghit;
     // the product pass (kr_products_*: h_products.inc), in the locate context: loc.L / loc.R are the texts' lengths
     struct Prod {
         int M = 0;
@@ -570,6 +580,9 @@ void kr_destroy(kr_ctx* c) {
         auto& nr = c->near;
         DevBuf* nb[] = {&nr.arena, &nr.table, &nr.list, &nr.bitmap, &nr.hits, &nr.rows};
         for (DevBuf* b : nb) release(c, *b);
+        auto& gh = c->ghit;
+        DevBuf* hb[] = {&gh.arena, &gh.table, &gh.list, &gh.bitmap, &gh.pairs, &gh.hits, &gh.kept, &gh.rows};
+        for (DevBuf* b : hb) release(c, *b);
         auto& pr = c->prod;
         DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.pairkeys, &pr.pairidx, &pr.seps, &pr.sites, &pr.rec, &pr.hits};
         for (DevBuf* b : pb) release(c, *b);

@@ -22,6 +22,8 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     l.nhits = -1;
     c->near.slots = c->near.ntargets = 0;       // (a table of another geometry: kr_near_table again)
     c->near.nhits = -1;
+    c->ghit.slots = c->ghit.nguides = 0;        // (likewise: kr_guide_hits_table again)
+    c->ghit.nhits = -1;
     c->prod.slots = 0;                          // (likewise: kr_products_table again)
     c->prod.nsites = c->prod.nhits = -1;
     c->prim.slots = 0;                          // (another soft-mask mode: kr_primers_table again)

@@ -1818,7 +1818,7 @@ def write_guides(path, templates, records, guide_size, pam5_len=0, pam3_len=0, r
 
 
 # ----------------------------------------------------------------------------
-# the picked guides searched in every genome: the table's texts and the result file; the pass itself is not built
+# the picked guides searched in every genome (--out_guide_hits)
 # ----------------------------------------------------------------------------
 GUIDE_HIT_HEADER = ("region\tfile\trecord\trecord_index\tstart\tend\tstrand\tmismatches\tmismatch_columns\tpam5_match\t"
                     "pam3_match\tsequence")
@@ -1845,6 +1845,83 @@ def guide_texts(templates, records, guide_size, regions=None):
         by_text.setdefault(t.encode("ascii"), []).append(i if regions is None else int(regions[i]))
     texts = sorted(by_text)
     return texts, [sorted(by_text[t]) for t in texts]
+
+
+GUIDE_HIT_MAX_MISMATCHES = 3
+
+
+def guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam):
+    """why the guide-hit pass does not take these figures (one line), or None"""
+    if guide_size < GUIDE_MIN_SIZE or guide_size > GUIDE_MAX_SIZE:
+        return f"--guide-size must lie between {GUIDE_MIN_SIZE} and {GUIDE_MAX_SIZE} (got {guide_size})"
+    if mismatches < 0 or mismatches > GUIDE_HIT_MAX_MISMATCHES:
+        return f"--guide-hit-mismatches must lie between 0 and {GUIDE_HIT_MAX_MISMATCHES} (got {mismatches})"
+    for opt, motif in (("--pam5", pam5), ("--pam3", pam3)):
+        if len(motif) > GUIDE_MAX_MOTIF:
+            return f"{opt} takes at most {GUIDE_MAX_MOTIF} letters (got {motif!r})"
+        try:
+            motif_masks(motif)
+        except ValueError as e:
+            return f"{opt}: {e}"
+    if need_pam and not pam5 and not pam3:
+        return "--guide-hits-need-pam needs a motif: --pam5 or --pam3"
+    return None
+
+
+def guide_hits(texts, text_regions, ingroup_files, outgroup_files, guide_size, mismatches=2, pam5="", pam3="", need_pam=False,
+               omit_soft=False, device=0):
+    """Every window of every input genome within Hamming distance `mismatches` of a picked guide's protospacer, on both
+    strands, wherever it lies: the specificity pass of --out_guides.  texts, text_regions = guide_texts(...):
+    the distinct protospacers and the regions that carry each.  A separate pass over the inputs on one device in the manner
+    of near_matches (kr_guide_hits_*: the near pass's scan, a per-hit step for the column mask and the motifs).  Returns a
+    GUIDE_HIT array: region, file, record, record_index, start, strand as in LOCATION, end = start + guide_size,
+    mismatches, mismatch_columns (the 1-based columns that differ, 5'->3' on the guide), pam5_match / pam3_match = 1 where
+    the motif lies beside the window as read on the guide's strand (an empty motif matches), sequence = the window on the
+    guide's strand.  With need_pam a window counts only where both motifs match.  A hit of a text that several regions
+    share is a row for each of them.  Rows in (region, file in command-line order, record_index, start, '+' before '-')
+    order.  ValueError for figures the pass does not take (guide_hits_refusal)."""
+    why = guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam)
+    if why is not None:
+        raise ValueError(why)
+    if len(texts) != len(text_regions):
+        raise ValueError(f"guide_hits: {len(texts)} texts, the regions of {len(text_regions)}")
+    files = list(ingroup_files) + list(outgroup_files)
+    G = guide_size
+    if len(texts) == 0:
+        return np.empty(0, dtype=GUIDE_HIT)
+    if any(len(t) != G for t in texts):
+        raise ValueError(f"guide_hits: every text has --guide-size = {G} letters")
+    t_bytes = np.frombuffer(b"".join(bytes(t) for t in texts), dtype=np.uint8).reshape(-1, G)
+    # text -> its rows: a hit of text t is a row for each of t's regions
+    n_regions = np.array([len(r) for r in text_regions], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(n_regions)])
+    flat = np.array([r for rs in text_regions for r in rs], dtype=np.uint32)
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, 0, G, 0, G, omit_soft, device,
+                                                   lambda eng: eng.guide_hits_table(t_bytes, mismatches, pam5, pam3, need_pam)):
+        hits = eng.guide_hits(0)
+        if len(hits) == 0:
+            continue
+        rows = eng.guide_hit_windows(G)
+        seps, ids = names()
+        shared = np.empty(len(hits), dtype=GUIDE_HIT)
+        _fill_shared(shared, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        shared["end"] = shared["start"] + G
+        shared["mismatches"] = hits["mismatches"]
+        shared["mismatch_columns"] = [_mask_columns(m) for m in hits["columns"].tolist()]
+        shared["pam5_match"] = hits["pam"] & 1
+        shared["pam3_match"] = (hits["pam"] >> 1) & 1
+        shared["sequence"] = _rows_text(rows, G, rna)
+        # hit h of text t becomes the rows [begin[h], begin[h] + cnt[h]), one per region of t
+        gd = hits["guide"].astype(np.int64)
+        cnt = n_regions[gd]
+        begin = np.cumsum(cnt) - cnt
+        rep = np.repeat(np.arange(len(hits)), cnt)
+        part = shared[rep]
+        part["region"] = flat[first[gd[rep]] + np.arange(len(rep)) - begin[rep]]
+        order = np.lexsort((part["strand"] == "-", part["start"], part["record_index"], part["region"]))
+        parts.append((fi, part[order], part["region"][order]))
+    return _sorted_parts(parts, GUIDE_HIT)
 
 
 def _mask_columns(mask):
@@ -2289,6 +2366,17 @@ def build_parser():
     p.add_argument("--guide-min-mismatches", type=int, default=None, metavar="INT",
                    help="columns in which the protospacer differs from EVERY outgroup sequence of its region at least:\n"
                         "0 .. --guide-size (default: 1)")
+    p.add_argument("--out_guide_hits", type=str, metavar="PATH",
+                   help="Also search every genome for the guides --out_guides picked, and write every window within\n"
+                        "--guide-hit-mismatches substitutions of a protospacer, on both strands, as a tab-separated file: region,\n"
+                        "file, record, record_index, start, end, strand, mismatches, mismatch_columns (1-based, 5'->3' on the\n"
+                        "guide), pam5_match, pam3_match (1: --pam5 / --pam3 lies beside the window), sequence.  A guide's own\n"
+                        "locus in its ingroup genomes is a row with 0 mismatches.  One more pass over the inputs; needs\n"
+                        "--out_guides.  (default: no search)")
+    p.add_argument("--guide-hit-mismatches", type=int, default=None, metavar="INT",
+                   help="Hamming distance of --out_guide_hits: 0 .. 3 (default: 2)")
+    p.add_argument("--guide-hits-need-pam", action="store_true",
+                   help="--out_guide_hits lists a window only where --pam5 and --pam3 lie beside it (needs one of the two)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -2434,6 +2522,20 @@ def main(argv=None):
         if why is not None:
             print("ERROR: " + why, file=sys.stderr)
             sys.exit(2)
+    if args.out_guide_hits is not None and args.out_guides is None:
+        print("ERROR: --out_guide_hits needs --out_guides (the guides it searches for)", file=sys.stderr)
+        sys.exit(2)
+    for opt, val in (("--guide-hit-mismatches", args.guide_hit_mismatches), ("--guide-hits-need-pam", args.guide_hits_need_pam or None)):
+        if val is not None and args.out_guide_hits is None:
+            print(f"ERROR: {opt} needs --out_guide_hits", file=sys.stderr)
+            sys.exit(2)
+    if args.out_guide_hits is not None:
+        if args.guide_hit_mismatches is None:
+            args.guide_hit_mismatches = 2
+        why = guide_hits_refusal(args.guide_size, args.guide_hit_mismatches, args.pam5, args.pam3, args.guide_hits_need_pam)
+        if why is not None:
+            print("ERROR: " + why, file=sys.stderr)
+            sys.exit(2)
     if args.primer3:
         from . import primers
         if not primers.available():
@@ -2551,6 +2653,15 @@ def main(argv=None):
         guides = design_guides(groups, ingroup, args.guide_size, args.pam5, args.pam3, tuple(args.guide_gc),
                                args.guide_min_mismatches, bounds=bounds, device=locate_device, templates=templates)
         write_guides(args.out_guides, templates[0], guides, args.guide_size, len(args.pam5), len(args.pam3), regions=regions)
+        if args.out_guide_hits is not None:
+            # (as the locations: one genome at a time on one device, written by rank 0)
+            if args.verbose:
+                print(f"Searching every genome for the guides with up to {args.guide_hit_mismatches} mismatches ... ", file=sys.stderr)
+            texts, text_regions = guide_texts(templates[0], guides, args.guide_size, regions=regions)
+            write_guide_hits(args.out_guide_hits,
+                             guide_hits(texts, text_regions, args.files, args.outgroup, args.guide_size,
+                                        mismatches=args.guide_hit_mismatches, pam5=args.pam5, pam3=args.pam3,
+                                        need_pam=args.guide_hits_need_pam, omit_soft=args.omit_soft, device=locate_device))
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
