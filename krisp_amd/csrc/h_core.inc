@@ -139,7 +139,7 @@ struct kr_ctx {
     int coarse_rest = 1;        // KR_OPT_COARSE_REST / KR_COARSE_REST env: 1 = kr_genome_partition stops behind pass 1 where the context is
                                 // eligible; 0 = it is kr_genome_sort
     int64_t coarse_done = 0, coarse_promoted = 0;   // genomes kr_intersect took in the coarse state; coarse genomes sorted fine after all
-    DevBuf co_state, co_tab;    // k_coarse_probe: the candidates' state words; cb[257] + ust[257] per genome
+    DevBuf co_state, co_tab;    // k_coarse_probe: the candidates' state words; cb[257], ust[257] and the 256 rows of a call
     u32 co_tcap = CO_TCAP;      // KR_COARSE_TCAP env (tests: several rounds per top byte at small sizes)
     u32 co_hitcap = 0;          // KR_COARSE_HITCAP env (tests: a hit list that overflows; 0 = sized from the candidate list)
     int co_occ = 0;             // resident k_coarse_probe workgroups per CU (occupancy query, cached)

@@ -74,7 +74,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     // (a hit list holds the genome's keys under ANY candidate of C: at the reference's divergences about 0.8 per candidate)
     const u32 hitcap = c->co_hitcap ? c->co_hitcap : (u32)std::min<u64>(2ull * nC + 65536, 0x7FFFFFF0ull);
     if ((rc = ensure(c, c->co_state, (size_t)nC * 4))) return rc;
-    if ((rc = ensure(c, c->co_tab, (size_t)(1 + cg.size()) * 260 * 4))) return rc;
+    if ((rc = ensure(c, c->co_tab, (size_t)(2 * 260 + 256 * CO_ROW) * 4))) return rc;
     if ((rc = ensure(c, c->flags, (size_t)nC * 4))) return rc;
     if ((rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4))) return rc;
     if ((rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4))) return rc;
@@ -94,26 +94,29 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     const u32 grid = c->co_grid ? c->co_grid : (u32)(c->co_occ * c->ncu);
     if ((rc = join_lanes(c))) return rc;                // (the partitions ran on the sort lanes)
     HIPCHK(c, hipMemsetAsync(c->co_state.p, 0, (size_t)nC * 4, st));
-    u32* cb = (u32*)c->co_tab.p;
+    u32 *cb = (u32*)c->co_tab.p, *ust = cb + 260, *rows = cb + 520;
     u32 need = 0;
     CoarsePub pub{};
     pub.n = (int)cg.size();
+    CoarseArgs ca{};
+    ca.n = (u32)cg.size();
+    for (size_t j = 0; j < cg.size(); j++) {
+        Genome& G = *cg[j];
+        ca.keys[j] = (const u64*)G.sl[0].keys.p;
+        ca.off[j] = (const u32*)G.sl[0].off.p;
+        ca.hits[j] = (u32*)G.hits.p;
+        ca.hitcap[j] = hitcap;
+        ca.bit[j] = 8u + (u32)j;
+        ca.side[j] = is_in[cpos[j]] ? 0u : 4u;
+        need |= 1u << (8 + j);
+        pub.cnt[j] = (const u32*)G.hits.p;
+    }
     {
+        // one launch each for all coarse genomes of the call (k_coarse_tables also clears their hit counts)
         StageScope sc(c, KR_ST_INTERSECT, st);
-        for (size_t j = 0; j < cg.size(); j++) {
-            Genome& G = *cg[j];
-            Slice& S = G.sl[0];
-            u32* ust = cb + 260 * (j + 1);
-            HIPCHK(c, hipMemsetAsync(G.hits.p, 0, 16, st));
-            hipLaunchKernelGGL(k_coarse_tables, dim3(1), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC, (const u32*)S.off.p,
-                               c->co_tcap, cb, ust);
-            hipLaunchKernelGGL(k_coarse_probe, dim3(grid), dim3(CO_T), 0, st, (const u64*)S.keys.p,
-                               (const u32*)S.off.p, (const u32*)cb, (const u32*)ust, (const kr_cand*)c->candB.p,
-                               (u32*)c->co_state.p, (u32*)G.hits.p, hitcap, c->co_tcap, (u32)j, is_in[cpos[j]] ? 0u : 4u,
-                               g.pmask, g.LRrel);
-            need |= 1u << (8 + j);
-            pub.cnt[j] = (const u32*)G.hits.p;
-        }
+        hipLaunchKernelGGL(k_coarse_tables, dim3(1), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC, ca, c->co_tcap, cb, ust, rows);
+        hipLaunchKernelGGL(k_coarse_probe, dim3(grid), dim3(CO_T), 0, st, ca, (const u32*)cb, (const u32*)ust, (const u32*)rows,
+                           (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel);
     }
     {
         StageScope sc(c, KR_ST_MERGE, st);

@@ -7,18 +7,32 @@
 // presence bit and its diagnostic base into the candidate's state word and joins the genome's hit list -- all that
 // kr_collect will ask of this genome.  Exact: a slot's 19-bit tag only gates the look at the candidate's full prefix.
 
-#define CO_T 1024               // threads of k_coarse_probe: two workgroups per CU (8 waves per SIMD, <= 64 VGPRs, 2 x 68 KB LDS)
+#include "co_units.inc"        // CO_CHUNK, the numbering of the work units and its decode (shared with a host check)
+
+#define CO_T 1024               // threads of k_coarse_probe: two workgroups per CU (8 waves per SIMD, <= 64 VGPRs, 2 x 75 KB LDS)
 #define CO_SLOT_LOG 13
 #define CO_SLOTS (1u << CO_SLOT_LOG)    // LDS slots: idx << 19 | tag, CO_EMPTY = free
 #define CO_BM_LOG 17            // bits of the prefilter in front of the table: 2^17
-#define CO_QCAP 1024            // keys of one iteration that passed the prefilter (more: looked up in place)
+#define CO_QCAP 2048            // keys of one unit that passed the prefilter (more: the unit is looked up in place)
 #define CO_TCAP 6144            // candidates one table takes (three quarters of the slots; idx << 19 | tag never equals CO_EMPTY);
                                 // a top byte with more of them is streamed once per CO_TCAP candidates ("rounds")
-#define CO_CHUNK 32768u         // keys of one work unit (even: a unit's 16-byte loads keep the parity of the bucket's base)
 #define CO_EMPTY 0xFFFFFFFFu
-#define CO_UNROLL 4             // 16-byte loads a thread has in flight: 8192 keys per iteration of a workgroup
+#define CO_UNROLL 4             // 16-byte loads of one register set: 8192 keys per iteration of a workgroup; two sets (A / B)
+#define CO_ITER (2u * CO_T * CO_UNROLL)
 #define CO_HB 1024              // hits a workgroup gathers in LDS before it takes room in the genome's list (one global atomic per unit)
 #define CO_MAXG 24              // genomes of a call on this route: 8 bits of diagnostic sets + 24 presence bits in one state word
+#define CO_ROW (2 * CO_MAXG)    // words of a top byte's row: every genome's bucket [b0, b1) (co_units.inc)
+
+// the coarse genomes of one call, one launch for all of them
+struct CoarseArgs {
+    const u64* keys[CO_MAXG];   // pass 1's output
+    const u32* off[CO_MAXG];    // its 257 bucket offsets
+    u32* hits[CO_MAXG];         // hit list: u32 count at word 0, keys from byte 16
+    u32 hitcap[CO_MAXG];
+    u32 bit[CO_MAXG];           // the genome's presence bit in the state word
+    u32 side[CO_MAXG];          // 0: ingroup, 4: outgroup -- where its diagnostic bases go in the state word
+    u32 n;
+};
 
 // state word of a candidate: bits 0..3 the bases its column shows in coarse ingroup genomes, 4..7 in coarse outgroup
 // genomes, bit 8 + j: coarse genome j holds the prefix
@@ -27,10 +41,10 @@ __device__ __forceinline__ u32 co_hash(u64 pre) {
     return ((u32)(pre >> 32) ^ y) * 0x85EBCA6Bu;
 }
 
-// cb[t] = first candidate whose prefix has a top byte >= t (t = 0 .. 256), and the work units of one genome:
-// ust[t] = units in front of top byte t; a top byte has rounds x chunks units, the chunk varying fastest
-__global__ __launch_bounds__(256) void k_coarse_tables(const kr_cand* __restrict__ cands, u32 n, const u32* __restrict__ base,
-                                                       u32 tcap, u32* __restrict__ cb, u32* __restrict__ ust) {
+// cb[t] = first candidate whose prefix has a top byte >= t (t = 0 .. 256); rows[t] = the buckets of top byte t in every
+// genome; ust[t] = units in front of top byte t (co_units.inc).  Also clears the genomes' hit counts.
+__global__ __launch_bounds__(256) void k_coarse_tables(const kr_cand* __restrict__ cands, u32 n, CoarseArgs A, u32 tcap,
+                                                       u32* __restrict__ cb, u32* __restrict__ ust, u32* rows) {
     __shared__ u32 waves[17];
     __shared__ u32 s_cb[257];
     for (u32 t = threadIdx.x; t <= 256; t += 256) {
@@ -48,8 +62,13 @@ __global__ __launch_bounds__(256) void k_coarse_tables(const kr_cand* __restrict
     }
     __syncthreads();
     const u32 t = threadIdx.x;
-    const u32 nc = s_cb[t + 1] - s_cb[t], len = base[t + 1] - base[t];
-    const u32 units = ((nc + tcap - 1) / tcap) * ((len + CO_CHUNK - 1) / CO_CHUNK);
+    if (t < 4 * A.n) A.hits[t >> 2][t & 3u] = 0;
+    u32* row = rows + t * CO_ROW;
+    for (u32 j = 0; j < A.n; j++) {
+        row[2 * j] = A.off[j][t];
+        row[2 * j + 1] = A.off[j][t + 1];
+    }
+    const u32 units = co_byte_units(s_cb[t + 1] - s_cb[t], tcap, row, A.n);
     u32 total;
     const u32 ex = block_excl_scan(units, waves, total);
     ust[t] = ex;
@@ -85,45 +104,74 @@ __device__ __forceinline__ void co_lookup(u64 key, u64 pmask, int LR, const u32*
     }
 }
 
-// persistent: workgroup w takes the units [w U / W, (w + 1) U / W) -- neighbours in a top byte, so a table is built once
-// per workgroup and top byte (twice at the seams).  hits: u32 count at word 0, keys from byte 16; the count runs on past
-// `hitcap` (nothing is written there): the host reads it and sorts the genome fine instead.
+// one register set: the iteration at p0 of the unit [.., k1) whose first aligned key is a0.  Clamped into the unit, never
+// predicated: the loads of a thread stay in flight together, and none reads behind the unit's (16-byte rounded) end --
+// key a0 may lie in front of the unit, key k1 behind it: both inside the array, which has two keys of slack
+__device__ __forceinline__ void co_load(u32x4 (&v)[CO_UNROLL], const u64* __restrict__ keys, u32 p0, u32 a0, u32 k1) {
+#pragma unroll
+    for (int q = 0; q < CO_UNROLL; q++) {
+        const u32 p = p0 + 2 * (q * CO_T + threadIdx.x);
+        const u32 pc = p < k1 ? p : a0;
+        v[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(keys + pc));
+    }
+}
+
+#define CO_RFL(x) ((u32)__builtin_amdgcn_readfirstlane((int)(x)))
+
+// persistent: workgroup w takes the units [w U / W, (w + 1) U / W) of ALL coarse genomes of the call (co_units.inc: top
+// byte -> round -> genome -> chunk) -- neighbours in a (top byte, round), so a table is built once per workgroup and
+// round (twice at the seams) and every genome's keys of the byte stream past it.  hits: the count runs on past `hitcap`
+// (nothing is written there): the host reads it and sorts the genomes fine instead.
 //
-// Two phases per iteration (2 CO_T CO_UNROLL keys).  About 1 % of the keys hit, so nearly every wave holds a hit: a look-up inside the stream
-// would run its dependent chain (slot, tag, the candidate's prefix in global memory) in every wave for one lane's sake.
-// Phase 1 only tests a bit of a 2^17-bit prefilter in LDS (set by the candidates' hashes: 3-7 % of the keys pass) and
-// queues what passes; phase 2 looks the queued keys up, a thread per key, densely.  A unit's hits gather in LDS and take
-// their room in the list with ONE atomic per unit (an atomic per hit wave on the single count word ran at that word's
-// ~90 atomics per microsecond: 7.7 ms per genome).
-__global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(const u64* __restrict__ keys, const u32* __restrict__ base,
-                                                       const u32* __restrict__ cb, const u32* __restrict__ ust,
-                                                       const kr_cand* __restrict__ cands, u32* __restrict__ state,
-                                                       u32* __restrict__ hits, u32 hitcap, u32 tcap, u32 gbit, u32 side_shift,
-                                                       u64 pmask, int LR) {
+// The key stream is software-pipelined over two register sets: the loads of the NEXT iteration -- of this unit, or the
+// first of the workgroup's next unit while it lies in the same top byte (its genome's bucket is in the row in LDS) -- are
+// issued before phase 1 of this one, so 64 KB per workgroup are in flight while it computes.  A new top byte starts cold:
+// its row and its table are fetched first anyway.
+//
+// Phase 1 (per iteration) only tests a bit of a 2^17-bit prefilter in LDS (set by the candidates' hashes: 3-7 % of the
+// keys pass) and queues what passes: a ballot per wave and key slot, one LDS atomic by one lane, a lane's place from the
+// lanes below it.  Phase 2 (per UNIT: its barriers and its dependent global reads would drain the prefetch) looks the
+// queued keys up, a thread per key, densely; a unit that overran the queue is read again and looked up in place.  A unit's hits gather
+// in LDS and take their room in the genome's list with ONE atomic per unit.
+__global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u32* __restrict__ cb, const u32* __restrict__ ust,
+                                                       const u32* __restrict__ rows, const kr_cand* __restrict__ cands,
+                                                       u32* __restrict__ state, u32 tcap, u64 pmask, int LR) {
     __shared__ u32 slots[CO_SLOTS];
     __shared__ u32 bitmap[1u << (CO_BM_LOG - 5)];
-    __shared__ u32 s_base[257], s_cb[257], s_ust[257];
+    __shared__ u32 s_ust[257];
+    __shared__ u32 s_bnd[CO_ROW];
     __shared__ u64 s_q[CO_QCAP];
     __shared__ u64 s_hit[CO_HB];
     __shared__ u32 s_nhit, s_hbase, s_qn;
     if (threadIdx.x == 0) { s_nhit = 0; s_qn = 0; }
-    for (u32 t = threadIdx.x; t <= 256; t += CO_T) { s_base[t] = base[t]; s_cb[t] = cb[t]; s_ust[t] = ust[t]; }
+    for (u32 t = threadIdx.x; t <= 256; t += CO_T) s_ust[t] = ust[t];
     __syncthreads();
+    const u32 G = A.n;
     const u32 U = s_ust[256];
     const u32 u0 = (u32)(((u64)blockIdx.x * U) / gridDim.x), u1 = (u32)(((u64)(blockIdx.x + 1) * U) / gridDim.x);
-    u64* __restrict__ hitkeys = (u64*)(hits + 4);
-    const u32 orbits = 1u << (8 + gbit);
-    u32 cur_t = ~0u, cur_r = ~0u, c0 = 0;
-    for (u32 u = u0; u < u1; u++) {
-        u32 lo = 0, hi = 256;                            // largest t with ust[t] <= u and units of its own
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (s_ust[mid] <= u) lo = mid; else hi = mid;
-        }
-        const u32 t = lo;
-        const u32 b0 = s_base[t], b1 = s_base[t + 1];
-        const u32 chunks = (b1 - b0 + CO_CHUNK - 1) / CO_CHUNK;
-        const u32 r = (u - s_ust[t]) / chunks, ch = (u - s_ust[t]) - r * chunks;
+    if (u0 >= u1) return;
+    const u32 lane = threadIdx.x & 63u;
+    // the unit at hand and its genome (all wave-uniform)
+    u32 u = u0, t = 0, ust_t = 0, ust_t1 = 0, k0 = 0, k1 = 0, p0 = 0, c0 = 0;
+    u32 cur_t = ~0u, cur_r = ~0u;
+    const u64* __restrict__ kp = nullptr;
+    u32* __restrict__ hits = nullptr;
+    u64* __restrict__ hitkeys = nullptr;
+    u32 hitcap = 0, orbits = 0, side_shift = 0;
+    bool cold = true;                                    // no load of the iteration at hand has been issued
+
+    // unit `un` of top byte t becomes the unit at hand; its round's table is built unless it stands
+    auto adopt = [&](const CoUnit& un) {
+        const u32 g = un.genome, r = un.round;
+        k0 = un.k0;
+        k1 = un.k1;
+        p0 = k0 & ~1u;
+        kp = A.keys[g];
+        hits = A.hits[g];
+        hitkeys = (u64*)(hits + 4);
+        hitcap = A.hitcap[g];
+        orbits = 1u << A.bit[g];
+        side_shift = A.side[g];
         if (t != cur_t || r != cur_r) {
             cur_t = t;
             cur_r = r;
@@ -131,8 +179,9 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(const u64* __restrict_
             for (u32 i = threadIdx.x; i < CO_SLOTS; i += CO_T) slots[i] = CO_EMPTY;
             for (u32 i = threadIdx.x; i < (1u << (CO_BM_LOG - 5)); i += CO_T) bitmap[i] = 0;
             __syncthreads();
-            c0 = s_cb[t] + r * tcap;
-            const u32 c1 = min(s_cb[t + 1], c0 + tcap);
+            const u32 cb0 = cb[t], cb1 = cb[t + 1];
+            c0 = cb0 + r * tcap;
+            const u32 c1 = cb1 - c0 > tcap ? c0 + tcap : cb1;
             for (u32 i = c0 + threadIdx.x; i < c1; i += CO_T) {
                 const u32 h = co_hash(cands[i].prefix);
                 const u32 word = ((i - c0) << 19) | (h & 0x7FFFFu);
@@ -142,55 +191,124 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(const u64* __restrict_
             }
             __syncthreads();
         }
-        const u32 k0 = b0 + ch * CO_CHUNK, k1 = min(b1, k0 + CO_CHUNK);
-        const u32 a0 = k0 & ~1u;                         // (16-byte aligned; key a0 may lie in front of the unit, key k1 behind it:
-                                                         //  both inside the array, which has two keys of slack, and masked below)
-        for (u32 p0 = a0; p0 < k1; p0 += 2 * CO_T * CO_UNROLL) {
-            u32x4 v[CO_UNROLL];
-            u32 at[CO_UNROLL];
-#pragma unroll
-            for (int q = 0; q < CO_UNROLL; q++) {
-                const u32 p = p0 + 2 * (q * CO_T + threadIdx.x);
-                at[q] = p;
-                const u32 pc = p < k1 ? p : a0;          // (clamped, never predicated: the loads of a thread stay in flight together)
-                v[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(keys + pc));
+    };
+    auto uniform = [](CoUnit un) {
+        un.round = CO_RFL(un.round); un.genome = CO_RFL(un.genome); un.chunk = CO_RFL(un.chunk);
+        un.k0 = CO_RFL(un.k0); un.k1 = CO_RFL(un.k1);
+        return un;
+    };
+    // unit u lies in another top byte than the one before: its row into LDS (every thread is behind a barrier since it
+    // last read the row)
+    auto new_byte = [&]() {
+        t = CO_RFL(co_unit_byte(s_ust, u));
+        ust_t = CO_RFL(s_ust[t]);
+        ust_t1 = CO_RFL(s_ust[t + 1]);
+        if (threadIdx.x < 2 * G) s_bnd[threadIdx.x] = rows[t * CO_ROW + threadIdx.x];
+        __syncthreads();
+        adopt(uniform(co_unit_decode(u - ust_t, s_bnd, G)));
+    };
+
+    // one iteration: V holds its keys (or takes them first: `cold`); NV takes the next one's.  -> the workgroup is done.
+    // Every step issues the same loads at the same place and has no other global access before the unit's end, so the
+    // compiler's counted waits leave the newer set in flight (k_sort2.inc, the comment at its head).
+    auto step = [&](u32x4 (&V)[CO_UNROLL], u32x4 (&NV)[CO_UNROLL]) -> bool {
+        const bool last = k1 - p0 <= CO_ITER;
+        // what NV takes: this unit's next iteration; behind its last one the first of the next unit, while that lies in
+        // the same top byte; else one key pair of this unit for every thread (k1 = 0 clamps all of them to a0)
+        bool ahead = false;
+        CoUnit un = {};
+        const u64* __restrict__ nkp = kp;
+        u32 np0 = p0 + CO_ITER, na0 = k0 & ~1u, nk1 = k1;
+        if (last) {
+            np0 = na0;
+            nk1 = 0;
+            if (u + 1 < u1 && u + 1 < ust_t1) {
+                un = uniform(co_unit_decode(u + 1 - ust_t, s_bnd, G));
+                nkp = A.keys[un.genome];
+                np0 = na0 = un.k0 & ~1u;
+                nk1 = un.k1;
+                ahead = true;
             }
-            // phase 1
+        }
+        if (cold) co_load(V, kp, p0, p0, k1);
+        cold = false;
+        co_load(NV, nkp, np0, na0, nk1);
+        __builtin_amdgcn_sched_barrier(0);               // (issued here, before anything of this iteration)
+        // phase 1
+        const int hi = (int)(k1 - p0) - 2 * (int)threadIdx.x;       // this thread's key slots below `hi` lie in front of k1
+        const bool front = p0 < k0 && threadIdx.x == 0;            // ... and its first one in front of k0 (an odd k0: key a0)
 #pragma unroll
-            for (int q = 0; q < CO_UNROLL; q++) {
+        for (int q = 0; q < CO_UNROLL; q++) {
 #pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    const u64 key = e ? ((u64)v[q].w << 32 | v[q].z) : ((u64)v[q].y << 32 | v[q].x);
-                    const u32 idx = at[q] + e;
-                    const u32 h = co_hash(key & pmask);
-                    const u32 bw = bitmap[h >> (37 - CO_BM_LOG)];
-                    if (idx >= k0 && idx < k1 && ((bw >> ((h >> (32 - CO_BM_LOG)) & 31u)) & 1u)) {
-                        const u32 qa = atomicAdd(&s_qn, 1u);
-                        if (qa < CO_QCAP) s_q[qa] = key;
-                        else co_lookup(key, pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap);
-                    }
+            for (int e = 0; e < 2; e++) {
+                const u64 key = e ? ((u64)V[q].w << 32 | V[q].z) : ((u64)V[q].y << 32 | V[q].x);
+                const u32 h = co_hash(key & pmask);
+                const u32 bw = bitmap[h >> (37 - CO_BM_LOG)];
+                // (no branch around the use of a loaded key: the counted waits must be met on every path)
+                const u32 inr = (u32)(2 * q * (int)CO_T + e < hi) & (u32)!(q == 0 && e == 0 && front);
+                const bool mine = ((bw >> ((h >> (32 - CO_BM_LOG)) & 31u)) & inr) != 0;
+                const u64 bal = __builtin_amdgcn_ballot_w64(mine);
+                if (bal) {                               // (wave-uniform; all 64 lanes are here)
+                    u32 qb = 0;
+                    if (lane == 0) qb = atomicAdd(&s_qn, (u32)__popcll(bal));
+                    qb = CO_RFL(qb);
+                    const u32 qa = qb + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
+                    if (mine && qa < CO_QCAP) s_q[qa] = key;         // (a key that finds the queue full: see below)
                 }
             }
-            // phase 2
-            __syncthreads();
-            const u32 qn = min(s_qn, (u32)CO_QCAP);
-            __syncthreads();                             // (every thread has read the count)
-            if (threadIdx.x == 0) s_qn = 0;
+        }
+        if (!last) { p0 += CO_ITER; return false; }
+        // phase 2: the unit's queue
+        __syncthreads();
+        if (s_qn <= CO_QCAP) {
+            const u32 qn = s_qn;
             for (u32 i = threadIdx.x; i < qn; i += CO_T)
                 co_lookup(s_q[i], pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap);
-            __syncthreads();                             // (the queue is free, its count is zero)
+        } else {
+            // more keys passed the prefilter than the queue holds, and some were dropped (nothing of the unit has been
+            // looked up yet): the queue is discarded and the unit's keys are read again and looked up in place -- exact
+            // under any input, and slow only where the prefilter does not filter
+            const u32 a0 = k0 & ~1u;
+            for (u32 p = a0 + 2 * threadIdx.x; p < k1; p += 2 * CO_T) {
+                const u32x4 w = *reinterpret_cast<const u32x4*>(kp + p);
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    const u64 key = e ? ((u64)w.w << 32 | w.z) : ((u64)w.y << 32 | w.x);
+                    const u32 h = co_hash(key & pmask);
+                    if (p + e >= k0 && p + e < k1 && ((bitmap[h >> (37 - CO_BM_LOG)] >> ((h >> (32 - CO_BM_LOG)) & 31u)) & 1u))
+                        co_lookup(key, pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap);
+                }
+            }
         }
-        // the unit's hits from LDS into the list
+        __syncthreads();                                 // (the look-ups are done: the unit's hits are counted)
         const u32 m = min(s_nhit, (u32)CO_HB);
-        __syncthreads();                                 // (every thread has read the count: it is the same in all of them)
-        if (m) {
-            if (threadIdx.x == 0) { s_hbase = atomicAdd(hits, m); s_nhit = 0; }
+        __syncthreads();                                 // (every thread has read both counts: they are the same in all of them)
+        if (threadIdx.x == 0) {
+            s_qn = 0;
+            s_nhit = 0;
+            if (m) s_hbase = atomicAdd(hits, m);
+        }
+        if (m) {                                         // the unit's hits from LDS into its genome's list
             __syncthreads();
             const u32 hb = s_hbase;
             for (u32 i = threadIdx.x; i < m; i += CO_T)
                 if (hb + i < hitcap) hitkeys[hb + i] = s_hit[i];
-            __syncthreads();                             // (the next unit's hits come behind the copy and the reset)
         }
+        __syncthreads();                                 // (queue and hit buffer are free, their counts zero)
+        if (++u >= u1) return true;
+        if (ahead) adopt(un);
+        else {
+            new_byte();
+            cold = true;
+        }
+        return false;
+    };
+
+    u32x4 va[CO_UNROLL], vb[CO_UNROLL];
+    new_byte();
+    for (;;) {
+        if (step(va, vb)) break;
+        if (step(vb, va)) break;
     }
 }
 
