@@ -650,6 +650,9 @@ enum { KR_OPT_SLICE_BASES = 1,       /* -1 automatic; 0..4: sort every genome in
        KR_OPT_LAZY_ORDER = 10,       /* 1 (default): kr_genome_sort stops at the fine buckets, the LDS sort runs where a reader needs
                                         the order (see kr_genome_sort); 0: every sort ends with it (rounds 1-5) */
        KR_OPT_COARSE_REST = 11,      /* 1 (default; KR_COARSE_REST in the environment): kr_genome_partition stops behind pass 1; 0: it is the full sort */
+       KR_OPT_COARSE_POOL = 12,      /* 1 (default; KR_COARSE_POOL in the environment): a genome that kr_genome_partition takes again and again
+                                        writes its pass 1 into a buffer the placement search chose (a pool of them, made behind the
+                                        kr_intersect that sees such a genome for the second time; the gates of KR_OPT_PLACE_TRIES); 0: always into its own key array */
        KR_OPT_WIDE_ORDERED = 6 };    /* wide path: 0 (default) flanks of >= 20 bases are numbered through minimizer buckets (look-ups
                                         of neighbouring windows share memory sectors): the same groups and hits, but `cand` no longer
                                         ascends with (left, right); 1: order-preserving ranks, groups in the reference's order */
@@ -704,6 +707,10 @@ int     kr_debug_isect(kr_ctx*, int64_t* out8);
  * [2..5] probe milliseconds of the four fastest candidates, [6] the median, [7] the slowest (bench.py prints them: which
  * placement class a line ran in) */
 int     kr_debug_place(kr_ctx*, double* out8);
+/* the pool of placed pass-1 targets of coarse genomes (KR_OPT_COARSE_POOL): out8[0] buffers in all, [1] free, [2] held by genomes,
+ * [3] partitions that wrote into a pooled buffer, [4] searches run, [5] / [6] the fastest / slowest probe milliseconds among the
+ * buffers held, [7] the option's value */
+int     kr_debug_coarse_pool(kr_ctx*, double* out8);
 /* what the multi-GPU exchange has cost this context so far: out[0] host synchronisations, [1] point-to-point calls,
  * [2] collectives, [3] microseconds inside kr_cands_reduce / kr_cands_bcast, [4] kr_cands_reduce calls, [5] entries of the
  * agreed message size */

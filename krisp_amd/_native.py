@@ -46,6 +46,7 @@ OPT_ISECT_KERNEL = 8
 OPT_LANES = 9
 OPT_LAZY_ORDER = 10
 OPT_COARSE_REST = 11
+OPT_COARSE_POOL = 12
 ERR_KEY, ERR_HOST = -5, -6
 STRANDS_BOTH, STRANDS_FORWARD, STRANDS_CANONICAL = 0, 1, 2
 STAGES = ["pack", "hist8", "reduce8", "scatter1", "hist2", "scan2", "scatter2", "chunks", "localsort",
@@ -166,6 +167,7 @@ SYMBOLS = [
     ("kr_mem_info", _c.c_int, [_P, _P]),
     ("kr_debug_comm", _c.c_int, [_P, _P]),
     ("kr_debug_place", _c.c_int, [_P, _P]),
+    ("kr_debug_coarse_pool", _c.c_int, [_P, _P]),
     ("kr_debug_comm_probe", _c.c_int, [_P, _c.c_size_t, _c.c_int, _P]),
     ("kr_debug_cands_selfexchange", _c.c_int64, [_P, _c.c_int]),
     ("kr_debug_info", _c.c_int, [_P, _P]),
@@ -961,6 +963,13 @@ class Engine:
         self._check(self.lib.kr_debug_place(self.ctx, _ptr(o)), "kr_debug_place")
         return dict(candidates=int(o[0]), taken=int(o[1]), fastest_ms=[round(float(x), 4) for x in o[2:6]],
                     median_ms=round(float(o[6]), 4), slowest_ms=round(float(o[7]), 4))
+
+    def debug_coarse_pool(self):
+        """the pool of placed pass-1 targets of coarse genomes (kr_debug_coarse_pool)"""
+        o = np.zeros(8, dtype=np.float64)
+        self._check(self.lib.kr_debug_coarse_pool(self.ctx, _ptr(o)), "kr_debug_coarse_pool")
+        return dict(total=int(o[0]), free=int(o[1]), held=int(o[2]), partitions=int(o[3]), searches=int(o[4]),
+                    held_ms=[round(float(o[5]), 4), round(float(o[6]), 4)], on=int(o[7]))
 
     def comm_set_timeout(self, seconds):
         """the exchange's deadline: the watchdog aborts the communicator `seconds` after an exchange call began (kr_comm_set_timeout)"""

@@ -31,6 +31,13 @@ struct Genome {
     bool coarse = false;     // kr_genome_partition: the sort stopped behind pass 1 -- sl[0].keys holds the keys in 256 buckets by their top byte,
                              // sl[0].off[0 .. 256] the buckets' bases, sl[0].off[2^b] the key count; `sorted` is false: whoever needs the fine
                              // buckets calls ensure_fine() first.  kr_intersect takes such a genome by k_coarse_probe (h_intersect.inc)
+    DevBuf ckeys;            // ... out of this array when the genome holds one: a pass-1 target of the context's pool of PLACED
+                             // buffers (coarse_pool_*); without one pass 1 writes sl[0].keys, which no placement search chose
+    double ckeys_ms = 0;     // ... its probe time
+    hipStream_t ckeys_busy = nullptr;  // ... the stream of the last kernel that touched it, until the host has waited for that stream
+    hipEvent_t ckeys_ev = nullptr;     // ... recorded behind that kernel when the buffer changes hands (coarse_pool_handover)
+    bool ckeys_wait = false;           // ... and not waited for yet: whoever writes the buffer next waits for it first
+    int64_t partitions = 0;  // coarse sorts of this genome in this context (the pool grows for genomes that come back)
     DevBuf hits;             // ... and leaves its keys under the candidates' prefixes here (u32 count, keys from byte 16) for kr_collect
     u32 hitcap = 0;
     bool hits_valid = false; // `hits` belongs to the context's current candidate list (or to a list the current one is a part of)
@@ -139,6 +146,14 @@ struct kr_ctx {
     int coarse_rest = 1;        // KR_OPT_COARSE_REST / KR_COARSE_REST env: 1 = kr_genome_partition stops behind pass 1 where the context is
                                 // eligible; 0 = it is kr_genome_sort
     int64_t coarse_done = 0, coarse_promoted = 0;   // genomes kr_intersect took in the coarse state; coarse genomes sorted fine after all
+    int coarse_pool = 1;        // KR_OPT_COARSE_POOL / KR_COARSE_POOL env: 1 = coarse genomes that are partitioned again and again write
+                                // their pass 1 into placed buffers (coarse_pool_grow); 0 = always into their own key arrays
+    struct PoolBuf { DevBuf buf; double ms; hipEvent_t ev; bool wait; };
+    std::vector<PoolBuf> cpool_free;    // placed pass-1 targets nobody holds, the fastest first
+    int cpool_total = 0;                // ... and in all: free + held by genomes (Genome.ckeys)
+    int64_t cpool_partitions = 0;       // coarse sorts that wrote into a pooled buffer
+    int64_t cpool_searches = 0;         // placement searches the pool has run
+    size_t place_min_bytes = (size_t)256 << 20;     // KR_PLACE_MIN_BYTES env (tests): buffers below this size are taken as allocated
     DevBuf co_state, co_tab;    // k_coarse_probe: the candidates' state words; cb[257], ust[257] and the 256 rows of a call
     u32 co_tcap = CO_TCAP;      // KR_COARSE_TCAP env (tests: several rounds per top byte at small sizes)
     u32 co_hitcap = 0;          // KR_COARSE_HITCAP env (tests: a hit list that overflows; 0 = sized from the candidate list)
@@ -362,7 +377,74 @@ static int mbox_slot(kr_ctx* c) {
     return c->mb_next++;
 }
 
+// The pool of placed pass-1 targets for coarse genomes (coarse_pool_grow, behind ensure_placed, makes them).  A buffer is
+// either in the free list or held by one genome (Genome.ckeys).  A genome that leaves the coarse state gives its buffer
+// back; the buffers are freed with the context or its parameters.
+// The hazard between owners: a buffer carries an event behind the last kernel that touched it -- the pass 1 that wrote
+// it, the probe that read it -- and the lane that writes it next waits for that event.  The event is recorded where the
+// buffer changes hands (a return, a sort on another stream), not behind every kernel: in the steady state -- the same
+// genome on the same buffer step after step, kr_intersect's closing synchronisation behind every probe -- no event call
+// is made at all (an event behind each pass 1 and each probe, and a wait in front of each pass 1, cost a one-lane step
+// 45 us of idle device between its kernels: profiles/r13/README.md).
+static void coarse_pool_handover(kr_ctx* c, Genome& G) {
+    if (!G.ckeys.p || !G.ckeys_busy) return;
+    if (!G.ckeys_ev && hipEventCreateWithFlags(&G.ckeys_ev, hipEventDisableTiming) != hipSuccess) G.ckeys_ev = nullptr;
+    if (G.ckeys_ev && hipEventRecord(G.ckeys_ev, G.ckeys_busy) == hipSuccess) G.ckeys_wait = true;
+    else (void)hipStreamSynchronize(G.ckeys_busy);          // (no event to be had: the host waits instead)
+    G.ckeys_busy = nullptr;
+    (void)c;
+}
+static void coarse_pool_return(kr_ctx* c, Genome& G) {
+    if (!G.ckeys.p) return;
+    coarse_pool_handover(c, G);
+    kr_ctx::PoolBuf pb{G.ckeys, G.ckeys_ms, G.ckeys_ev, G.ckeys_wait};
+    auto at = c->cpool_free.begin();
+    while (at != c->cpool_free.end() && at->ms <= pb.ms) ++at;
+    c->cpool_free.insert(at, pb);
+    G.ckeys = DevBuf();
+    G.ckeys_ms = 0;
+    G.ckeys_ev = nullptr;
+    G.ckeys_wait = false;
+}
+// free buffers shorter than `bytes` (the lanes' scratch has grown since they were made) leave the pool
+static void coarse_pool_purge(kr_ctx* c, size_t bytes) {
+    for (size_t i = c->cpool_free.size(); i-- > 0;) {
+        kr_ctx::PoolBuf& pb = c->cpool_free[i];
+        if (pb.buf.bytes >= bytes) continue;
+        if (pb.ev) { if (pb.wait) (void)hipEventSynchronize(pb.ev); (void)hipEventDestroy(pb.ev); }
+        release(c, pb.buf);
+        c->cpool_free.erase(c->cpool_free.begin() + (long)i);
+        c->cpool_total--;
+    }
+}
+// the fastest free buffer of at least `bytes`, if there is one
+static bool coarse_pool_take(kr_ctx* c, Genome& G, size_t bytes) {
+    for (auto at = c->cpool_free.begin(); at != c->cpool_free.end(); ++at)
+        if (at->buf.bytes >= bytes) {
+            G.ckeys = at->buf;
+            G.ckeys_ms = at->ms;
+            G.ckeys_ev = at->ev;
+            G.ckeys_wait = at->wait;
+            G.ckeys_busy = nullptr;
+            c->cpool_free.erase(at);
+            return true;
+        }
+    return false;
+}
+// (the caller has returned every genome's buffer, or there are no genomes: kr_destroy, kr_set_params*)
+static void coarse_pool_release(kr_ctx* c) {
+    if (c->cpool_free.empty()) return;
+    (void)hipDeviceSynchronize();
+    for (auto& pb : c->cpool_free) {
+        release(c, pb.buf);
+        if (pb.ev) (void)hipEventDestroy(pb.ev);
+    }
+    c->cpool_total -= (int)c->cpool_free.size();
+    c->cpool_free.clear();
+}
+
 static void release_genome(kr_ctx* c, Genome& G) {
+    coarse_pool_return(c, G);
     if (G.up_done) { (void)hipEventDestroy(G.up_done); G.up_done = nullptr; }
     if (G.sort_ev) { (void)hipEventDestroy(G.sort_ev); G.sort_ev = nullptr; }
     release(c, G.bases);
@@ -491,6 +573,10 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         c->lazy_order = e15 ? atoi(e15) != 0 : 1;
         const char* e17 = getenv("KR_COARSE_REST");
         c->coarse_rest = e17 ? atoi(e17) != 0 : 1;
+        const char* e21 = getenv("KR_COARSE_POOL");
+        c->coarse_pool = e21 ? atoi(e21) != 0 : 1;
+        const char* e22 = getenv("KR_PLACE_MIN_BYTES");
+        if (e22) c->place_min_bytes = (size_t)std::max(0ll, atoll(e22));
         const char* e18 = getenv("KR_COARSE_TCAP");
         if (e18) c->co_tcap = (u32)std::max(1, std::min((int)CO_TCAP, atoi(e18)));
         const char* e19 = getenv("KR_COARSE_HITCAP");
@@ -556,6 +642,7 @@ void kr_destroy(kr_ctx* c) {
         for (DevBuf* b : lb) release(c, *b);
     }
     for (auto& kv : c->genomes) release_genome(c, kv.second);
+    coarse_pool_release(c);
     DevBuf* all[] = {&c->candA, &c->candB, &c->chunkcnt,
                      &c->chunkpos, &c->flags, &c->blockcnt, &c->blockpos, &c->other, &c->records, &c->nrec, &c->fbdesc, &c->fbsegs,
                      &c->coltab, &c->collo, &c->colcnt, &c->colpos, &c->coltsum, &c->coltpos, &c->colfirst, &c->colfm, &c->isovf,
@@ -680,6 +767,7 @@ int kr_set_params(kr_ctx* c, int L, int D, int R, int softmask_mode, size_t max_
     if (softmask_mode != KR_SOFT_MAP && softmask_mode != KR_SOFT_OMIT)
         return fail(c, KR_ERR_PARAM, "unknown softmask mode %d", softmask_mode);
     if (!c->genomes.empty()) return fail(c, KR_ERR_STATE, "kr_set_params after genomes were uploaded");
+    coarse_pool_release(c);
     // (round 6: base positions, word indexes and key counts of the packed path are 64 bits throughout -- k_pack, k_hist8,
     // k_scatter1p<., BIG>, k_hist16, the pass-0 array; the code words of a genome stay below the 4 GiB a buffer descriptor
     // spans up to 2^34 bases.  KR_MAX_BASES = 2^33: 1.7e10 keys of 8 bytes twice -- pass 0 and the slices -- are what one
@@ -747,6 +835,10 @@ int kr_set_option(kr_ctx* c, int option, int64_t value) {
     case KR_OPT_COARSE_REST:
         if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_COARSE_REST: 0 or 1");
         c->coarse_rest = (int)value;
+        return KR_OK;
+    case KR_OPT_COARSE_POOL:
+        if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_COARSE_POOL: 0 or 1");
+        c->coarse_pool = (int)value;
         return KR_OK;
     case KR_OPT_ABLATE:
 #ifdef KR_ABLATE
@@ -875,6 +967,7 @@ int kr_set_params_wide(kr_ctx* c, int L, int D, int R, int softmask_mode, size_t
     if (softmask_mode != KR_SOFT_MAP && softmask_mode != KR_SOFT_OMIT)
         return fail(c, KR_ERR_PARAM, "unknown softmask mode %d", softmask_mode);
     if (!c->genomes.empty()) return fail(c, KR_ERR_STATE, "kr_set_params_wide after genomes were uploaded");
+    coarse_pool_release(c);
     if (max_bases >= (1ull << 32) - 256) return fail(c, KR_ERR_PARAM, "genomes of >= 2^32 bases are not supported");
     int sb, b, rc;
     // (every sorted spectrum / composite must carry the slice digits: the shortest piece decides)
@@ -923,7 +1016,7 @@ static int alloc_slice(kr_ctx* c, Slice& S, u64 count) {
 static double probe_scatter_ms(kr_ctx* c, void* p, size_t bytes) {
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
-    const u64 nkeys = bytes / 8 - 64;
+    const u64 nkeys = bytes / 8 > 64 ? bytes / 8 - 64 : 0;      // (a buffer too small for the kernel's loop is not written at all)
     hipLaunchKernelGGL(k_probe_scatter, dim3(NWG), dim3(512), 0, c->stream, (u64*)p, nkeys);      // warm-up (first touch)
     (void)hipEventRecord(e0, c->stream);
     for (int r = 0; r < 2; r++) hipLaunchKernelGGL(k_probe_scatter, dim3(NWG), dim3(512), 0, c->stream, (u64*)p, nkeys);
@@ -935,28 +1028,30 @@ static double probe_scatter_ms(kr_ctx* c, void* p, size_t bytes) {
     (void)hipEventDestroy(e1);
     return ms / 2;
 }
-// bufs = the pass-1 output buffers of the lanes that need (more) room: ONE pool of place_tries candidates per buffer
-// is allocated and probed, the fastest go to the lanes, the rest is freed -- a lane-by-lane search sees the pages the
-// lane before it gave back, and the probe classes (0.19 / 0.22 / 0.255 ms for 800 MB) come in streaks: three lanes
-// with 8 candidates each ended at 0.22 / 0.19 / 0.22, a pool of 24 gives every lane one of the best.
-static int ensure_placed(kr_ctx* c, DevBuf* const* bufs, int nbuf, size_t bytes) {
-    std::vector<DevBuf*> todo;
-    for (int i = 0; i < nbuf; i++)
-        if (bufs[i]->bytes < bytes) todo.push_back(bufs[i]);
-    if (todo.empty()) return KR_OK;
-    static const bool trace = getenv("KR_TRACE_ALLOC") != nullptr;
-    int rc;
-    for (DevBuf* b : todo)
-        if ((rc = ensure(c, *b, bytes))) return rc;
+// What a search saw: candidates probed, buffers handed out, the probe times of the four fastest, the median, the slowest.
+struct PlaceStats {
+    int n = 0, taken = 0;
+    double ms[6] = {0, 0, 0, 0, 0, 0};
+    size_t bytes = 0;
+};
+// the gates of a search, for buffers of `bytes`: candidates per buffer (<= 1: the buffers are taken as allocated)
+static int place_tries_for(const kr_ctx* c, size_t bytes) {
     // the search transiently holds place_tries x lanes buffers: not for a context that was given an HBM budget or that
     // shares its GPU with other ranks, unless the caller asked for it
     const int tries = (!c->place_tries_set && (c->budget || c->shared_gpu)) ? 1 : c->place_tries;
-    if (tries <= 1 || bytes < ((size_t)256 << 20)) return KR_OK;
+    if (tries <= 1 || bytes < c->place_min_bytes) return 1;
     // ... nor for a context that has not shown yet that it will sort many genomes (KR_OPT_LANES set, the automatic
     // switch after LANES_AFTER sorts, or KR_OPT_PLACE_TRIES set): the candidates are device memory the driver may have to clear first, 15-40 ms per GB
     // to obtain (tools/allocbench.hip) -- 7 ms of a 100 ms run over four 50 Mbp files, half a second of one over two
     // 3 Gbp genomes, for a few per cent of sort time that a one-shot run does not have
-    if (!c->place_tries_set && c->nlanes == 0 && c->sorts_done < LANES_AFTER) return KR_OK;
+    if (!c->place_tries_set && c->nlanes == 0 && c->sorts_done < LANES_AFTER) return 1;
+    return tries;
+}
+// The search: todo = allocated buffers of `bytes`; `tries` candidates per buffer are allocated and probed, the fastest go to
+// todo (in order: todo[0] the fastest, its time in ms_out[0]), the rest is freed.
+static void place_search(kr_ctx* c, const std::vector<DevBuf*>& todo, size_t bytes, int tries, PlaceStats& ps,
+                         std::vector<double>* ms_out = nullptr) {
+    static const bool trace = getenv("KR_TRACE_ALLOC") != nullptr;
     struct Cand { DevBuf buf; double ms; };
     std::vector<Cand> pool;            // (candidates stay allocated until the choice is made: a freed one would come back)
     for (DevBuf* b : todo) {
@@ -996,18 +1091,75 @@ static int ensure_placed(kr_ctx* c, DevBuf* const* bufs, int nbuf, size_t bytes)
     std::stable_sort(pool.begin(), pool.end(), [](const Cand& a, const Cand& b2) {
         return (a.ms > 0 ? a.ms : 1e30) < (b2.ms > 0 ? b2.ms : 1e30);
     });
-    // (what the search saw, for kr_debug_place: bench.py prints it, so that a line says which placement class it ran in)
-    c->place_n = (int)pool.size();
-    c->place_taken = (int)todo.size();
-    for (int i = 0; i < 4; i++) c->place_ms[i] = (size_t)i < pool.size() ? pool[i].ms : 0.0;
-    c->place_ms[4] = pool.empty() ? 0.0 : pool[pool.size() / 2].ms;
-    c->place_ms[5] = pool.empty() ? 0.0 : pool.back().ms;
-    c->place_bytes = bytes;
+    ps.n = (int)pool.size();
+    ps.taken = (int)todo.size();
+    for (int i = 0; i < 4; i++) ps.ms[i] = (size_t)i < pool.size() ? pool[i].ms : 0.0;
+    ps.ms[4] = pool.empty() ? 0.0 : pool[pool.size() / 2].ms;
+    ps.ms[5] = pool.empty() ? 0.0 : pool.back().ms;
+    ps.bytes = bytes;
     for (size_t i = 0; i < pool.size(); i++) {
-        if (i < todo.size()) *todo[i] = pool[i].buf;
-        else release(c, pool[i].buf);
+        if (i < todo.size()) {
+            *todo[i] = pool[i].buf;
+            if (ms_out) ms_out->push_back(pool[i].ms);
+        } else release(c, pool[i].buf);
     }
+}
+// bufs = the pass-1 output buffers of the lanes that need (more) room: ONE pool of place_tries candidates per buffer
+// is allocated and probed, the fastest go to the lanes, the rest is freed -- a lane-by-lane search sees the pages the
+// lane before it gave back, and the probe classes (0.19 / 0.22 / 0.255 ms for 800 MB) come in streaks: three lanes
+// with 8 candidates each ended at 0.22 / 0.19 / 0.22, a pool of 24 gives every lane one of the best.
+static int ensure_placed(kr_ctx* c, DevBuf* const* bufs, int nbuf, size_t bytes) {
+    std::vector<DevBuf*> todo;
+    for (int i = 0; i < nbuf; i++)
+        if (bufs[i]->bytes < bytes) todo.push_back(bufs[i]);
+    if (todo.empty()) return KR_OK;
+    int rc;
+    for (DevBuf* b : todo)
+        if ((rc = ensure(c, *b, bytes))) return rc;
+    const int tries = place_tries_for(c, bytes);
+    if (tries <= 1) return KR_OK;
+    // (what the search saw, for kr_debug_place: bench.py prints it, so that a line says which placement class it ran in)
+    PlaceStats ps;
+    place_search(c, todo, bytes, tries, ps);
+    c->place_n = ps.n;
+    c->place_taken = ps.taken;
+    for (int i = 0; i < 6; i++) c->place_ms[i] = ps.ms[i];
+    c->place_bytes = ps.bytes;
     return KR_OK;
+}
+
+// The pool grows: one search for `want` more buffers (intersect_coarse calls this behind its closing synchronisation, for the
+// coarse genomes of a call that hold no pooled buffer and have been partitioned at least twice -- a run that partitions each
+// genome once never comes here).  The gates are ensure_placed's; the statistics are the pool's own (kr_debug_coarse_pool):
+// c->place_* go on describing the lanes' buffers.  A device without room for a buffer ends the growth, not the call.
+static void coarse_pool_grow(kr_ctx* c, int want) {
+    const size_t bytes = ((size_t)c->lane_maxcount + 2) * 8;
+    if (want <= 0 || !c->coarse_pool || !c->lane_maxcount) return;
+    coarse_pool_purge(c, bytes);
+    want -= (int)c->cpool_free.size();
+    if (want <= 0) return;
+    const int tries = place_tries_for(c, bytes);
+    if (tries <= 1) return;
+    std::vector<DevBuf> fresh((size_t)want);
+    std::vector<DevBuf*> todo;
+    for (DevBuf& b : fresh) {
+        if (ensure(c, b, bytes)) break;
+        todo.push_back(&b);
+    }
+    c->err.clear();
+    if (todo.empty()) return;
+    PlaceStats ps;
+    std::vector<double> ms;
+    place_search(c, todo, bytes, tries, ps, &ms);
+    c->err.clear();        // (a candidate the device had no room for ended the search: not an error of the call)
+    c->cpool_searches++;
+    for (size_t i = 0; i < todo.size(); i++) {
+        if (!todo[i]->p) continue;
+        c->cpool_free.push_back({*todo[i], ms[i] > 0 ? ms[i] : 1e30, nullptr, false});      // (a failed probe sorts last)
+        c->cpool_total++;
+    }
+    std::stable_sort(c->cpool_free.begin(), c->cpool_free.end(),
+                     [](const kr_ctx::PoolBuf& a, const kr_ctx::PoolBuf& b2) { return a.ms < b2.ms; });
 }
 
 static int ensure_lanes(kr_ctx* c, u64 maxcount) {
@@ -1135,6 +1287,7 @@ static int count_slices(kr_ctx* c, Genome& G) {
     u64 maxcount = 0;
     G.nmax = 0;
     G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
+    coarse_pool_return(c, G);
     G.count = -1;
     // ONE histogram of the top byte of the absolute keys: a slice is 2^(8 - sbits) of its buckets
     Geom g0 = c->g;
@@ -1195,6 +1348,7 @@ int kr_genome_upload(kr_ctx* c, int id, const uint8_t* bases, size_t n) {
     G.n_bases = n;
     G.nwords = (n + 31) / 32;
     G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
+    coarse_pool_return(c, G);
     G.count = -1;
     int rc;
     if ((rc = ensure(c, G.bases, n + 64))) return rc;
@@ -1363,6 +1517,12 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
     u32* bad = (u32*)ln.bad.p;
     G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
     G.count = -1;
+    const size_t cbytes = ((size_t)c->lane_maxcount + 2) * 8;       // (a pooled buffer has the size of a lane's tmpkeys)
+    if (G.ckeys.p && (!coarse || !c->coarse_pool || G.ckeys.bytes < cbytes)) coarse_pool_return(c, G);
+    if (coarse) {
+        G.partitions++;
+        if (c->coarse_pool && !G.ckeys.p) (void)coarse_pool_take(c, G, cbytes);
+    }
     const bool cached_keys = reuse_count && c->g.wmode == 2 && c->g.wcache;
     const int cached_mode = c->g.wlcnt ? 4 : 2;         // (the key list, Geom.wlcnt, or 16 bytes per window start)
     const bool sliced = c->nslices > 1;
@@ -1478,6 +1638,17 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
         region += S.nmax;
         const u32 tile2 = 2 * P2_TILE;
         u64* pass1_dst = (g.b > 8 && !coarse) ? (u64*)ls.tmpkeys.p : (u64*)S.keys.p;
+        if (coarse && G.ckeys.p) {
+            // a placed buffer of the pool: its last owner's kernels may still be at it on another stream
+            pass1_dst = (u64*)G.ckeys.p;
+            if (G.ckeys_busy && G.ckeys_busy != ss) coarse_pool_handover(c, G);      // (its own last pass 1, on another lane)
+            if (G.ckeys_wait) {
+                HIPCHK(c, hipStreamWaitEvent(ss, G.ckeys_ev, 0));
+                G.ckeys_wait = false;
+            }
+            G.ckeys_busy = ss;
+            c->cpool_partitions++;
+        }
         if (route2) {
             const u32 ntA = (u32)((S.nmax + tile2 - 1) / tile2);
             if (ntA) {
@@ -1805,6 +1976,7 @@ int64_t kr_genome_load_sorted(kr_ctx* c, int id, const uint64_t* keys, size_t n)
     HIPCHK(c, hipGetLastError());
     G.uploaded = false;
     G.coarse = G.hits_valid = false;
+    coarse_pool_return(c, G);
     G.sorted = true;
     G.ordered = true;
     G.finalized = true;

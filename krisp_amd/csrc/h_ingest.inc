@@ -156,6 +156,7 @@ static int64_t upload_text_impl(kr_ctx* c, int id, const uint8_t* text, size_t n
     Genome& G = c->genomes[id];
     G.id = id;
     G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
+    coarse_pool_return(c, G);
     G.uploaded = false;
     G.count = -1;
     int rc;

@@ -102,7 +102,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     ca.n = (u32)cg.size();
     for (size_t j = 0; j < cg.size(); j++) {
         Genome& G = *cg[j];
-        ca.keys[j] = (const u64*)G.sl[0].keys.p;
+        ca.keys[j] = (const u64*)(G.ckeys.p ? G.ckeys.p : G.sl[0].keys.p);       // (pass 1 wrote the pooled buffer where the genome holds one)
         ca.off[j] = (const u32*)G.sl[0].off.p;
         ca.hits[j] = (u32*)G.hits.p;
         ca.hitcap[j] = hitcap;
@@ -118,6 +118,8 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
         hipLaunchKernelGGL(k_coarse_probe, dim3(grid), dim3(CO_T), 0, st, ca, (const u32*)cb, (const u32*)ust, (const u32*)rows,
                            (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel);
     }
+    for (Genome* G : cg)
+        if (G->ckeys.p) G->ckeys_busy = st;             // (the probe is the last reader of a pooled buffer)
     {
         StageScope sc(c, KR_ST_MERGE, st);
         hipLaunchKernelGGL(k_coarse_flag, dim3(nblk), dim3(256), 0, st, (kr_cand*)c->candB.p, nC, (const u32*)c->co_state.p, need,
@@ -131,6 +133,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     }
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
+    for (Genome* G : cg) G->ckeys_busy = nullptr;       // (the host has waited: nothing is at the pooled buffers)
     for (size_t j = 0; j < cg.size(); j++)
         if (((volatile u32*)c->mbox)[32 + j] > hitcap) {
             // a hit list that overflowed (a genome that repeats the candidates' prefixes many times over): nothing is
@@ -143,6 +146,12 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     c->ncand = total;
     for (Genome* G : cg) G->hits_valid = true;
     c->coarse_done += (int64_t)cg.size();
+    {
+        // the stream is idle: placed pass-1 targets for the genomes that came back without one (from their next partition on)
+        int want = 0;
+        for (Genome* G : cg) want += !G->ckeys.p && G->partitions >= 2;
+        if (want > 0) coarse_pool_grow(c, want);      // (less what lies in the free list)
+    }
     return total;
 }
 
@@ -441,7 +450,7 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         // launches it again)
         auto gather = [&](u32 cap) {
             if (by_items)
-                hipLaunchKernelGGL(k_gather_items, dim3((nunits + 63) / 64), dim3(64), 0, st, g.sbits, g.slice,
+                hipLaunchKernelGGL(k_gather_items, dim3((nunits + GI_ITEMS - 1) / GI_ITEMS), dim3(GI_T), 0, st, g.sbits, g.slice,
                                    (const kr_cand*)c->candA.p, (const u32*)AS.off.p, a3.mlog, nbk,
                                    (const u32*)c->chunkcnt.p, (const u32*)c->chunkpos.p, (kr_cand*)c->candB.p + running,
                                    nunits, cap);

@@ -13,6 +13,7 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     if (softmask_mode != KR_SOFT_MAP && softmask_mode != KR_SOFT_OMIT)
         return fail(c, KR_ERR_PARAM, "unknown softmask mode %d", softmask_mode);
     if (!c->genomes.empty()) return fail(c, KR_ERR_STATE, "kr_set_params_locate after genomes were uploaded");
+    coarse_pool_release(c);
     if (max_bases >= KR_MAX_BASES) return fail(c, KR_ERR_PARAM, "genomes of >= 2^33 bases are not supported");
     auto& l = c->loc;
     l.on = true;

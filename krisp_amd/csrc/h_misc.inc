@@ -264,6 +264,31 @@ int kr_debug_place(kr_ctx* c, double* out8) {
     return KR_OK;
 }
 
+// the pool of placed pass-1 targets for coarse genomes (h_core.inc: coarse_pool_*): out[0] buffers in all, [1] free, [2] held by
+// genomes, [3] coarse sorts that wrote into a pooled buffer, [4] placement searches the pool has run, [5] / [6] the fastest and
+// the slowest probe milliseconds among the buffers held (0 when none is), [7] KR_OPT_COARSE_POOL
+int kr_debug_coarse_pool(kr_ctx* c, double* out8) {
+    if (!c || !out8) return KR_ERR_PARAM;
+    int held = 0;
+    double lo = 0, hi = 0;
+    for (auto& kv : c->genomes) {
+        const Genome& G = kv.second;
+        if (!G.ckeys.p) continue;
+        lo = held ? std::min(lo, G.ckeys_ms) : G.ckeys_ms;
+        hi = held ? std::max(hi, G.ckeys_ms) : G.ckeys_ms;
+        held++;
+    }
+    out8[0] = c->cpool_total;
+    out8[1] = (double)c->cpool_free.size();
+    out8[2] = held;
+    out8[3] = (double)c->cpool_partitions;
+    out8[4] = (double)c->cpool_searches;
+    out8[5] = lo;
+    out8[6] = hi;
+    out8[7] = c->coarse_pool;
+    return KR_OK;
+}
+
 int kr_debug_isect(kr_ctx* c, int64_t* o) {
     if (!c || !o) return KR_ERR_PARAM;
     o[0] = c->isect_ovf_items;

@@ -421,30 +421,44 @@ __global__ __launch_bounds__(I3_MAXT, FMT == 0 ? I3_OCC0 : (FMT == 1 ? 6 : 4)) v
     }
 }
 
-// dense, ordered candidate list from the per-item runs of k_intersect3: a wave per 64 items (most hold no survivor:
-// one ballot finds those that do -- 65536 one-wave workgroups that mostly had nothing to do took 15 us)
-__global__ __launch_bounds__(64) void k_gather_items(int sbits, u32 slice, const kr_cand* __restrict__ tmp,
-                                                    const u32* __restrict__ offA, int mlog, u32 nb,
-                                                    const u32* __restrict__ itemcnt, const u32* __restrict__ itempos,
-                                                    kr_cand* __restrict__ out, u32 nunits, u32 cap) {
+// dense, ordered candidate list from the per-item runs of k_intersect3: a workgroup of GI_T threads per GI_ITEMS items.
+// Two shapes of list come here.  Without the filter most items hold no survivor: a workgroup whose items hold none reads
+// two prefix sums and leaves.  The filtered list of a sorted pair holds something in nearly every item (1.16e6 entries in
+// 48 000 items at 2 x 50 Mbp): the workgroup scans its counts in LDS and its threads walk its OUTPUTS, entry by entry, each
+// finding its item in the prefix sums (gi_index.inc) -- every lane moves an entry in every trip, where a wave per item
+// kept as many lanes busy as the item had entries (about 24 of 64).
+#include "gi_index.inc"
+#define GI_T 256
+__global__ __launch_bounds__(GI_T) void k_gather_items(int sbits, u32 slice, const kr_cand* __restrict__ tmp,
+                                                      const u32* __restrict__ offA, int mlog, u32 nb,
+                                                      const u32* __restrict__ itemcnt, const u32* __restrict__ itempos,
+                                                      kr_cand* __restrict__ out, u32 nunits, u32 cap) {
     if (itempos[nunits] > cap) return;               // (as k_gather_cands)
-    const u32 lane = threadIdx.x;
-    const u32 mine = blockIdx.x * 64 + lane;
-    const u32 nmine = mine < nunits ? itemcnt[mine] : 0u;
-    u64 live = __ballot(nmine != 0);
-    const u64 top = sbits ? ((u64)slice << (64 - sbits)) : 0;
-    while (live) {
-        const u32 l = (u32)__ffsll((long long)live) - 1;
-        live &= live - 1;
-        const u32 it = blockIdx.x * 64 + l;
-        const u32 n = __shfl(nmine, (int)l, 64);
+    const u32 tid = threadIdx.x, first = blockIdx.x * GI_ITEMS;
+    const u32 last = first + GI_ITEMS < nunits ? first + GI_ITEMS : nunits;
+    const u32 dst = itempos[first], total = itempos[last] - dst;
+    if (total == 0) return;                          // (the sparse list: nothing to scan)
+    __shared__ u32 pre[GI_ITEMS + 1], srcs[GI_ITEMS];
+    if (tid < GI_ITEMS) {                            // (one wave: the scan needs no barrier of its own)
+        const u32 it = first + tid;
+        const u32 n = it < nunits ? itemcnt[it] : 0u;
         const u64 f = (u64)it << mlog;
-        const u64 src = offA[f < nb ? f : nb];
-        const u32 dst = itempos[it];
-        for (u32 i = lane; i < n; i += 64) {
-            kr_cand c = tmp[src + i];
-            c.prefix = top | (c.prefix >> sbits);          // relative -> absolute prefix
-            out[dst + i] = c;
+        srcs[tid] = n ? offA[f < nb ? f : nb] : 0u;
+        u32 s = n;
+#pragma unroll
+        for (u32 d = 1; d < GI_ITEMS; d <<= 1) {
+            const u32 t = __shfl_up(s, d, 64);
+            if (tid >= d) s += t;
         }
+        pre[tid + 1] = s;
+        if (tid == 0) pre[0] = 0;
+    }
+    __syncthreads();
+    const u64 top = sbits ? ((u64)slice << (64 - sbits)) : 0;
+    for (u32 o = tid; o < total; o += GI_T) {
+        const GiSlot at = gi_slot(pre, o);
+        kr_cand c = tmp[(u64)srcs[at.item] + at.offset];
+        c.prefix = top | (c.prefix >> sbits);          // relative -> absolute prefix
+        out[dst + o] = c;
     }
 }
