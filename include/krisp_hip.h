@@ -702,6 +702,8 @@ int     kr_build_experiments(void);
  * anchor genome stayed in bucket order as well (k_intersect3t<., UA>), [5] 1 unless KR_FUSE_ANCHOR=0,
  * [6] genomes an intersection took in the coarse state (kr_genome_partition), [7] coarse genomes sorted fine after all */
 int     kr_debug_lazy(kr_ctx*, int64_t* out8);
+/* the intersection's counters: out8[0] items the chunk kernel took, [1] slices redone by chunks, [2] threads and [3] log2 buckets of
+ * the latest call's items, [4] 1 where it took the kernels with 32-bit heads, [5] the sort lanes in use, [6] and [7] unused (0) */
 int     kr_debug_isect(kr_ctx*, int64_t* out8);
 /* the latest placement search of the pass-1 output buffers: out8[0] candidates probed, [1] buffers handed to the sort lanes,
  * [2..5] probe milliseconds of the four fastest candidates, [6] the median, [7] the slowest (bench.py prints them: which

@@ -928,7 +928,7 @@ class Engine:
         o = np.zeros(8, dtype=np.int64)
         self.lib.kr_debug_isect(self.ctx, _ptr(o))
         return dict(chunk_kernel_items=int(o[0]), slices_redone=int(o[1]), threads=int(o[2]), buckets_per_item_log2=int(o[3]),
-                    heads32=int(o[4]), sort_lanes=int(o[5]), splits=int(o[6]), probed=int(o[7]))
+                    heads32=int(o[4]), sort_lanes=int(o[5]))
 
     def debug_lazy(self):
         """KR_OPT_LAZY_ORDER's counters (kr_debug_lazy): LDS sorts of whole slices the sorts left out, made later, collects

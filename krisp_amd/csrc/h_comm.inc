@@ -469,17 +469,12 @@ static int64_t cands_merge_incoming(kr_ctx* c, int apply_filter) {
     int rc = KR_OK;
     u32 total = 0;
     if (n) {
-        if (!rc) rc = ensure(c, c->flags, (size_t)n * 4);
-        if (!rc) rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4);
-        if (!rc) rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4);
+        rc = cands_compact_room(c, n);          // (candA: sized by exchange_prepare already)
         if (!rc) {
             StageScope sc(c, KR_ST_MERGE);
             hipLaunchKernelGGL(k_cands_flag, dim3(nblk), dim3(256), 0, st, (kr_cand*)c->candB.p, n, (const kr_cand*)c->other.p, 0u,
                                1, fmode(c, apply_filter), c->g.D, (u32*)c->flags.p, (u32*)c->blockcnt.p, hdr);
-            hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
-            hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, n,
-                               (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
-            HIPCHK(c, hipMemcpyAsync(&total, (u32*)c->blockpos.p + nblk, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(&total, cands_compact_enqueue(c, n, st, false), 4, hipMemcpyDeviceToHost, st));
         }
     }
     HIPCHK(c, hipMemcpyAsync(m->hdr_in, hdr, 16, hipMemcpyDeviceToHost, st));
@@ -487,10 +482,7 @@ static int64_t cands_merge_incoming(kr_ctx* c, int apply_filter) {
     if (rs) return rs;
     if (rc) return rc;
     HIPCHK(c, hipGetLastError());
-    if (n) {
-        std::swap(c->candA, c->candB);
-        c->ncand = total;
-    }
+    if (n) cands_compact_adopt(c, total);
     return c->ncand;
 }
 

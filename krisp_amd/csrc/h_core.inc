@@ -45,8 +45,6 @@ struct Genome {
                              // on its own lane, beside the other genomes' passes, instead of in front of the intersection
     int64_t count = -1;
     hipEvent_t up_done = nullptr;      // the H2D copy of `bases` (copy stream); sorts wait for it
-    hipEvent_t sort_ev = nullptr;      // behind the genome's latest sort on its lane (kr_intersect waits genome by genome)
-    int64_t sort_seq = 0;              // the context's sort counter at that sort: which genomes were sorted last
 };
 
 // one sort "lane" = a stream + the scratch one genome sort needs; consecutive genome sorts
@@ -69,7 +67,6 @@ struct kr_ctx {
     kr_comm* comm = nullptr;          // multi-GPU exchange (h_comm.inc)
     hipStream_t stream = nullptr;     // main stream = lanes[0].stream
     hipStream_t copy_stream = nullptr;   // H2D of genomes from pinned buffers (kr_ingest_file), beside the sorts
-    hipStream_t isect_stream = nullptr;  // the intersection over the early genomes of a call, beside the late sorts (h_intersect.inc)
     Lane lanes[MAX_LANES];
     int nlanes = 0, next_lane = 0;    // sort lanes (KR_OPT_LANES / KR_LANES env; 0 = automatic): lanes_used() of them take the sorts in turn
     int lanes_ready = 0;              // lanes whose scratch fits lane_maxcount
@@ -123,7 +120,7 @@ struct kr_ctx {
     int mb_next = 0;
     int i3_occ[3][4][9] = {{{0}}};      // ([2]: k_intersect3t<FMT, UA = true>)      // resident k_intersect3<FMT> ([1]: k_intersect3t<FMT>) workgroups per CU by threads / 64 (occupancy query, cached)
     DevBuf isovf;                   // k_intersect3: oversized items
-    int64_t isect_ovf_items = 0, isect_refall = 0, isect_splits = 0, isect_probed = 0;
+    int64_t isect_ovf_items = 0, isect_refall = 0;
     int i3_last_T = 0, i3_last_mlog = 0, i3_last_tags = 0, i3_last_ua = 0;
     int64_t isect_ua = 0;            // intersections whose anchor stayed in bucket order (k_intersect3t<., true>)
     int fuse_anchor = 1;             // KR_FUSE_ANCHOR env (A/B, tests): 0 = the anchor genome is sorted by k_localsort2 before every intersection
@@ -132,8 +129,6 @@ struct kr_ctx {
     int opt_slice_bases = -1;   // KR_OPT_SLICE_BASES / KR_SLICE_BASES env: -1 = automatic
     hipEvent_t slice_ready[2] = {nullptr, nullptr};   // a sliced genome's pass 0 is done (per genome lane): its slices may start on the helper lane
     bool custom_layout = false; // kr_set_field_order moved fields: a sort-only context (no (left,right) prefix to intersect on)
-    int isect_split = 0;        // KR_ISECT_SPLIT env (A/B, tests): 1 = the genomes of the last sort round probe the candidates of the early ones
-                                // (h_intersect.inc; exact, and measured neutral to -1 %: off unless asked for)
     bool mixed_alphabets = false;   // kr_set_mixed_alphabets: the diagnostic filter in its mode 2 (k_intersect.inc: passes_filter)
     int lazy_order = 1;         // KR_OPT_LAZY_ORDER / KR_LAZY_ORDER env: 1 = a sort stops at the fine buckets (two partition passes); the order
                                 // inside the buckets is made when somebody reads it: the anchor of an intersection, the buckets a candidate
@@ -446,7 +441,6 @@ static void coarse_pool_release(kr_ctx* c) {
 static void release_genome(kr_ctx* c, Genome& G) {
     coarse_pool_return(c, G);
     if (G.up_done) { (void)hipEventDestroy(G.up_done); G.up_done = nullptr; }
-    if (G.sort_ev) { (void)hipEventDestroy(G.sort_ev); G.sort_ev = nullptr; }
     release(c, G.bases);
     release(c, G.wkeys);
     release(c, G.wlcnt);
@@ -565,8 +559,6 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         c->isect_fmt = e2 ? (atoi(e2) == 1 ? 1 : (atoi(e2) == 2 ? 2 : 0)) : 0;
         const char* e3 = getenv("KR_SLICE_BASES");
         c->opt_slice_bases = e3 ? std::max(0, std::min(4, atoi(e3))) : -1;
-        const char* e14 = getenv("KR_ISECT_SPLIT");
-        c->isect_split = e14 ? atoi(e14) != 0 : 0;
         const char* e16 = getenv("KR_FUSE_ANCHOR");
         c->fuse_anchor = e16 ? atoi(e16) != 0 : 1;
         const char* e15 = getenv("KR_LAZY_ORDER");
@@ -686,7 +678,6 @@ void kr_destroy(kr_ctx* c) {
     if (c->mbox) (void)hipHostFree(c->mbox);
     for (auto e : c->pool) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->isect_stream) (void)hipStreamDestroy(c->isect_stream);
     for (hipEvent_t e : c->slice_ready) if (e) (void)hipEventDestroy(e);
     (void)hipEventDestroy(c->t0);
     (void)hipEventDestroy(c->t1);
@@ -1531,7 +1522,7 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
     // (kstream) sorts are read in order right away and end with the LDS sort as before.  KR_LAZY_WIDE=0: the wide path eager (A/B)
     static const bool lazy_wide = [] { const char* e = getenv("KR_LAZY_WIDE"); return e ? atoi(e) != 0 : true; }();
     const bool lazy = c->lazy_order && (lazy_wide || (!c->wide.on && c->g.wmode == 0)) && !c->custom_layout && c->g.strands == 0 &&
-                      !c->isect_split && !c->order_wanted && !(G.was_anchor && !c->i3_last_ua);       // (an anchor the fused kernel takes needs no order either)
+                      !c->order_wanted && !(G.was_anchor && !c->i3_last_ua);       // (an anchor the fused kernel takes needs no order either)
     if (sliced) {
         // the slices of the genome this lane sorted before may still run on its helper lane, out of this lane's arrays
         for (int h = 0; h < SLICE_HELPERS; h++) {
@@ -1759,11 +1750,6 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
     G.ordered = !lazy && !coarse;
     G.sorted = !coarse;   // enqueued; oversized buckets (if any) are resolved by finalize()
     G.coarse = coarse;
-    G.sort_seq = c->sorts_done;
-    if (!sliced) {
-        if (!G.sort_ev) HIPCHK(c, hipEventCreateWithFlags(&G.sort_ev, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(G.sort_ev, st));
-    }
     return KR_OK;
 }
 

@@ -2,7 +2,6 @@
 static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* is_in, int apply_filter, bool* redo);
 
 static int64_t cands_merge_device(kr_ctx* c, size_t m, int have_other, int apply_filter);
-static int64_t cands_probe_device(kr_ctx* c, const IsectArgs& pa);
 
 // candidate lists are indexed with 32 bits on the device (flags, block scans, the pair index of kr_collect): a longer list --
 // possible where nothing prunes: one side only, no filter, genomes of > 2e9 bases -- is refused, never truncated (ADVICE r5)
@@ -21,6 +20,35 @@ static int cands_fit(kr_ctx* c, uint64_t n, const char* who) {
     return fail(c, KR_ERR_CAPACITY, "%s: a candidate list of %llu entries exceeds the %llu a list may hold (an intersection that "
                 "nothing prunes: give both ingroup and outgroup genomes to one call, or fewer genomes per call)", who,
                 (unsigned long long)n, (unsigned long long)KR_MAX_CANDS);
+}
+
+// The compaction of the live list (the n candidates in candB), shared by every site that prunes it.  The site's own flag
+// kernel leaves a keep flag per candidate in `flags` and the count of each block of 256 in `blockcnt`; k_scan places the
+// blocks, k_cands_compact writes the kept candidates to candA, and the site adopts candA once its own synchronisation has
+// brought the total to the host.  cands_compact_room: the scratch and the target for n candidates.
+static int cands_compact_room(kr_ctx* c, u32 n) {
+    const size_t nblk = ((size_t)n + 255) / 256;
+    int rc;
+    if ((rc = ensure(c, c->flags, (size_t)n * 4))) return rc;
+    if ((rc = ensure(c, c->blockcnt, (nblk + 2) * 4))) return rc;
+    if ((rc = ensure(c, c->blockpos, (nblk + 2) * 4))) return rc;
+    return ensure(c, c->candA, ((size_t)n + 2) * sizeof(kr_cand));
+}
+// behind the flag kernel on `st`; returns where the total lies on the device (publish: also sent to mbox[16])
+static const u32* cands_compact_enqueue(kr_ctx* c, u32 n, hipStream_t st, bool publish) {
+    const u32 nblk = (n + 255) / 256;
+    const u32* total = (const u32*)c->blockpos.p + nblk;
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
+    hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, n,
+                       (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
+    if (publish)
+        hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, total, (const u32*)nullptr, (const u32*)nullptr, c->mbox + 16);
+    return total;
+}
+static int64_t cands_compact_adopt(kr_ctx* c, u32 total) {
+    std::swap(c->candA, c->candB);
+    c->ncand = total;
+    return total;
 }
 
 static int64_t intersect_batch(kr_ctx* c, const int* ids, int n, const uint8_t* is_in, int apply_filter) {
@@ -75,10 +103,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     const u32 hitcap = c->co_hitcap ? c->co_hitcap : (u32)std::min<u64>(2ull * nC + 65536, 0x7FFFFFF0ull);
     if ((rc = ensure(c, c->co_state, (size_t)nC * 4))) return rc;
     if ((rc = ensure(c, c->co_tab, (size_t)(2 * 260 + 256 * CO_ROW) * 4))) return rc;
-    if ((rc = ensure(c, c->flags, (size_t)nC * 4))) return rc;
-    if ((rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4))) return rc;
-    if ((rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4))) return rc;
-    if ((rc = ensure(c, c->candA, ((size_t)nC + 2) * sizeof(kr_cand)))) return rc;
+    if ((rc = cands_compact_room(c, nC))) return rc;
     for (Genome* G : cg) {
         if (G->hitcap < hitcap || !G->hits.p) {
             if ((rc = ensure(c, G->hits, (size_t)hitcap * 8 + 16))) return rc;
@@ -124,11 +149,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
         StageScope sc(c, KR_ST_MERGE, st);
         hipLaunchKernelGGL(k_coarse_flag, dim3(nblk), dim3(256), 0, st, (kr_cand*)c->candB.p, nC, (const u32*)c->co_state.p, need,
                            fmode(c, 1), (u32*)c->flags.p, (u32*)c->blockcnt.p);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
-        hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC,
-                           (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
-        hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, (const u32*)c->blockpos.p + nblk, (const u32*)nullptr,
-                           (const u32*)nullptr, c->mbox + 16);
+        cands_compact_enqueue(c, nC, st, true);
         hipLaunchKernelGGL(k_coarse_publish, dim3(1), dim3(64), 0, st, pub, c->mbox + 32);
     }
     HIPCHK(c, hipStreamSynchronize(st));
@@ -142,8 +163,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
             return KR_COARSE_PASS;
         }
     const u32 total = ((volatile u32*)c->mbox)[16];
-    std::swap(c->candA, c->candB);
-    c->ncand = total;
+    cands_compact_adopt(c, total);
     for (Genome* G : cg) G->hits_valid = true;
     c->coarse_done += (int64_t)cg.size();
     {
@@ -199,16 +219,38 @@ int64_t kr_intersect(kr_ctx* c, const int* ids, int n, const uint8_t* is_in, int
 // probability for evenly filled buckets, at most 4 T anchor keys (T = 256 .. 512 threads); fuller ones are listed and go
 // through k_intersect.  tagk: 32-bit heads (k_intersect3t.inc) where the sub-bin field starts in the key's high word and at
 // most 32 bits above the prefix's lowest bit
-static void item_plan(const kr_ctx* c, const Slice& AS, const Geom& g, int& mlog, u32& T, bool& tagk) {
+struct ItemPlan {
+    int mlog;       // an item is 2^mlog buckets
+    u32 T;          // threads of its workgroup
+    bool tagk;      // the kernels with 32-bit heads apply
+    int p0, sht;    // the prefix's lowest bit; the shift to the sub-bin field of the 32-bit heads
+};
+static ItemPlan item_plan(const kr_ctx* c, const Slice& AS, const Geom& g) {
     const u32 nbk = 1u << c->g.b;
     const double avg = (double)std::max<int64_t>(AS.count >= 0 ? AS.count : (int64_t)AS.nmax, 1) / nbk;   // (nmax: the bound 2 n, exact but for N / masked windows)
     auto need = [](double mean) { return mean + 6.0 * std::sqrt(mean) + 8.0; };
-    mlog = 0;
-    while ((2u << mlog) <= nbk && need(avg * (2u << mlog)) <= (double)I3_SLOTS) mlog++;
-    T = (u32)std::min(512.0, std::max(256.0, 64.0 * std::ceil(need(avg * (1u << mlog)) / 256.0)));
-    const int p0 = 64 - 2 * g.LRrel, sht = g.rb + mlog - (int)I3T_NB_LOG;
-    tagk = c->isect_kernel != 2 && p0 >= 0 && p0 < 32 && sht >= 32 && sht <= p0 + 32;
+    ItemPlan p;
+    p.mlog = 0;
+    while ((2u << p.mlog) <= nbk && need(avg * (2u << p.mlog)) <= (double)I3_SLOTS) p.mlog++;
+    p.T = (u32)std::min(512.0, std::max(256.0, 64.0 * std::ceil(need(avg * (1u << p.mlog)) / 256.0)));
+    p.p0 = 64 - 2 * g.LRrel;
+    p.sht = g.rb + p.mlog - (int)I3T_NB_LOG;
+    p.tagk = c->isect_kernel != 2 && p.p0 >= 0 && p.p0 < 32 && p.sht >= 32 && p.sht <= p.p0 + 32;
+    return p;
 }
+
+// the pipelined kernels by [anchor in bucket order: k_intersect3t<., true>][mask format; 3 = one 32-bit state word] for the
+// 32-bit heads, by [mask format] for the 64-bit ones; the chunk kernel by [mask format]
+typedef void (*Isect3Kernel)(Isect3Args, Geom);
+static Isect3Kernel isect3_kernel(bool ua, bool tagk, bool st32, int fmt) {
+    static const Isect3Kernel heads32[2][4] = {
+        {k_intersect3t<0>, k_intersect3t<1>, k_intersect3t<2>, k_intersect3t<3>},
+        {k_intersect3t<0, true>, k_intersect3t<1, true>, k_intersect3t<2, true>, k_intersect3t<3, true>}};
+    static const Isect3Kernel heads64[3] = {k_intersect3<0>, k_intersect3<1>, k_intersect3<2>};
+    return tagk ? heads32[ua ? 1 : 0][st32 ? 3 : fmt] : heads64[fmt];
+}
+typedef void (*IsectKernel)(IsectArgs, Geom);
+static const IsectKernel isect_chunk_kernel[3] = {k_intersect<0>, k_intersect<1>, k_intersect<2>};
 
 // The genomes' sorts may still be running: their kernels are ordered before the intersection on the device, the
 // host does not wait for them.  What a sort leaves open (its key count; rarely oversized buckets for the merge
@@ -218,54 +260,21 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
     *redo = false;
     if (!c || n < 1 || n > MAXG) return fail(c, KR_ERR_PARAM, "kr_intersect: 1 .. %d genomes per batch", MAXG);
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<Genome*> gall;
-    for (int i = 0; i < n; i++) {
-        auto it = c->genomes.find(ids[i]);
-        if (it == c->genomes.end() || !it->second.sorted) return fail(c, KR_ERR_STATE, "genome %d not sorted", ids[i]);
-        gall.push_back(&it->second);
-    }
-    // Round 4: the genomes whose sorts were enqueued last (the last round over the sort lanes) stay out of the big
-    // intersection.  It runs over the EARLY genomes as soon as THEIR lanes are done -- beside the late sorts -- with the
-    // diagnostic filter on partial masks (monotone: what fails on partial masks fails for good), and the late genomes
-    // then only look the few surviving candidates up (k_cands_probe).  The step used to end with 0.8 ms of intersection
-    // alone on the device behind the last sort; with the split it ends with a probe of some 10^5 prefixes.  Needs the filter,
-    // an early group with ingroup AND outgroup genomes (else nothing is pruned), one sort unit.  KR_ISECT_SPLIT=1 switches it
-    // on: exact under test, but measured neutral to -1 % per step (DESIGN 3: the persistent intersection's LDS keeps the late
-    // sort's kernels off the CUs it sits on, so the two do not overlap; the probe chain costs what the smaller intersection saves).
-    std::vector<int> ord(n);
-    for (int i = 0; i < n; i++) ord[i] = i;
-    int n1 = n;
-    {
-        const int L = lanes_used(c);
-        bool all_ord = true;          // (the probe of the late genomes searches sorted runs)
-        for (Genome* G : gall) all_ord = all_ord && G->ordered;
-        if (c->isect_split && all_ord && apply_filter && c->g.D > 0 && c->nslices == 1 && n >= 3 && L > 1 && !c->wide.on) {
-            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return gall[x]->sort_seq < gall[y]->sort_seq; });
-            const int late = (n - 1) % L + 1;           // genomes of the last round over the lanes
-            const int m = n - late;
-            bool has_in = false, has_out = false, evs = true;
-            for (int q = 0; q < m; q++) { (is_in[ord[q]] ? has_in : has_out) = true; }
-            for (int q = 0; q < n; q++) evs = evs && gall[ord[q]]->sort_ev != nullptr;
-            if (m >= 2 && has_in && has_out && evs) n1 = m;
-            else for (int i = 0; i < n; i++) ord[i] = i;
-        }
-    }
-    const bool split = n1 < n;
     int anchor = 0;
     u64 best = ~0ull;
     u32 ingroup_bits = 0;
-    std::vector<Genome*> gs;            // early genomes first (all of them without a split), then the late ones
-    for (int q = 0; q < n; q++) {
-        Genome& G = *gall[ord[q]];
-        if (q < n1) {
-            if (is_in[ord[q]]) ingroup_bits |= 1u << q;
-            if (G.nmax < best) { best = G.nmax; anchor = q; }
-        }
+    std::vector<Genome*> gs;
+    for (int i = 0; i < n; i++) {
+        auto it = c->genomes.find(ids[i]);
+        if (it == c->genomes.end() || !it->second.sorted) return fail(c, KR_ERR_STATE, "genome %d not sorted", ids[i]);
+        Genome& G = it->second;
+        if (is_in[i]) ingroup_bits |= 1u << i;
+        if (G.nmax < best) { best = G.nmax; anchor = i; }
         gs.push_back(&G);
     }
     int rc;
     // the pipelined kernel (k_intersect3.inc) wherever a (left,right) group lies inside one fine bucket
-    const bool use3 = n1 >= 2 && 2 * c->g.LRrel >= c->g.b && !(c->dbg & 32) && c->isect_kernel != 1;
+    const bool use3 = n >= 2 && 2 * c->g.LRrel >= c->g.b && !(c->dbg & 32) && c->isect_kernel != 1;
     // KR_OPT_LAZY_ORDER: genomes whose sort stopped at the fine buckets.  The pipelined kernels hash every streamed key
     // into the sub-bins of the item's anchor run -- they never look at a streamed genome's order inside a bucket --, so
     // only the ANCHOR's buckets are sorted now (its run of an item is the slot array: equal prefixes adjacent, survivors
@@ -274,15 +283,11 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
     for (Genome* G : gs) all_ordered = all_ordered && G->ordered;
     for (int q = 0; q < n; q++) gs[q]->was_anchor = use3 && q == anchor;
     if (!all_ordered) {
-        if (use3 && !split) {
+        if (use3) {
             // (the anchor, too, may stay as it is where the kernel with 32-bit heads applies to EVERY slice -- the item
             // geometry below decides that, k_intersect3t<., UA> then makes the item's slots itself; else its LDS sort runs now)
             bool ua_ok = c->fuse_anchor && c->isect_kernel != 2;
-            for (int s = 0; ua_ok && s < c->nslices; s++) {
-                int mlog_s; u32 T_s; bool tagk_s;
-                item_plan(c, gs[anchor]->sl[s], slice_geom(c, (u32)s), mlog_s, T_s, tagk_s);
-                ua_ok = tagk_s;
-            }
+            for (int s = 0; ua_ok && s < c->nslices; s++) ua_ok = item_plan(c, gs[anchor]->sl[s], slice_geom(c, (u32)s)).tagk;
             if (!gs[anchor]->ordered && !ua_ok) {
                 if ((rc = join_lanes(c))) return rc;
                 if ((rc = order_genome(c, *gs[anchor], c->stream))) return rc;
@@ -302,12 +307,7 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         for (Genome* G : gs)
             if (!G->finalized)
                 for (Slice& S : G->sl) open_slices.push_back(&S);
-        if (split) {
-            // (only the early genomes' sorts are waited for, and on a stream of its own: the context's stream is the
-            // first lane's, a late sort may be queued on it; the words of all genomes are published behind the probe)
-            if (!c->isect_stream) HIPCHK(c, hipStreamCreate(&c->isect_stream));
-            for (int q = 0; q < n1; q++) HIPCHK(c, hipStreamWaitEvent(c->isect_stream, gs[q]->sort_ev, 0));
-        } else if (open_slices.size() > PUB_CAP) {
+        if (open_slices.size() > PUB_CAP) {
             if ((rc = finalize(c, gs))) return rc;
             pending = false;
         } else {
@@ -328,7 +328,7 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         if ((rc = ensure(c, c->coltsum, nt * 4))) return rc;
         if ((rc = ensure(c, c->coltpos, nt * 4))) return rc;
     }
-    hipStream_t st = (split && pending) ? c->isect_stream : c->stream;
+    hipStream_t st = c->stream;
     u64 running = 0;
     const u32 nbk = 1u << c->g.b;
     if (use3) {
@@ -344,12 +344,12 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         Slice& AS = A.sl[s];
         const int fmt = g.D > 8 ? 2 : ((g.D > 4 || c->isect_fmt == 1) ? 1 : 0);
         IsectArgs a{};
-        a.n = n1;
+        a.n = n;
         a.ingroup_bits = ingroup_bits;
         a.apply_filter = fmode(c, apply_filter);
         a.dbg = c->dbg;
         a.anchor = anchor;
-        for (int i = 0; i < n1; i++) {
+        for (int i = 0; i < n; i++) {
             a.keys[i] = (const u64*)gs[i]->sl[s].keys.p;
             a.off[i] = (const u32*)gs[i]->sl[s].off.p;
         }
@@ -357,9 +357,7 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         a.tmp = (kr_cand*)c->candA.p;
         a.chunkcnt = (u32*)c->chunkcnt.p;
         auto launch_chunks = [&](u32 grid) {
-            if (fmt == 2) hipLaunchKernelGGL(k_intersect<2>, dim3(grid), dim3(IS_THREADS), 0, st, a, g);
-            else if (fmt == 1) hipLaunchKernelGGL(k_intersect<1>, dim3(grid), dim3(IS_THREADS), 0, st, a, g);
-            else hipLaunchKernelGGL(k_intersect<0>, dim3(grid), dim3(IS_THREADS), 0, st, a, g);
+            hipLaunchKernelGGL(isect_chunk_kernel[fmt], dim3(grid), dim3(IS_THREADS), 0, st, a, g);
         };
         bool by_items = use3;
         u32 nunits = AS.nchunks;          // runs of survivors: per chunk, or per item
@@ -367,20 +365,21 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         if (by_items) {
             // items of 2^mlog buckets that hold, with all but vanishing probability for evenly filled buckets, at most
             // 4 T anchor keys (T = 256 .. 512 threads); fuller ones are listed and go through k_intersect below
-            int mlog; u32 T; bool tagk;
-            item_plan(c, AS, g, mlog, T, tagk);
-            const int p0 = 64 - 2 * g.LRrel, sht = g.rb + mlog - (int)I3T_NB_LOG;
+            const ItemPlan ip = item_plan(c, AS, g);
+            const int mlog = ip.mlog;
+            const u32 T = ip.T;
+            const bool tagk = ip.tagk;
             const bool ua = tagk && !gs[anchor]->ordered;        // (an anchor in bucket order: every slice's kernel has 32-bit heads -- checked above)
-            a3.n = n1;
+            a3.n = n;
             a3.ingroup_bits = ingroup_bits;
             a3.anchor = anchor;
             a3.apply_filter = a.apply_filter;
-            for (int i = 0; i < n1; i++) { a3.keys[i] = a.keys[i]; a3.off[i] = a.off[i]; }
+            for (int i = 0; i < n; i++) { a3.keys[i] = a.keys[i]; a3.off[i] = a.off[i]; }
             a3.nb = nbk;
             a3.mlog = mlog;
             a3.nitems = (nbk + (1u << mlog) - 1) >> mlog;
-            a3.sh = tagk ? sht : std::max(g.rb + mlog - (int)I3_NB_LOG, 64 - 2 * g.LRrel);
-            a3.p0 = p0;
+            a3.sh = tagk ? ip.sht : std::max(g.rb + mlog - (int)I3_NB_LOG, ip.p0);
+            a3.p0 = ip.p0;
             a3.tmp = (kr_cand*)c->candA.p;
             a3.itemcnt = (u32*)c->chunkcnt.p;
             a3.ovf = (u32*)c->isovf.p;
@@ -390,47 +389,20 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
             nunits = a3.nitems;
             c->i3_last_tags = tagk ? 1 : 0;
             // (one diagnostic column, at most 24 genomes: the slot's state is one 32-bit word)
-            const bool st32 = tagk && fmt == 0 && g.D == 1 && n1 <= 24 && c->isect_fmt == 0;
+            const bool st32 = tagk && fmt == 0 && g.D == 1 && n <= 24 && c->isect_fmt == 0;
+            const Isect3Kernel kern = isect3_kernel(ua, tagk, st32, fmt);
             int& occ = c->i3_occ[ua ? 2 : (tagk ? 1 : 0)][st32 ? 3 : fmt][T / 64];
             if (occ == 0) {
                 int per = 0;
-                hipError_t e;
-                if (ua)
-                    e = st32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<3, true>, (int)T, 0)
-                      : fmt == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<2, true>, (int)T, 0)
-                      : fmt == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<1, true>, (int)T, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<0, true>, (int)T, 0);
-                else if (st32)
-                    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<3>, (int)T, 0);
-                else if (tagk)
-                    e = fmt == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<2>, (int)T, 0)
-                      : fmt == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<1>, (int)T, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3t<0>, (int)T, 0);
-                else
-                    e = fmt == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3<2>, (int)T, 0)
-                      : fmt == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3<1>, (int)T, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_intersect3<0>, (int)T, 0);
+                const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, (int)T, 0);
                 occ = (e == hipSuccess && per >= 1) ? per : 1;
             }
             const u32 grid = std::min<u32>(a3.nitems, (u32)(occ * c->ncu));
             {
                 StageScope sc(c, KR_ST_INTERSECT, st);
                 c->i3_last_ua = ua ? 1 : 0;
-                if (ua) {
-                    c->isect_ua++;
-                    if (st32) hipLaunchKernelGGL((k_intersect3t<3, true>), dim3(grid), dim3(T), 0, st, a3, g);
-                    else if (fmt == 2) hipLaunchKernelGGL((k_intersect3t<2, true>), dim3(grid), dim3(T), 0, st, a3, g);
-                    else if (fmt == 1) hipLaunchKernelGGL((k_intersect3t<1, true>), dim3(grid), dim3(T), 0, st, a3, g);
-                    else hipLaunchKernelGGL((k_intersect3t<0, true>), dim3(grid), dim3(T), 0, st, a3, g);
-                } else if (st32) {
-                    hipLaunchKernelGGL(k_intersect3t<3>, dim3(grid), dim3(T), 0, st, a3, g);
-                } else if (tagk) {
-                    if (fmt == 2) hipLaunchKernelGGL(k_intersect3t<2>, dim3(grid), dim3(T), 0, st, a3, g);
-                    else if (fmt == 1) hipLaunchKernelGGL(k_intersect3t<1>, dim3(grid), dim3(T), 0, st, a3, g);
-                    else hipLaunchKernelGGL(k_intersect3t<0>, dim3(grid), dim3(T), 0, st, a3, g);
-                } else if (fmt == 2) hipLaunchKernelGGL(k_intersect3<2>, dim3(grid), dim3(T), 0, st, a3, g);
-                else if (fmt == 1) hipLaunchKernelGGL(k_intersect3<1>, dim3(grid), dim3(T), 0, st, a3, g);
-                else hipLaunchKernelGGL(k_intersect3<0>, dim3(grid), dim3(T), 0, st, a3, g);
+                if (ua) c->isect_ua++;
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(T), 0, st, a3, g);
                 a.ovf = (const u32*)c->isovf.p;
                 a.ovf_cap = c->i3_ovf_cap;
                 a.mlog = mlog;
@@ -529,39 +501,6 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         if ((rc = cands_fit(c, running, "kr_intersect"))) return rc;
     }
     HIPCHK(c, hipGetLastError());        // (no wait for the last gather: everything that reads the list is ordered behind it)
-    if (split) {
-        // the late genomes: their sorts are waited for on the device, the words every open sort left are published
-        // behind them, and the candidates look their prefixes up
-        st = c->stream;         // (the big intersection is complete: the host waited for its totals)
-        if ((rc = join_lanes(c))) return rc;
-        for (int q = n1; q < n; q++) HIPCHK(c, hipStreamWaitEvent(st, gs[q]->sort_ev, 0));
-        if (pending) {
-            if (open_slices.size() > PUB_CAP) {
-                if ((rc = finalize(c, gs))) return rc;
-                pending = false;
-            } else {
-                publish_slices(c, open_slices.data(), open_slices.size(), st);
-            }
-        }
-        c->ncand = (int64_t)running;
-        c->isect_splits++;
-        c->isect_probed = (int64_t)running;
-        if (running) {
-            IsectArgs pa{};
-            pa.n = n - n1;
-            pa.apply_filter = fmode(c, 1);
-            for (int q = n1; q < n; q++) {
-                pa.keys[q - n1] = (const u64*)gs[q]->sl[0].keys.p;
-                pa.off[q - n1] = (const u32*)gs[q]->sl[0].off.p;
-                if (is_in[ord[q]]) pa.ingroup_bits |= 1u << (q - n1);
-            }
-            const int64_t left = cands_probe_device(c, pa);
-            if (left < 0) return left;
-            running = (u64)left;
-        } else if (pending) {
-            HIPCHK(c, hipStreamSynchronize(st));
-        }
-    }
     if (pending) {
         if ((rc = finalize(c, gs, true, redo))) return rc;
         if (*redo) return 0;
@@ -603,58 +542,21 @@ static int64_t cands_merge_device(kr_ctx* c, size_t m, int have_other, int apply
     hipStream_t st = c->stream;
     int rc;
     const u32 nblk = (n + 255) / 256;
-    if ((rc = ensure(c, c->flags, (size_t)n * 4))) return rc;
-    if ((rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4))) return rc;
-    if ((rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4))) return rc;
-    if ((rc = ensure(c, c->candA, ((size_t)n + 2) * sizeof(kr_cand)))) return rc;
+    if ((rc = cands_compact_room(c, n))) return rc;
     if ((rc = ensure(c, c->other, 64))) return rc;
+    const u32* dtotal;
     {
         StageScope sc(c, KR_ST_MERGE);
         hipLaunchKernelGGL(k_cands_flag, dim3(nblk), dim3(256), 0, st, (kr_cand*)c->candB.p, n,
                            (const kr_cand*)c->other.p, (u32)m, have_other ? 1 : 0, fmode(c, apply_filter), c->g.D,
                            (u32*)c->flags.p, (u32*)c->blockcnt.p, (const u64*)nullptr);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
-        hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, n,
-                           (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
+        dtotal = cands_compact_enqueue(c, n, st, false);
     }
     u32 total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, (u32*)c->blockpos.p + nblk, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&total, dtotal, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    std::swap(c->candA, c->candB);
-    c->ncand = total;
-    return total;
-}
-
-// candidates := those whose prefix every genome of `pa` holds, these genomes' diagnostic bases OR-ed into the masks, the
-// filter applied (k_cands_probe); returns the new count
-static int64_t cands_probe_device(kr_ctx* c, const IsectArgs& pa) {
-    if (cands_fit(c, (uint64_t)c->ncand, "kr_intersect")) return KR_ERR_CAPACITY;
-    const u32 n = (u32)c->ncand;
-    if (n == 0) return 0;
-    hipStream_t st = c->stream;
-    int rc;
-    const u32 nblk = (n + 255) / 256;
-    if ((rc = ensure(c, c->flags, (size_t)n * 4))) return rc;
-    if ((rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4))) return rc;
-    if ((rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4))) return rc;
-    if ((rc = ensure(c, c->candA, ((size_t)n + 2) * sizeof(kr_cand)))) return rc;
-    {
-        StageScope sc(c, KR_ST_MERGE);
-        hipLaunchKernelGGL(k_cands_probe, dim3(nblk), dim3(256), 0, st, (kr_cand*)c->candB.p, n, pa, slice_geom(c, 0),
-                           (u32*)c->flags.p, (u32*)c->blockcnt.p);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
-        hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, n,
-                           (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
-        hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, (const u32*)c->blockpos.p + nblk, (const u32*)nullptr,
-                           (const u32*)nullptr, c->mbox + 16);
-    }
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    const u32 total = ((volatile u32*)c->mbox)[16];
-    std::swap(c->candA, c->candB);
-    c->ncand = total;
-    return total;
+    return cands_compact_adopt(c, total);
 }
 
 // candidates := those whose (left,right) prefix EVERY listed genome holds, the genomes' diagnostic bases OR-ed into the
@@ -709,27 +611,17 @@ static int64_t cands_probe_impl(kr_ctx* c, const int* ids, int n, const uint8_t*
         a.arena = nullptr;
         a.mcnt = nullptr;
         const u32 nc = (u32)c->ncand, nblk = (nc + 255) / 256;
-        if ((rc = ensure(c, c->flags, (size_t)nc * 4))) return rc;
-        if ((rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4))) return rc;
-        if ((rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4))) return rc;
-        if ((rc = ensure(c, c->candA, ((size_t)nc + 2) * sizeof(kr_cand)))) return rc;
+        if ((rc = cands_compact_room(c, nc))) return rc;
         {
             StageScope sc(c, KR_ST_MERGE);
             // (the filter with the last batch of 32 only: before it the masks are not complete -- but partial masks may prune, it is monotone)
             hipLaunchKernelGGL(k_cands_probe_tab, dim3(nblk), dim3(256), 0, st, (kr_cand*)c->candB.p, nc, a, bits, fmode(c, apply_filter),
                                slice_geom(c, 0), (u32*)c->flags.p, (u32*)c->blockcnt.p);
-            hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
-            hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, nc,
-                               (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
-            hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, (const u32*)c->blockpos.p + nblk, (const u32*)nullptr,
-                               (const u32*)nullptr, c->mbox + 16);
+            cands_compact_enqueue(c, nc, st, true);
         }
         HIPCHK(c, hipStreamSynchronize(st));        // (also: `tab` may go out of scope now)
         HIPCHK(c, hipGetLastError());
-        const u32 total = ((volatile u32*)c->mbox)[16];
-        std::swap(c->candA, c->candB);
-        c->ncand = total;
-        if (total == 0) break;
+        if (cands_compact_adopt(c, ((volatile u32*)c->mbox)[16]) == 0) break;
     }
     return c->ncand;
 }

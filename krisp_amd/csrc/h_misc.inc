@@ -297,8 +297,7 @@ int kr_debug_isect(kr_ctx* c, int64_t* o) {
     o[3] = c->i3_last_mlog;
     o[4] = c->i3_last_tags;
     o[5] = lanes_used(c);
-    o[6] = c->isect_splits;       // intersections that left their late genomes to the probe
-    o[7] = c->isect_probed;       // candidates the latest of them probed
+    o[6] = o[7] = 0;              // (unused)
     return KR_OK;
 }
 

@@ -128,25 +128,18 @@ static int64_t wide_phase(kr_ctx* c, const int* ids, int n, const uint8_t* is_in
     if (canonical && nc > 0) {
         // Dict.canon: of a spectrum closed under reverse complement only the canonical flanks are kept (the list stays sorted)
         const u32 n0 = (u32)nc, nblk = (n0 + 255) / 256;
-        if ((rc = ensure(c, c->flags, (size_t)n0 * 4))) return rc;
-        if ((rc = ensure(c, c->blockcnt, ((size_t)nblk + 2) * 4))) return rc;
-        if ((rc = ensure(c, c->blockpos, ((size_t)nblk + 2) * 4))) return rc;
-        if ((rc = ensure(c, c->candA, ((size_t)n0 + 2) * sizeof(kr_cand)))) return rc;
+        if ((rc = cands_compact_room(c, n0))) return rc;
         if ((rc = ensure(c, c->wide.tsum, 64))) return rc;
         HIPCHK(c, hipMemsetAsync(c->wide.tsum.p, 0, 4, st));
         hipLaunchKernelGGL(k_flag_canonical, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, n0, flank_len,
                            (u32*)c->flags.p, (u32*)c->blockcnt.p, (u32*)c->wide.tsum.p);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->blockcnt.p, (u32*)c->blockpos.p, nblk);
-        hipLaunchKernelGGL(k_cands_compact, dim3(nblk), dim3(256), 0, st, (const kr_cand*)c->candB.p, n0,
-                           (const u32*)c->flags.p, (const u32*)c->blockpos.p, (kr_cand*)c->candA.p);
+        const u32* dkept = cands_compact_enqueue(c, n0, st, false);
         u32 kept = 0, npal = 0;
-        HIPCHK(c, hipMemcpyAsync(&kept, (u32*)c->blockpos.p + nblk, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&kept, dkept, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(&npal, c->wide.tsum.p, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (2ull * kept - npal == n0) {      // (closed under reverse complement, as the packed spectra are: else the full list stays)
-            std::swap(c->candA, c->candB);
-            c->ncand = kept;
-            nc = kept;
+            nc = cands_compact_adopt(c, kept);
             d.canon = true;
         }
     }

@@ -707,47 +707,12 @@ __global__ void k_cands_flag(kr_cand* __restrict__ cur, u32 n, const kr_cand* __
     if (threadIdx.x == 0) blockcnt[blockIdx.x] = tot;
 }
 
-// Round 4: the genomes whose sorts end last join a candidate list instead of the big intersection.  The intersection
-// over the EARLY genomes ran beside the late sorts and was pruned with the diagnostic filter on its partial masks -- safe,
-// the predicate is monotone (masks only grow) -- so the list is short; here every candidate looks its prefix up in each
-// late genome (a.keys / a.off [0 .. a.n), a.ingroup_bits by position): absent anywhere -> dropped; else the genome's
-// diagnostic bases join the masks and the filter is applied again.  flags / blockcnt as k_cands_flag leaves them.
-__global__ void k_cands_probe(kr_cand* __restrict__ cur, u32 n, IsectArgs a, Geom g, u32* __restrict__ flags,
-                              u32* __restrict__ blockcnt) {
-    __shared__ u32 waves[17];
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    bool keep = false;
-    if (i < n) {
-        kr_cand c = cur[i];
-        keep = true;
-        const u64 pre = c.prefix;                       // (one sort unit: relative = absolute)
-        for (int gi = 0; gi < a.n && keep; gi++) {
-            const u64* __restrict__ K = a.keys[gi];
-            u32 e;
-            u32 p = collect_lower_bound(K, a.off[gi], pre, g, e);
-            u64 dm = 0;
-            bool found = false;
-            for (; p < e; p++) {
-                const u64 key = K[p];
-                if ((key & g.pmask) != pre) break;
-                found = true;
-                dm |= diag_mask(key, g.LRrel, g.D);
-            }
-            keep = found;
-            if ((a.ingroup_bits >> gi) & 1u) c.in_mask |= dm; else c.out_mask |= dm;
-        }
-        if (keep && a.apply_filter && g.D > 0) keep = passes_filter(c.in_mask, c.out_mask, g.D, a.apply_filter);
-        if (keep) cur[i] = c;
-        flags[i] = keep ? 1u : 0u;
-    }
-    u32 tot;
-    block_compact(keep, waves, tot);
-    if (threadIdx.x == 0) blockcnt[blockIdx.x] = tot;
-}
-
-// The same probe over genomes given as tables [genome][slice] (kr_cands_probe, round 5: the streaming flow of genome sets
-// beyond one GPU's memory -- a later batch's genomes look the running candidates up instead of being intersected whole):
-// slice-aware as k_collect_count is (the candidate's slice = the top bits of its absolute prefix).
+// Genomes join a candidate list instead of an intersection (kr_cands_probe, round 5: the streaming flow of genome sets
+// beyond one GPU's memory -- a later batch's genomes look the running candidates up instead of being intersected whole).
+// Every candidate looks its prefix up in each genome, given as tables [genome][slice] (ingroup_bits by position): absent
+// anywhere -> dropped; else the genome's diagnostic bases join the masks and the filter is applied -- safe on partial
+// masks, the predicate is monotone (masks only grow).  flags / blockcnt as k_cands_flag leaves them; slice-aware as
+// k_collect_count is (the candidate's slice = the top bits of its absolute prefix).
 __global__ void k_cands_probe_tab(kr_cand* __restrict__ cur, u32 n, CollectArgs a, u32 ingroup_bits, int apply_filter, Geom g,
                                   u32* __restrict__ flags, u32* __restrict__ blockcnt) {
     __shared__ u32 waves[17];

@@ -27,7 +27,6 @@ KR_LANES=4 run configs1_four_sort_lanes --config 1 --steps 10 --warmup 2 --no-cp
 KR_ISECT_KERNEL=1 run configs1_chunk_intersect_kernel --config 1 --steps 10 --warmup 2 --no-cpu-baseline
 KR_ISECT_KERNEL=2 run configs1_pipelined_64bit_heads --config 1 --steps 10 --warmup 2 --no-cpu-baseline
 KR_ISECT_FMT=2 run configs1_32bit_heads_64bit_state --config 1 --steps 10 --warmup 2 --no-cpu-baseline
-KR_ISECT_SPLIT=1 run configs1_late_genomes_probe --config 1 --steps 10 --warmup 2 --no-cpu-baseline
 run configs3_per_gpu_load_4x100Mbp --config 3 --steps 10 --warmup 2 --no-cpu-baseline
 run configs3_all_32x100Mbp_one_gpu --config 3 --per-gpu 32 --steps 3 --warmup 1 --no-cpu-baseline
 fi
