@@ -524,6 +524,35 @@ int64_t kr_guide_hits_fetch(kr_ctx*, kr_guide_hit* out, size_t cap);
  * size query */
 int64_t kr_guide_hits_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
 
+/* ---- guide hits with a bulge: in the locate context of kr_guide_hits_*, with a state of its own (a table and
+ * a scan of either pass do not disturb the other's).  A bulged hit of size b is a window of G + b bases (a DNA bulge: b
+ * bases of the genome have no partner) or G - b bases (an RNA bulge: b letters of the guide have none) that lies within
+ * `mismatches` columns of a guide's protospacer, or of its reverse complement, when cut at one place inside the guide:
+ * one contiguous bulge, never at an end.
+ * kr_guide_bulges_table: as kr_guide_hits_table, with bulges = the largest b (1 or 2).  The seeds are the guides' halves of
+ * (G - bulges) / 2 letters, searched by the near-match scan.  Returns the number of slots of the seed table.  KR_ERR_PARAM
+ * as kr_guide_hits_table, and for bulges outside 1 .. 2, G below 20 or mismatches above 2 (shorter or looser halves seed
+ * nearly every window); KR_ERR_CAPACITY for 2^23 guides or more, or a table that does not fit.  kr_set_params_locate drops
+ * the table (its texts are rows of G letters): a scan after it, before a new table, is KR_ERR_PARAM. */
+int64_t kr_guide_bulges_table(kr_ctx*, const uint8_t* texts, uint64_t nguides, int mismatches, int bulges, const char* pam5,
+                              const char* pam3, int need_pam);
+/* one bulged hit, 32 bytes: guide, strand, pam as in kr_guide_hit; mismatches = the least number of aligned columns that
+ * differ over the cuts; bulge = +b for a DNA bulge, -b for an RNA bulge; pos = the window's first base, length = G + bulge
+ * its bases; bulge_column = the guide columns that lie 5' of the bulge on the guide's strand (of the cuts with the least
+ * mismatches the smallest); columns bit c = aligned guide column c differs, 5'->3' on the protospacer (a column without a
+ * partner is never set).  One row per (guide, strand, bulge, pos). */
+typedef struct { uint32_t guide; uint8_t strand, mismatches, pam; int8_t bulge; uint64_t pos; uint64_t columns;
+                 uint32_t bulge_column, length; } kr_guide_bulge_hit;
+/* scans uploaded genome `id`: returns the number of bulged hits, kept on the device for the fetch, in the order of the seed
+ * pairs that own them (position of the seed, seed piece, the table's entry order), a pair's rows by DNA 1, RNA 1, DNA 2,
+ * RNA 2.  Counted, scanned, written: the same bytes on every run.  KR_ERR_PARAM before a table; KR_ERR_CAPACITY for 2^32
+ * seed pairs or hits or more, or lists that do not fit. */
+int64_t kr_guide_bulges_scan(kr_ctx*, int id);
+int64_t kr_guide_bulges_fetch(kr_ctx*, kr_guide_bulge_hit* out, size_t cap);
+/* the hits' windows as the guide's strand reads them: row i = G + bulges bytes, the `length` letters of hit i (upper case,
+ * the reverse complement for strand 1), then 0.  Returns the number of rows; rows == NULL: size query */
+int64_t kr_guide_bulges_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

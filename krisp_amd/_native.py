@@ -35,6 +35,8 @@ GUIDE_RECORD = np.dtype([("found", "<u4"), ("strand", "<u4"), ("start", "<u4"), 
                          ("sum_mismatches", "<u4"), ("gc", "<u4"), ("candidates", "<u4"), ("pad", "<u4")])    # kr_guide_record
 GUIDE_HIT_RAW = np.dtype([("guide", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("pam", "u1"), ("pad", "u1"), ("pos", "<u8"),
                           ("columns", "<u8")])                                 # kr_guide_hit
+GUIDE_BULGE_HIT_RAW = np.dtype([("guide", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("pam", "u1"), ("bulge", "i1"),
+                                ("pos", "<u8"), ("columns", "<u8"), ("bulge_column", "<u4"), ("length", "<u4")])   # kr_guide_bulge_hit
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 WIDE_MAX_K = 1024
 WIDE_MAX_FLANK = 256
@@ -137,6 +139,10 @@ SYMBOLS = [
     ("kr_guide_hits_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_guide_hits_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_hits_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_guide_bulges_table", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_char_p, _c.c_char_p, _c.c_int]),
+    ("kr_guide_bulges_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_guide_bulges_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_guide_bulges_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -772,6 +778,35 @@ class Engine:
         out = np.empty((max(n, 1), G), dtype=np.uint8)
         if n:
             self._check(self.lib.kr_guide_hits_windows(self.ctx, _ptr(out), out.nbytes), "kr_guide_hits_windows")
+        return out[:n]
+
+    def guide_bulges_table(self, texts, mismatches, bulges, pam5="", pam3="", need_pam=False):
+        """as guide_hits_table, for the bulged search with bulges of 1 .. `bulges` bases (1 or 2): the seed table of the
+        guides' halves -> its slots (kr_guide_bulges_table).  A state of its own beside guide_hits_table's"""
+        t = np.ascontiguousarray(texts, dtype=np.uint8)
+        # (the library reads len(t) rows of L+D+R bytes: another shape would be read past its end)
+        k = sum(self.params) if self.params is not None else None
+        if t.size and (t.ndim != 2 or (k is not None and t.shape[1] != k)):
+            raise ValueError(f"guide_bulges_table: texts is a matrix with a row of L+D+R = {k} letters per guide (got shape {t.shape})")
+        as_bytes = lambda m: m if isinstance(m, bytes) else str(m).encode("ascii", "replace")      # noqa: E731
+        return self._check(self.lib.kr_guide_bulges_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches, bulges,
+                                                          as_bytes(pam5), as_bytes(pam3), 1 if need_pam else 0), "kr_guide_bulges_table")
+
+    def guide_bulges(self, gid):
+        """GUIDE_BULGE_HIT_RAW array of uploaded genome gid against the guides' table: the bulged hits, in the order of the
+        seed pairs that own them (kr_guide_bulges_scan)"""
+        n = self._check(self.lib.kr_guide_bulges_scan(self.ctx, gid), "kr_guide_bulges_scan")
+        out = np.empty(max(n, 1), dtype=GUIDE_BULGE_HIT_RAW)
+        self._check(self.lib.kr_guide_bulges_fetch(self.ctx, _ptr(out), n), "kr_guide_bulges_fetch")
+        return out[:n]
+
+    def guide_bulge_windows(self, width):
+        """the latest guide_bulges()'s windows as the guide's strand reads them, cut on the device: uint8 [nhits, width],
+        width = G + bulges; row i holds hit i's `length` letters, then 0 (kr_guide_bulges_windows)"""
+        n = self._check(self.lib.kr_guide_bulges_windows(self.ctx, None, 0), "kr_guide_bulges_windows")
+        out = np.empty((max(n, 1), width), dtype=np.uint8)
+        if n:
+            self._check(self.lib.kr_guide_bulges_windows(self.ctx, _ptr(out), out.nbytes), "kr_guide_bulges_windows")
         return out[:n]
 
     def products_table(self, left, right, pairs, mismatches, max_product):

@@ -249,6 +249,16 @@ struct kr_ctx {
         int gid = -1;                   // the genome of the latest kr_guide_hits_scan
         DevBuf arena, table, list, bitmap, pairs, hits, kept, rows;    // pairs: the scan's list; kept: what need_pam leaves (it changes places with hits)
     } ghit;
+    // the bulged guide-hit pass (kr_guide_bulges_*: h_guide_bulges.inc), in the same context: a state of its own beside ghit.
+    // arena / table / list / bitmap: the seed table of the guides' halves of h letters; texts: the entries' whole text
+    struct Gbulge {
+        int M = 0, B = 0;
+        u32 h = 0, sets5 = 0, a = 0, sets3 = 0, b = 0, need = 0;
+        u64 nguides = 0, slots = 0;
+        int64_t nhits = -1;
+        int gid = -1;                   // the genome of the latest kr_guide_bulges_scan
+        DevBuf arena, table, list, bitmap, texts, pairs, hits, rows;
+    } gbulge;
     // the product pass (kr_products_*: h_products.inc), in the locate context: loc.L / loc.R are the texts' lengths
     struct Prod {
         int M = 0;
@@ -662,6 +672,9 @@ void kr_destroy(kr_ctx* c) {
         auto& gh = c->ghit;
         DevBuf* hb[] = {&gh.arena, &gh.table, &gh.list, &gh.bitmap, &gh.pairs, &gh.hits, &gh.kept, &gh.rows};
         for (DevBuf* b : hb) release(c, *b);
+        auto& gbu = c->gbulge;
+        DevBuf* bb[] = {&gbu.arena, &gbu.table, &gbu.list, &gbu.bitmap, &gbu.texts, &gbu.pairs, &gbu.hits, &gbu.rows};
+        for (DevBuf* b : bb) release(c, *b);
         auto& pr = c->prod;
         DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.pairkeys, &pr.pairidx, &pr.seps, &pr.sites, &pr.rec, &pr.hits};
         for (DevBuf* b : pb) release(c, *b);

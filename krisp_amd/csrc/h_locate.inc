@@ -25,7 +25,9 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     c->near.nhits = -1;
     c->ghit.slots = c->ghit.nguides = 0;        // (likewise: kr_guide_hits_table again)
     c->ghit.nhits = -1;
-    c->prod.slots = 0;                          // (likewise: kr_products_table again)
+    c->gbulge.slots = c->gbulge.nguides = 0;    // (likewise: kr_guide_bulges_table again -- its texts are rows of G letters)
+    c->gbulge.nhits = -1;
+    c->prod.slots = 0;                         // (likewise: kr_products_table again)
     c->prod.nsites = c->prod.nhits = -1;
     c->prim.slots = 0;                          // (another soft-mask mode: kr_primers_table again)
     c->prim.nsites = c->prim.nhits = -1;

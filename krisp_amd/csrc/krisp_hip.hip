@@ -47,6 +47,7 @@
 #include "k_locate.inc"      // the locate pass: flank-table scan of a genome's bases
 #include "k_near.inc"        // the near-match pass: pigeonhole seeds of the targets, scan within Hamming distance M
 #include "k_guide_hits.inc"  // the guide-hit pass: behind the near pass's scan a per-hit step (ghit_step.inc: column mask, PAM motifs), need_pam's selection
+#include "k_guide_bulges.inc" // the bulged guide-hit pass: the near scan over the guides' halves, a per-pair step (gbulge_step.inc) for DNA / RNA bulges
 
 #include "k_products.inc"    // the product pass: sites of the flanks within M substitutions, joined into PCR products
 #include "k_primers.inc"     // the primer-product pass: sites of primer texts of mixed lengths, joined into PCR products
@@ -60,6 +61,7 @@
 #include "h_locate.inc"      // kr_set_params_locate, kr_locate_*: where the surviving groups' windows lie
 #include "h_near.inc"        // kr_near_*: the windows of a genome within M substitutions of an ingroup window
 #include "h_guide_hits.inc"  // kr_guide_hits_*: the windows of a genome within M substitutions of a picked guide, with their motifs
+#include "h_guide_bulges.inc" // kr_guide_bulges_*: the windows of a genome within M substitutions and one bulge of a picked guide
 #include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome
 #include "h_primers.inc"     // kr_primers_*: in-silico PCR of designed primer pairs against a genome
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options

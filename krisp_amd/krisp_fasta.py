@@ -1850,8 +1850,21 @@ def guide_texts(templates, records, guide_size, regions=None):
 GUIDE_HIT_MAX_MISMATCHES = 3
 
 
-def guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam):
-    """why the guide-hit pass does not take these figures (one line), or None"""
+GUIDE_HIT_MAX_BULGES = 2
+GUIDE_BULGE_MIN_SIZE = 20           # with --guide-hit-bulges: the seeds are the guides' halves, (guide size - bulges) / 2 letters
+GUIDE_BULGE_MAX_MISMATCHES = 2      # ... and each is searched within the mismatches: shorter or looser, nearly every window is a seed
+
+
+def guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam, bulges=0):
+    """why the guide-hit pass does not take these figures (one line), or None.  bulges: --guide-hit-bulges"""
+    if bulges < 0 or bulges > GUIDE_HIT_MAX_BULGES:
+        return f"--guide-hit-bulges must lie between 0 and {GUIDE_HIT_MAX_BULGES} (got {bulges})"
+    if bulges and guide_size < GUIDE_BULGE_MIN_SIZE:
+        return (f"--guide-hit-bulges needs --guide-size >= {GUIDE_BULGE_MIN_SIZE} (got {guide_size}): the bulged search seeds with "
+                "half-guides, and halves of fewer than 9 letters lie within the mismatches of nearly every window (DESIGN §20, cost)")
+    if bulges and mismatches > GUIDE_BULGE_MAX_MISMATCHES:
+        return (f"--guide-hit-bulges needs --guide-hit-mismatches <= {GUIDE_BULGE_MAX_MISMATCHES} (got {mismatches}): a half-guide "
+                "within 3 mismatches seeds millions of windows per guide and genome (DESIGN §20, cost)")
     if guide_size < GUIDE_MIN_SIZE or guide_size > GUIDE_MAX_SIZE:
         return f"--guide-size must lie between {GUIDE_MIN_SIZE} and {GUIDE_MAX_SIZE} (got {guide_size})"
     if mismatches < 0 or mismatches > GUIDE_HIT_MAX_MISMATCHES:
@@ -1938,6 +1951,96 @@ def write_guide_hits(path, rows):
                          rows["region"].tolist(), rows["file"], rows["record"], rows["record_index"].tolist(),
                          rows["start"].tolist(), rows["end"].tolist(), rows["strand"], rows["mismatches"].tolist(),
                          rows["mismatch_columns"], rows["pam5_match"].tolist(), rows["pam3_match"].tolist(), rows["sequence"]))
+
+
+GUIDE_BULGE_HIT_HEADER = GUIDE_HIT_HEADER + "\tbulge\tbulge_size\tbulge_column"
+GUIDE_BULGE_HIT = np.dtype(GUIDE_HIT.descr + [("bulge", "O"), ("bulge_size", "<u4"), ("bulge_column", "O")])
+
+
+def guide_bulge_hits(texts, text_regions, ingroup_files, outgroup_files, guide_size, mismatches=2, bulges=1, pam5="", pam3="",
+                     need_pam=False, omit_soft=False, device=0):
+    """Every window of every input genome that lies within `mismatches` substitutions of a picked guide's protospacer once
+    one bulge of 1 .. `bulges` bases is allowed for, on both strands (--guide-hit-bulges): a DNA bulge (the
+    genome holds bases the guide has no partner for: the window has guide_size + b bases) or an RNA bulge (guide letters
+    have no partner: guide_size - b bases).  One contiguous bulge, never at a guide end; a window's row carries the least
+    number of mismatches over the places of the bulge and, of those that reach it, the one nearest the guide's 5' end.
+    The arguments and the rows' order are guide_hits'; the unbulged hits are guide_hits' own and no part of the result.
+    (kr_guide_bulges_*: the near pass's scan over the guides' halves, a per-pair step that extends each seed.)  Returns a
+    GUIDE_BULGE_HIT array: GUIDE_HIT's fields -- end = start + guide_size +- b, mismatch_columns of the aligned columns
+    only, sequence = the window on the guide's strand -- and bulge ("DNA" / "RNA"), bulge_size, bulge_column (the
+    1-based guide column after which the bulge lies).  Rows in (region, file in command-line order, record_index, start,
+    '+' before '-', end) order.  ValueError for figures the pass does not take (guide_hits_refusal)."""
+    why = guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam, bulges=bulges)
+    if why is None and bulges < 1:
+        why = f"guide_bulge_hits: bulges is 1 or 2 (got {bulges})"
+    if why is not None:
+        raise ValueError(why)
+    if len(texts) != len(text_regions):
+        raise ValueError(f"guide_bulge_hits: {len(texts)} texts, the regions of {len(text_regions)}")
+    files = list(ingroup_files) + list(outgroup_files)
+    G, W = guide_size, guide_size + bulges
+    if len(texts) == 0:
+        return np.empty(0, dtype=GUIDE_BULGE_HIT)
+    if any(len(t) != G for t in texts):
+        raise ValueError(f"guide_bulge_hits: every text has --guide-size = {G} letters")
+    t_bytes = np.frombuffer(b"".join(bytes(t) for t in texts), dtype=np.uint8).reshape(-1, G)
+    n_regions = np.array([len(r) for r in text_regions], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(n_regions)])
+    flat = np.array([r for rs in text_regions for r in rs], dtype=np.uint32)
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, 0, G, 0, G, omit_soft, device,
+                                                   lambda eng: eng.guide_bulges_table(t_bytes, mismatches, bulges, pam5, pam3, need_pam)):
+        hits = eng.guide_bulges(0)
+        if len(hits) == 0:
+            continue
+        rows = eng.guide_bulge_windows(W)
+        seps, ids = names()
+        shared = np.empty(len(hits), dtype=GUIDE_BULGE_HIT)
+        _fill_shared(shared, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        length = hits["length"].astype(np.int64)
+        shared["end"] = shared["start"] + length
+        shared["mismatches"] = hits["mismatches"]
+        shared["mismatch_columns"] = [_mask_columns(m) for m in hits["columns"].tolist()]
+        shared["pam5_match"] = hits["pam"] & 1
+        shared["pam3_match"] = (hits["pam"] >> 1) & 1
+        padded = _rows_text(np.where(rows == 0, np.uint8(ord(" ")), rows), W, rna)
+        shared["sequence"] = [t[:n] for t, n in zip(padded, length.tolist())]
+        shared["bulge"] = np.where(hits["bulge"] > 0, "DNA", "RNA").astype(object)
+        shared["bulge_size"] = np.abs(hits["bulge"].astype(np.int64))
+        shared["bulge_column"] = [str(c) for c in hits["bulge_column"].tolist()]
+        # hit h of text t becomes the rows [begin[h], begin[h] + cnt[h]), one per region of t
+        gd = hits["guide"].astype(np.int64)
+        cnt = n_regions[gd]
+        begin = np.cumsum(cnt) - cnt
+        rep = np.repeat(np.arange(len(hits)), cnt)
+        part = shared[rep]
+        part["region"] = flat[first[gd[rep]] + np.arange(len(rep)) - begin[rep]]
+        # (a region's rows at one start and strand differ in their end: G + 1, G - 1, G + 2, G - 2)
+        order = np.lexsort((part["end"], part["strand"] == "-", part["start"], part["record_index"], part["region"]))
+        parts.append((fi, part[order], part["region"][order]))
+    return _sorted_parts(parts, GUIDE_BULGE_HIT)
+
+
+def write_guide_bulge_hits(path, rows, bulged, files):
+    """the TSV of the guide hits under --guide-hit-bulges: GUIDE_BULGE_HIT_HEADER, then guide_hits' rows (with -, 0, - in the
+    three bulge columns) and guide_bulge_hits' rows, merged by (region, file in the order of `files`, record_index, start,
+    '+' before '-', end)"""
+    both = np.empty(len(rows) + len(bulged), dtype=GUIDE_BULGE_HIT)
+    head = both[:len(rows)]
+    for name in GUIDE_HIT.names:
+        head[name] = rows[name]
+    head["bulge"] = "-"
+    head["bulge_size"] = 0
+    head["bulge_column"] = "-"
+    both[len(rows):] = bulged
+    index = {}
+    for i, f_ in enumerate(files):
+        index.setdefault(f_, i)
+    fidx = np.array([index[f_] for f_ in both["file"]], dtype=np.int64)
+    both = both[np.lexsort((both["end"], both["strand"] == "-", both["start"], both["record_index"], fidx, both["region"]))]
+    with open(path, "w") as f:
+        f.write(GUIDE_BULGE_HIT_HEADER + "\n")
+        f.writelines("\t".join(str(x) for x in r) + "\n" for r in both.tolist())
 
 
 # ----------------------------------------------------------------------------
@@ -2375,6 +2478,12 @@ def build_parser():
                         "--out_guides.  (default: no search)")
     p.add_argument("--guide-hit-mismatches", type=int, default=None, metavar="INT",
                    help="Hamming distance of --out_guide_hits: 0 .. 3 (default: 2)")
+    p.add_argument("--guide-hit-bulges", type=int, default=None, metavar="INT",
+                   help="--out_guide_hits also lists the windows that match a protospacer once one bulge of up to INT bases is\n"
+                        "allowed for: a DNA bulge (bases of the genome without a partner in the guide) or an RNA bulge (guide\n"
+                        "letters without a partner), 0 .. 2.  The file gains the columns bulge (-, DNA, RNA), bulge_size and\n"
+                        "bulge_column (the 1-based guide column after which the bulge lies).  Needs --guide-size >= 20 and\n"
+                        "--guide-hit-mismatches <= 2; one more pass over the inputs.  (default: 0, no bulges)")
     p.add_argument("--guide-hits-need-pam", action="store_true",
                    help="--out_guide_hits lists a window only where --pam5 and --pam3 lie beside it (needs one of the two)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
@@ -2525,14 +2634,18 @@ def main(argv=None):
     if args.out_guide_hits is not None and args.out_guides is None:
         print("ERROR: --out_guide_hits needs --out_guides (the guides it searches for)", file=sys.stderr)
         sys.exit(2)
-    for opt, val in (("--guide-hit-mismatches", args.guide_hit_mismatches), ("--guide-hits-need-pam", args.guide_hits_need_pam or None)):
+    for opt, val in (("--guide-hit-mismatches", args.guide_hit_mismatches), ("--guide-hits-need-pam", args.guide_hits_need_pam or None),
+                     ("--guide-hit-bulges", args.guide_hit_bulges)):
         if val is not None and args.out_guide_hits is None:
             print(f"ERROR: {opt} needs --out_guide_hits", file=sys.stderr)
             sys.exit(2)
     if args.out_guide_hits is not None:
         if args.guide_hit_mismatches is None:
             args.guide_hit_mismatches = 2
-        why = guide_hits_refusal(args.guide_size, args.guide_hit_mismatches, args.pam5, args.pam3, args.guide_hits_need_pam)
+        if args.guide_hit_bulges is None:
+            args.guide_hit_bulges = 0
+        why = guide_hits_refusal(args.guide_size, args.guide_hit_mismatches, args.pam5, args.pam3, args.guide_hits_need_pam,
+                                 bulges=args.guide_hit_bulges)
         if why is not None:
             print("ERROR: " + why, file=sys.stderr)
             sys.exit(2)
@@ -2658,10 +2771,17 @@ def main(argv=None):
             if args.verbose:
                 print(f"Searching every genome for the guides with up to {args.guide_hit_mismatches} mismatches ... ", file=sys.stderr)
             texts, text_regions = guide_texts(templates[0], guides, args.guide_size, regions=regions)
-            write_guide_hits(args.out_guide_hits,
-                             guide_hits(texts, text_regions, args.files, args.outgroup, args.guide_size,
-                                        mismatches=args.guide_hit_mismatches, pam5=args.pam5, pam3=args.pam3,
-                                        need_pam=args.guide_hits_need_pam, omit_soft=args.omit_soft, device=locate_device))
+            how = dict(mismatches=args.guide_hit_mismatches, pam5=args.pam5, pam3=args.pam3, need_pam=args.guide_hits_need_pam,
+                       omit_soft=args.omit_soft, device=locate_device)
+            rows = guide_hits(texts, text_regions, args.files, args.outgroup, args.guide_size, **how)
+            if not args.guide_hit_bulges:
+                write_guide_hits(args.out_guide_hits, rows)
+            else:
+                if args.verbose:
+                    print(f"... and once more with bulges of up to {args.guide_hit_bulges} ... ", file=sys.stderr)
+                bulged = guide_bulge_hits(texts, text_regions, args.files, args.outgroup, args.guide_size,
+                                          bulges=args.guide_hit_bulges, **how)
+                write_guide_bulge_hits(args.out_guide_hits, rows, bulged, list(args.files) + list(args.outgroup))
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
