@@ -734,6 +734,11 @@ int     kr_debug_lazy(kr_ctx*, int64_t* out8);
 /* the intersection's counters: out8[0] items the chunk kernel took, [1] slices redone by chunks, [2] threads and [3] log2 buckets of
  * the latest call's items, [4] 1 where it took the kernels with 32-bit heads, [5] the sort lanes in use, [6] and [7] unused (0) */
 int     kr_debug_isect(kr_ctx*, int64_t* out8);
+/* the latest tile scan's geometry (locate, near-match, product, primer and guide-hit passes): out8[0] tiles, [1] workgroups launched
+ * and [2] the cap in force (KR_SCAN_GRID in the environment when the context is made, 1 .. 65 536: the scans' persistent grids and
+ * their element-stride launches take at most that many workgroups; 0 = none) of the latest scan, [3] the tiles or blocks of the
+ * latest two-pass list (a join's or an extend step's blocks), [4..7] 0 */
+int     kr_debug_scan(kr_ctx*, int64_t* out8);
 /* the latest placement search of the pass-1 output buffers: out8[0] candidates probed, [1] buffers handed to the sort lanes,
  * [2..5] probe milliseconds of the four fastest candidates, [6] the median, [7] the slowest (bench.py prints them: which
  * placement class a line ran in) */

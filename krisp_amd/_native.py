@@ -182,6 +182,7 @@ SYMBOLS = [
     ("kr_text_free", None, [_P]),
     ("kr_debug_isect", _c.c_int, [_P, _P]),
     ("kr_debug_lazy", _c.c_int, [_P, _P]),
+    ("kr_debug_scan", _c.c_int, [_P, _P]),
     ("kr_set_mixed_alphabets", _c.c_int, [_P, _c.c_int]),
     ("kr_build_experiments", _c.c_int, []),
     ("kr_comm_set_timeout", _c.c_int, [_P, _c.c_int]),
@@ -972,6 +973,13 @@ class Engine:
         self.lib.kr_debug_lazy(self.ctx, _ptr(o))
         return dict(skipped=int(o[0]), ordered_later=int(o[1]), touch_collects=int(o[2]), on=int(o[3]),
                     anchor_in_bucket_order=int(o[4]), fuse_anchor=int(o[5]), coarse=int(o[6]), coarse_promoted=int(o[7]))
+
+    def debug_scan(self):
+        """the latest tile scan's geometry (kr_debug_scan): tiles, workgroups launched and the KR_SCAN_GRID cap in force (0:
+        none) of the latest scan, the tiles or blocks of the latest two-pass list"""
+        o = np.zeros(8, dtype=np.int64)
+        self.lib.kr_debug_scan(self.ctx, _ptr(o))
+        return dict(tiles=int(o[0]), grid=int(o[1]), cap=int(o[2]), blocks=int(o[3]))
 
     def copy_gbps(self, nbytes=1 << 30, reps=10):
         v = self.lib.kr_debug_copy_gbps(self.ctx, nbytes, reps)

@@ -154,6 +154,8 @@ struct kr_ctx {
     u32 co_hitcap = 0;          // KR_COARSE_HITCAP env (tests: a hit list that overflows; 0 = sized from the candidate list)
     int co_occ = 0;             // resident k_coarse_probe workgroups per CU (occupancy query, cached)
     u32 co_grid = 0;            // KR_COARSE_GRID env (tests: a few workgroups walk many work units; 0 = co_occ x the CUs)
+    u32 scan_cap = 0;           // KR_SCAN_GRID env (tests: a few workgroups walk many tiles of a scan; 0 = scan_grid()'s occupancy x the CUs)
+    int64_t scan_dbg[3] = {0, 0, 0};      // kr_debug_scan: tiles and grid of the latest scan_grid(), blocks of the latest scan_two_pass
     int slice_route = 1;        // KR_SLICE_ROUTE env (A/B, tests): 0 = every slice counts its keys again before its pass 1 (k_hist8k / k_scatter1kp)
     // wide windows (kr_set_params_wide / kr_wide_run)
     struct Wide {
@@ -585,6 +587,8 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         if (e19) c->co_hitcap = (u32)std::max(1, atoi(e19));
         const char* e20 = getenv("KR_COARSE_GRID");
         if (e20) c->co_grid = (u32)std::max(0, std::min(65536, atoi(e20)));
+        const char* e23 = getenv("KR_SCAN_GRID");
+        if (e23) c->scan_cap = (u32)std::max(0, std::min(65536, atoi(e23)));
         const char* e13 = getenv("KR_SLICE_ROUTE");
         c->slice_route = e13 ? atoi(e13) != 0 : 1;
         const char* e8 = getenv("KR_PLACE_TRIES");

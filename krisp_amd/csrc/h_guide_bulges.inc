@@ -191,7 +191,7 @@ int64_t kr_guide_bulges_windows(kr_ctx* c, uint8_t* rows, size_t cap_bytes) {
     if (bytes > cap_bytes) return fail(c, KR_ERR_CAPACITY, "row buffer too small: %llu > %zu", (unsigned long long)bytes, cap_bytes);
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure(c, gb.rows, bytes))) return rc;
-    const u32 grid = (u32)std::min<u64>((bytes + 255) / 256, (u64)c->ncu * 16);
+    const u32 grid = scan_stride_grid(c, (bytes + 255) / 256);
     hipLaunchKernelGGL(k_gbulge_cut, dim3(grid), dim3(256), 0, c->stream, (const uint8_t*)it->second.bases.p, (u64)it->second.n_bases,
                        (const kr_guide_bulge_hit*)gb.hits.p, (u64)nhits, W, (uint8_t*)gb.rows.p);
     HIPCHK(c, hipMemcpyAsync(rows, gb.rows.p, bytes, hipMemcpyDeviceToHost, c->stream));

@@ -117,7 +117,7 @@ static int ghit_finish_hits(kr_ctx* c, const Genome& G, u64* total) {
     auto& gh = c->ghit;
     const u64 nhits = *total;
     const GhitMotifs gm = {gh.sets5, gh.a, gh.sets3, gh.b};
-    const u32 grid = (u32)std::min<u64>((nhits + 255) / 256, (u64)c->ncu * 16);
+    const u32 grid = scan_stride_grid(c, (nhits + 255) / 256);
     hipLaunchKernelGGL(k_ghit_finish, dim3(grid), dim3(256), 0, c->stream, (const uint8_t*)G.bases.p, (u64)G.n_bases,
                        (const uint8_t*)gh.arena.p, (u32)c->loc.k, (u32)c->loc.omit, gm, (u32)gh.nguides, (const kr_near_hit*)gh.pairs.p,
                        (kr_guide_hit*)gh.hits.p, nhits);

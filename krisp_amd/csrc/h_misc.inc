@@ -301,6 +301,18 @@ int kr_debug_isect(kr_ctx* c, int64_t* o) {
     return KR_OK;
 }
 
+// the latest tile scan's geometry (h_scan.inc): o[0] tiles, [1] workgroups and [2] the KR_SCAN_GRID cap (0: none) of the latest
+// scan_grid(), [3] the tiles or blocks of the latest scan_two_pass, [4..7] 0
+int kr_debug_scan(kr_ctx* c, int64_t* o) {
+    if (!c || !o) return KR_ERR_PARAM;
+    o[0] = c->scan_dbg[0];
+    o[1] = c->scan_dbg[1];
+    o[2] = c->scan_cap;
+    o[3] = c->scan_dbg[2];
+    o[4] = o[5] = o[6] = o[7] = 0;
+    return KR_OK;
+}
+
 // which result-changing experiment switches this library was compiled with (k_keys.inc): 0 for a product build
 int kr_build_experiments(void) {
     int bits = 0;

@@ -190,7 +190,7 @@ int64_t kr_primers_scan(kr_ctx* c, int id) {
     }
     if (rc) return rc;
     if (ns) {
-        const u32 grid = (u32)std::min<u64>((ns + 255) / 256, (u64)c->ncu * 16);
+        const u32 grid = scan_stride_grid(c, (ns + 255) / 256);
         hipLaunchKernelGGL(k_prod_rec, dim3(grid), dim3(256), 0, c->stream, (const kr_product_site*)pm.sites.p, ns,
                            (const u64*)pm.seps.p, nseps, (u32*)pm.rec.p);
         if ((rc = prim_join(c, pg, ns, &np))) return rc;

@@ -114,7 +114,15 @@ static u32 scan_grid(kr_ctx* c, K kernel, size_t lds, u64 ntiles) {
         (void)hipGetLastError();
         per = 1;
     }
-    return (u32)std::min<u64>(ntiles, (u64)c->ncu * per);
+    const u32 grid = (u32)std::min<u64>(ntiles, c->scan_cap ? (u64)c->scan_cap : (u64)c->ncu * per);
+    c->scan_dbg[0] = (int64_t)ntiles;
+    c->scan_dbg[1] = grid;
+    return grid;
+}
+
+// blocks of an element-stride launch over `blocks` blocks' worth of elements: 16 per CU at most (KR_SCAN_GRID: that many)
+static u32 scan_stride_grid(kr_ctx* c, u64 blocks) {
+    return (u32)std::min<u64>(blocks, c->scan_cap ? (u64)c->scan_cap : (u64)c->ncu * 16);
 }
 
 // a list made in two passes over nblocks tiles (or blocks): count(tcount, flag) launches the counting kernel,
@@ -127,6 +135,7 @@ static int scan_two_pass(kr_ctx* c, u64 nblocks, const char* over, C&& count, R&
     int rc;
     if ((rc = ensure(c, l.tcount, (nblocks + 1) * 4)) || (rc = ensure(c, l.toff, (nblocks + 1) * 8)) || (rc = ensure(c, l.flag, 16)))
         return rc;
+    c->scan_dbg[2] = (int64_t)nblocks;
     hipStream_t st = c->stream;
     u32* tc = (u32*)l.tcount.p;
     u64* to = (u64*)l.toff.p;
@@ -186,7 +195,7 @@ static int64_t scan_windows(kr_ctx* c, int64_t nhits, int gid, const char* scan_
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
     if ((rc = ensure(c, dev_rows, bytes))) return rc;
-    const u32 grid = (u32)std::min<u64>((bytes + 255) / 256, (u64)c->ncu * 16);
+    const u32 grid = scan_stride_grid(c, (bytes + 255) / 256);
     hipLaunchKernelGGL(k_loc_cut<H>, dim3(grid), dim3(256), 0, c->stream, (const uint8_t*)it->second.bases.p, (const H*)hits.p,
                        (u64)nhits, (u32)c->loc.k, (uint8_t*)dev_rows.p);
     HIPCHK(c, hipMemcpyAsync(rows, dev_rows.p, bytes, hipMemcpyDeviceToHost, c->stream));
