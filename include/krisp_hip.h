@@ -682,6 +682,9 @@ enum { KR_OPT_SLICE_BASES = 1,       /* -1 automatic; 0..4: sort every genome in
        KR_OPT_COARSE_POOL = 12,      /* 1 (default; KR_COARSE_POOL in the environment): a genome that kr_genome_partition takes again and again
                                         writes its pass 1 into a buffer the placement search chose (a pool of them, made behind the
                                         kr_intersect that sees such a genome for the second time; the gates of KR_OPT_PLACE_TRIES); 0: always into its own key array */
+       KR_OPT_JOIN2 = 13,            /* 1 (default; KR_JOIN2 in the environment): an intersection of two genomes, one of each side, with one
+                                        diagnostic column and the filter on screens its keys in LDS and joins only the live ones
+                                        (k_join2); 0: the n-way kernel as for every other call.  KR_JOIN2_GRID in the environment caps its grid (tests) */
        KR_OPT_WIDE_ORDERED = 6 };    /* wide path: 0 (default) flanks of >= 20 bases are numbered through minimizer buckets (look-ups
                                         of neighbouring windows share memory sectors): the same groups and hits, but `cand` no longer
                                         ascends with (left, right); 1: order-preserving ranks, groups in the reference's order */
@@ -732,7 +735,8 @@ int     kr_build_experiments(void);
  * [6] genomes an intersection took in the coarse state (kr_genome_partition), [7] coarse genomes sorted fine after all */
 int     kr_debug_lazy(kr_ctx*, int64_t* out8);
 /* the intersection's counters: out8[0] items the chunk kernel took, [1] slices redone by chunks, [2] threads and [3] log2 buckets of
- * the latest call's items, [4] 1 where it took the kernels with 32-bit heads, [5] the sort lanes in use, [6] and [7] unused (0) */
+ * the latest call's items, [4] 1 where it took the kernels with 32-bit heads, [5] the sort lanes in use, [6] launches that took
+ * k_join2 (KR_OPT_JOIN2), [7] items it handed to the redo path because their live keys found no room in its table */
 int     kr_debug_isect(kr_ctx*, int64_t* out8);
 /* the latest tile scan's geometry (locate, near-match, product, primer and guide-hit passes): out8[0] tiles, [1] workgroups launched
  * and [2] the cap in force (KR_SCAN_GRID in the environment when the context is made, 1 .. 65 536: the scans' persistent grids and

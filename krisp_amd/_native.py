@@ -49,6 +49,7 @@ OPT_LANES = 9
 OPT_LAZY_ORDER = 10
 OPT_COARSE_REST = 11
 OPT_COARSE_POOL = 12
+OPT_JOIN2 = 13
 ERR_KEY, ERR_HOST = -5, -6
 STRANDS_BOTH, STRANDS_FORWARD, STRANDS_CANONICAL = 0, 1, 2
 STAGES = ["pack", "hist8", "reduce8", "scatter1", "hist2", "scan2", "scatter2", "chunks", "localsort",
@@ -964,7 +965,7 @@ class Engine:
         o = np.zeros(8, dtype=np.int64)
         self.lib.kr_debug_isect(self.ctx, _ptr(o))
         return dict(chunk_kernel_items=int(o[0]), slices_redone=int(o[1]), threads=int(o[2]), buckets_per_item_log2=int(o[3]),
-                    heads32=int(o[4]), sort_lanes=int(o[5]))
+                    heads32=int(o[4]), sort_lanes=int(o[5]), join2_launches=int(o[6]), join2_handed_on=int(o[7]))
 
     def debug_lazy(self):
         """KR_OPT_LAZY_ORDER's counters (kr_debug_lazy): LDS sorts of whole slices the sorts left out, made later, collects

@@ -336,7 +336,7 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
         if ((rc = ensure(c, c->chunkpos, ((size_t)std::max(cmax, nbk) + 2) * 4))) return rc;
         if (!c->isovf.p) {
             if ((rc = ensure(c, c->isovf, ((size_t)I3_OVF_CAP + 4) * 4))) return rc;
-            HIPCHK(c, hipMemsetAsync(c->isovf.p, 0, 16, st));      // (once: k_publish_reset reads the count and clears it)
+            HIPCHK(c, hipMemsetAsync(c->isovf.p, 0, ((size_t)I3_OVF_CAP + 4) * 4, st));      // (once: k_publish_reset reads the count and clears it)
         }
     }
     for (int s = 0; s < c->nslices; s++) {
@@ -390,18 +390,24 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
             c->i3_last_tags = tagk ? 1 : 0;
             // (one diagnostic column, at most 24 genomes: the slot's state is one 32-bit word)
             const bool st32 = tagk && fmt == 0 && g.D == 1 && n <= 24 && c->isect_fmt == 0;
-            const Isect3Kernel kern = isect3_kernel(ua, tagk, st32, fmt);
-            int& occ = c->i3_occ[ua ? 2 : (tagk ? 1 : 0)][st32 ? 3 : fmt][T / 64];
+            // two genomes, one of each side, one diagnostic column, filter on: the screen and the small exact join
+            // (k_join2.inc) -- it never looks at the order inside a bucket, of either genome
+            const bool join2 = c->join2 && n == 2 && (ingroup_bits == 1u || ingroup_bits == 2u) && a.apply_filter == 1 &&
+                               g.D == 1 && tagk && ip.p0 >= 2 && c->isect_fmt == 0 && c->isect_kernel == 0 && c->fuse_anchor != 0;
+            const Isect3Kernel kern = join2 ? k_join2 : isect3_kernel(ua, tagk, st32, fmt);
+            int& occ = join2 ? c->j2_occ[T / 64] : c->i3_occ[ua ? 2 : (tagk ? 1 : 0)][st32 ? 3 : fmt][T / 64];
             if (occ == 0) {
                 int per = 0;
                 const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, (int)T, 0);
                 occ = (e == hipSuccess && per >= 1) ? per : 1;
             }
-            const u32 grid = std::min<u32>(a3.nitems, (u32)(occ * c->ncu));
+            u32 grid = std::min<u32>(a3.nitems, (u32)(occ * c->ncu));
+            if (join2 && c->j2_grid) grid = std::min(grid, c->j2_grid);
             {
                 StageScope sc(c, KR_ST_INTERSECT, st);
                 c->i3_last_ua = ua ? 1 : 0;
                 if (ua) c->isect_ua++;
+                if (join2) c->j2_launches++;
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(T), 0, st, a3, g);
                 a.ovf = (const u32*)c->isovf.p;
                 a.ovf_cap = c->i3_ovf_cap;
@@ -464,6 +470,14 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
             HIPCHK(c, hipGetLastError());
             total = ((volatile u32*)c->mbox)[0];
             novf = by_items ? ((volatile u32*)c->mbox)[1] : 0u;
+            if (by_items && novf > 0 && c->j2_launches) {
+                // (rare) items k_join2 handed on because their live keys found no room in its table: counted once per call
+                u32 nfull = 0;
+                HIPCHK(c, hipMemcpy(&nfull, (const u32*)c->isovf.p + J2_FULL_WORD, 4, hipMemcpyDeviceToHost));
+                if (nfull) HIPCHK(c, hipMemset((u32*)c->isovf.p + J2_FULL_WORD, 0, 4));
+                if (!c->j2_full_counted) c->j2_full += nfull;
+                c->j2_full_counted = !all_ordered && !c->j2_full_counted;
+            }
             if (by_items && novf > 0 && !all_ordered) {
                 // an item whose anchor run exceeds the slot array (skew): its turn is the chunk kernel's -- every genome
                 // in order first, then the whole call once more (rare: satellites, low-complexity runs)

@@ -297,7 +297,8 @@ int kr_debug_isect(kr_ctx* c, int64_t* o) {
     o[3] = c->i3_last_mlog;
     o[4] = c->i3_last_tags;
     o[5] = lanes_used(c);
-    o[6] = o[7] = 0;              // (unused)
+    o[6] = c->j2_launches;
+    o[7] = c->j2_full;
     return KR_OK;
 }
 

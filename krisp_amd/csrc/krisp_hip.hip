@@ -39,6 +39,7 @@
 #include "k_intersect.inc"   // n-way intersection, candidate compaction, collection, list merge
 #include "k_intersect3.inc"  // the same intersection as a persistent, software-pipelined kernel (items of whole buckets)
 #include "k_intersect3t.inc" // ... with 32-bit heads where the geometry allows
+#include "k_join2.inc"       // two genomes, one of each side: a byte screen in LDS, an exact join of the live keys only
 #include "k_text.inc"        // the reference reader on the device: file text -> upload buffer
 #include "k_inflate.inc"     // BGZF members inflated on the device, a lane per member (round 6)
 #include "k_gunzip.inc"      // one plain gzip member inflated on the device: chunks, block starts found by trial, windows
