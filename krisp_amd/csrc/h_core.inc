@@ -228,6 +228,22 @@ struct kr_ctx {
         u64 ngroups = 0;                // (left,right) groups present in all genomes (= nfin unless the list is canonical)
         int64_t nhits = -1;
     } wide;
+    // the one-genome scans (h_scan.inc), all in the locate context.  bufs(): a pass's device buffers, named here alone
+    // (kr_destroy releases them); reset(): what another geometry leaves of a pass (kr_set_params_locate: no table, no result)
+    typedef std::vector<DevBuf*> Bufs;
+    // the seed table of a seed pass on the device (seed_table_build): the entries' text, the slots, the entry list, the
+    // membership bitmap; slots = 0: no table
+    struct SeedTable {
+        DevBuf arena, table, list, bitmap;
+        u64 slots = 0;
+        void bufs(Bufs& v) { v.insert(v.end(), {&arena, &table, &list, &bitmap}); }
+    };
+    // the pair list of a product pass (pair_list_sort, pair_list_upload): (left << 32 | right) ascending, the pairs' rows
+    struct PairList {
+        DevBuf pairkeys, pairidx;
+        u64 npairs = 0;
+        void bufs(Bufs& v) { v.insert(v.end(), {&pairkeys, &pairidx}); }
+    };
     // the locate pass (kr_set_params_locate / kr_locate_*: h_locate.inc)
     struct Loc {
         bool on = false;
@@ -236,51 +252,66 @@ struct kr_ctx {
         int64_t nhits = -1;
         int gid = -1;                   // the genome of the latest kr_locate_scan
         DevBuf arena, table, bitmap, hits, seps, rows;
-        DevBuf tcount, toff, flag;      // the two-pass scratch of all three passes (h_scan.inc: scan_two_pass)
+        DevBuf tcount, toff, flag;      // the two-pass scratch of all six passes (h_scan.inc: scan_two_pass)
+        void bufs(Bufs& v) { v.insert(v.end(), {&arena, &table, &bitmap, &tcount, &toff, &flag, &hits, &seps, &rows}); }
     } loc;
     // the near-match pass (kr_near_*: h_near.inc), in the locate context: it shares loc's geometry and scratch
     struct Near {
         int M = 0;
-        u64 ntargets = 0, slots = 0;
+        u64 ntargets = 0;
         int64_t nhits = -1;
         int gid = -1;                   // the genome of the latest kr_near_scan
-        DevBuf arena, table, list, bitmap, hits, rows;
+        SeedTable seed;
+        DevBuf hits, rows;
+        void bufs(Bufs& v) { seed.bufs(v); v.insert(v.end(), {&hits, &rows}); }
+        void reset() { seed.slots = ntargets = 0; nhits = -1; }
     } near;
     // the guide-hit pass (kr_guide_hits_*: h_guide_hits.inc), in the locate context with loc.k = the protospacer length:
     // a state of its own beside the near pass's, loc's scratch
     struct Ghit {
         int M = 0;
-        u32 sets5 = 0, a = 0, sets3 = 0, b = 0, need = 0;      // the motifs (GhitMotifs), need_pam
-        u64 nguides = 0, slots = 0;
+        GhitMotifs gm = {0, 0, 0, 0};
+        u32 need = 0;                   // need_pam
+        u64 nguides = 0;
         int64_t nhits = -1;
         int gid = -1;                   // the genome of the latest kr_guide_hits_scan
-        DevBuf arena, table, list, bitmap, pairs, hits, kept, rows;    // pairs: the scan's list; kept: what need_pam leaves (it changes places with hits)
+        SeedTable seed;
+        DevBuf pairs, hits, kept, rows; // pairs: the scan's list; kept: what need_pam leaves (it changes places with hits)
+        void bufs(Bufs& v) { seed.bufs(v); v.insert(v.end(), {&pairs, &hits, &kept, &rows}); }
+        void reset() { seed.slots = nguides = 0; nhits = -1; }
     } ghit;
     // the bulged guide-hit pass (kr_guide_bulges_*: h_guide_bulges.inc), in the same context: a state of its own beside ghit.
-    // arena / table / list / bitmap: the seed table of the guides' halves of h letters; texts: the entries' whole text
+    // seed: the table of the guides' halves of h letters; texts: the entries' whole text
     struct Gbulge {
         int M = 0, B = 0;
-        u32 h = 0, sets5 = 0, a = 0, sets3 = 0, b = 0, need = 0;
-        u64 nguides = 0, slots = 0;
+        u32 h = 0, need = 0;
+        GhitMotifs gm = {0, 0, 0, 0};
+        u64 nguides = 0;
         int64_t nhits = -1;
         int gid = -1;                   // the genome of the latest kr_guide_bulges_scan
-        DevBuf arena, table, list, bitmap, texts, pairs, hits, rows;
+        SeedTable seed;
+        DevBuf texts, pairs, hits, rows;
+        void bufs(Bufs& v) { seed.bufs(v); v.insert(v.end(), {&texts, &pairs, &hits, &rows}); }
+        void reset() { seed.slots = nguides = 0; nhits = -1; }
     } gbulge;
     // the product pass (kr_products_*: h_products.inc), in the locate context: loc.L / loc.R are the texts' lengths
     struct Prod {
         int M = 0;
         u32 max_product = 0;
-        u64 nleft = 0, nright = 0, npairs = 0, slots = 0;
+        u64 nleft = 0, nright = 0;
         int64_t nsites = -1, nhits = -1;
-        DevBuf arena, table, list, bitmap, pairkeys, pairidx, seps, sites, rec, hits;
+        SeedTable seed;
+        PairList plist;
+        DevBuf seps, sites, rec, hits;
+        void bufs(Bufs& v) { seed.bufs(v); plist.bufs(v); v.insert(v.end(), {&seps, &sites, &rec, &hits}); }
+        void reset() { seed.slots = 0; nsites = nhits = -1; }
     } prod;
-    // the primer-product pass (kr_primers_*: h_primers.inc), in the locate context: texts of mixed lengths, smin .. maxlen
-    struct Prim {
-        int M = 0;
-        u32 max_product = 0, smin = 0, maxlen = 0;
-        u64 nleft = 0, nright = 0, npairs = 0, slots = 0;
-        int64_t nsites = -1, nhits = -1;
-        DevBuf arena, eoff, table, list, bitmap, pairkeys, pairidx, seps, sites, rec, hits;
+    // the primer-product pass (kr_primers_*: h_primers.inc), in the locate context: the product pass's state for texts of
+    // mixed lengths, smin .. maxlen, entry e's text at eoff[e]
+    struct Prim : Prod {
+        u32 smin = 0, maxlen = 0;
+        DevBuf eoff;
+        void bufs(Bufs& v) { Prod::bufs(v); v.push_back(&eoff); }
     } prim;
     // the primer design pass (kr_design_*: h_design.inc): no genome, no geometry of another pass
     struct Design {
@@ -676,24 +707,9 @@ void kr_destroy(kr_ctx* c) {
             }
     }
     {
-        auto& l = c->loc;
-        DevBuf* lb[] = {&l.arena, &l.table, &l.bitmap, &l.tcount, &l.toff, &l.flag, &l.hits, &l.seps, &l.rows};
-        for (DevBuf* b : lb) release(c, *b);
-        auto& nr = c->near;
-        DevBuf* nb[] = {&nr.arena, &nr.table, &nr.list, &nr.bitmap, &nr.hits, &nr.rows};
-        for (DevBuf* b : nb) release(c, *b);
-        auto& gh = c->ghit;
-        DevBuf* hb[] = {&gh.arena, &gh.table, &gh.list, &gh.bitmap, &gh.pairs, &gh.hits, &gh.kept, &gh.rows};
-        for (DevBuf* b : hb) release(c, *b);
-        auto& gbu = c->gbulge;
-        DevBuf* bb[] = {&gbu.arena, &gbu.table, &gbu.list, &gbu.bitmap, &gbu.texts, &gbu.pairs, &gbu.hits, &gbu.rows};
-        for (DevBuf* b : bb) release(c, *b);
-        auto& pr = c->prod;
-        DevBuf* pb[] = {&pr.arena, &pr.table, &pr.list, &pr.bitmap, &pr.pairkeys, &pr.pairidx, &pr.seps, &pr.sites, &pr.rec, &pr.hits};
-        for (DevBuf* b : pb) release(c, *b);
-        auto& pm = c->prim;
-        DevBuf* mb[] = {&pm.arena, &pm.eoff, &pm.table, &pm.list, &pm.bitmap, &pm.pairkeys, &pm.pairidx, &pm.seps, &pm.sites, &pm.rec, &pm.hits};
-        for (DevBuf* b : mb) release(c, *b);
+        kr_ctx::Bufs sb;                // the one-genome scans': every pass hands over its own
+        c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb);
+        for (DevBuf* b : sb) release(c, *b);
         auto& ds = c->design;
         DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec, &ds.hprec};
         for (DevBuf* b : db) release(c, *b);

@@ -28,6 +28,23 @@ static int ghit_motif_sets(kr_ctx* c, const char* name, const char* motif, u32* 
     return KR_OK;
 }
 
+// what kr_guide_hits_table and kr_guide_bulges_table (`who`) check alike, in the order both had it: the motifs -> *gm, fewer
+// than `limit` guides, texts of k letters in A, C, G, T.  (A motif's refusal names kr_guide_hits_table for either: legacy)
+static int guide_table_prologue(kr_ctx* c, const char* who, const uint8_t* texts, u64 nguides, int k, u64 limit, const char* pam5,
+                                const char* pam3, GhitMotifs* gm) {
+    int rc;
+    if ((rc = ghit_motif_sets(c, "pam5", pam5, &gm->sets5, &gm->a)) || (rc = ghit_motif_sets(c, "pam3", pam3, &gm->sets3, &gm->b))) return rc;
+    if (nguides >= limit)
+        return fail(c, KR_ERR_CAPACITY, "%s: %llu guides (the limit is %u)", who, (unsigned long long)nguides, (u32)limit - 1);
+    for (u64 i = 0; i < nguides * (u64)k; i++) {
+        const uint8_t ch = texts[i];
+        if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T')
+            return fail(c, KR_ERR_PARAM, "%s: guide %llu holds a byte that is none of A, C, G, T (0x%02x)", who,
+                        (unsigned long long)(i / (u64)k), ch);
+    }
+    return KR_OK;
+}
+
 int64_t kr_guide_hits_table(kr_ctx* c, const uint8_t* texts, uint64_t nguides, int mismatches, const char* pam5, const char* pam3,
                             int need_pam) {
     int rc;
@@ -40,86 +57,42 @@ int64_t kr_guide_hits_table(kr_ctx* c, const uint8_t* texts, uint64_t nguides, i
                     GHIT_MAX_SIZE, k);
     if (M < 0 || M >= NEAR_MAXP) return fail(c, KR_ERR_PARAM, "kr_guide_hits_table: 0 <= mismatches <= %d (got %d)", NEAR_MAXP - 1, M);
     if (!texts && nguides) return fail(c, KR_ERR_PARAM, "kr_guide_hits_table: null texts");
-    u32 sets5, a, sets3, b;
-    if ((rc = ghit_motif_sets(c, "pam5", pam5, &sets5, &a)) || (rc = ghit_motif_sets(c, "pam3", pam3, &sets3, &b))) return rc;
-    if (nguides >= (1ull << 24))
-        return fail(c, KR_ERR_CAPACITY, "kr_guide_hits_table: %llu guides (the limit is %u)", (unsigned long long)nguides, (1u << 24) - 1);
-    for (u64 i = 0; i < nguides * (u64)k; i++) {
-        const uint8_t ch = texts[i];
-        if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T')
-            return fail(c, KR_ERR_PARAM, "kr_guide_hits_table: guide %llu holds a byte that is none of A, C, G, T (0x%02x)",
-                        (unsigned long long)(i / (u64)k), ch);
-    }
+    GhitMotifs gm;
+    if ((rc = guide_table_prologue(c, "kr_guide_hits_table", texts, nguides, k, 1ull << 24, pam5, pam3, &gm))) return rc;
     const u32 NP = (u32)M + 1;
     u32 off[NEAR_MAXP + 1] = {0, 0, 0, 0, 0};
-    for (u32 j = 0; j <= NP; j++) off[j] = (u32)((u64)j * k / NP);
-    const u64 ne = 2 * nguides, nk = ne * NP;
+    seed_pieces((u32)k, NP, off, nullptr);
+    const u64 ne = 2 * nguides;
     std::vector<uint8_t> text;
-    std::vector<std::pair<u64, u32>> keyed;
+    SeedKeys keyed;
     try {
-        // entry 2 i = text i, entry 2 i + 1 = its reverse complement
-        text.resize(ne * k + 16);
-        for (u64 t = 0; t < nguides; t++) {
-            const uint8_t* s = texts + t * k;
-            uint8_t* f = text.data() + 2 * t * k;
-            for (int i = 0; i < k; i++) {
-                f[i] = s[i];
-                f[k + i] = loc_comp(s[k - 1 - i]);
-            }
-        }
-        keyed.reserve(nk);
-        for (u64 e = 0; e < ne; e++)
-            for (u32 j = 0; j < NP; j++)
-                keyed.emplace_back(near_key(j, loc_hash(text.data() + e * k + off[j], (int)(off[j + 1] - off[j]))), (u32)e);
+        text.resize(ne * k + 16);                   // entry 2 i = text i, entry 2 i + 1 = its reverse complement
+        for (u64 t = 0; t < nguides; t++) seed_both_strands(text.data() + 2 * t * k, texts + t * k, (size_t)k);
+        keyed.reserve(ne * NP);
+        for (u64 e = 0; e < ne; e++) seed_keys(keyed, text.data() + e * k, off, NP, 0, (u32)e);
     } catch (const std::bad_alloc&) {
         return fail(c, KR_ERR_CAPACITY, "kr_guide_hits_table: no host memory for the table of %llu guides", (unsigned long long)nguides);
     }
-    gh.slots = 0;                                   // (from here on the device's copy of an earlier table is written over)
+    gh.seed.slots = 0;                              // (from here on the device's copy of an earlier table is written over)
     gh.nhits = -1;
-    const int64_t slots = seed_table_build(c, keyed, text, gh.table, gh.arena, gh.list, gh.bitmap, "kr_guide_hits_table", nguides, "guides");
+    const int64_t slots = seed_table_build(c, keyed, text, gh.seed, "kr_guide_hits_table", nguides, "guides");
     if (slots < 0) return slots;
     gh.M = M;
-    gh.sets5 = sets5; gh.a = a; gh.sets3 = sets3; gh.b = b;
+    gh.gm = gm;
     gh.need = need_pam ? 1u : 0u;
     gh.nguides = nguides;
-    gh.slots = (u64)slots;
+    gh.seed.slots = (u64)slots;
     return slots;
 }
-
-extern "C++" {    // (a template inside the translation unit's extern "C" block)
-// the near pass's scan kernels over the guides' table: the pairs (guide, strand, distance, position) into gh.pairs
-template <u32 NP>
-static int ghit_launch(kr_ctx* c, const Genome& G, const NearGeom& ng, u64 ntiles, u64* total_out) {
-    auto& gh = c->ghit;
-    const size_t lds = scan_lds_bytes(ng.k, LOC_T * 8);           // (a 64-bit scan array: the near pass's expression)
-    const u32 grid = scan_grid(c, k_near_scan<NP, false>, lds, ntiles);
-    auto launch = [&](auto kernel, u32* tc, const u64* to, kr_near_hit* out, u32* fl) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(LOC_T), lds, c->stream, (const uint8_t*)G.bases.p, (u64)G.n_bases, ng,
-                           (const u32*)gh.bitmap.p, (const NearSlot*)gh.table.p, (u64)(gh.slots - 1), (const u32*)gh.list.p,
-                           (const uint8_t*)gh.arena.p, ntiles, tc, to, out, fl);
-    };
-    return scan_two_pass(
-        c, ntiles, "kr_guide_hits_scan: 2^32 or more hits in one genome (fewer mismatches or guides)",
-        [&](u32* tc, u32* fl) { launch(k_near_scan<NP, false>, tc, nullptr, nullptr, fl); },
-        [&](u64 total) {
-            int rc = ensure(c, gh.pairs, total * sizeof(kr_near_hit));
-            if (!rc) rc = ensure(c, gh.hits, total * sizeof(kr_guide_hit));
-            return rc ? fail(c, rc, "kr_guide_hits_scan: %llu hits do not fit the device (%s)", (unsigned long long)total, c->err.c_str())
-                      : KR_OK;
-        },
-        [&](u32* tc, const u64* to, u32* fl) { launch(k_near_scan<NP, true>, tc, to, (kr_near_hit*)gh.pairs.p, fl); }, total_out);
-}
-}  // extern "C++"
 
 // the per-hit step over the *total pairs of the scan (k_ghit_finish: gh.pairs -> gh.hits), then -- with need_pam -- the hits with both motifs beside
 // them, in their order (k_ghit_keep, into gh.kept; the two lists change places): *total = what is left
 static int ghit_finish_hits(kr_ctx* c, const Genome& G, u64* total) {
     auto& gh = c->ghit;
     const u64 nhits = *total;
-    const GhitMotifs gm = {gh.sets5, gh.a, gh.sets3, gh.b};
     const u32 grid = scan_stride_grid(c, (nhits + 255) / 256);
     hipLaunchKernelGGL(k_ghit_finish, dim3(grid), dim3(256), 0, c->stream, (const uint8_t*)G.bases.p, (u64)G.n_bases,
-                       (const uint8_t*)gh.arena.p, (u32)c->loc.k, (u32)c->loc.omit, gm, (u32)gh.nguides, (const kr_near_hit*)gh.pairs.p,
+                       (const uint8_t*)gh.seed.arena.p, (u32)c->loc.k, (u32)c->loc.omit, gh.gm, (u32)gh.nguides, (const kr_near_hit*)gh.pairs.p,
                        (kr_guide_hit*)gh.hits.p, nhits);
     if (!gh.need) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -153,7 +126,8 @@ int64_t kr_guide_hits_scan(kr_ctx* c, int id) {
     const Genome* Gp;
     int rc;
     if ((rc = scan_ctx(c))) return rc;
-    if (!c->ghit.slots) return fail(c, KR_ERR_PARAM, "kr_guide_hits_scan: kr_guide_hits_table first");
+    // (KR_ERR_PARAM where the other passes answer KR_ERR_STATE: deliberate, callers hold the code)
+    if (!c->ghit.seed.slots) return fail(c, KR_ERR_PARAM, "kr_guide_hits_scan: kr_guide_hits_table first");
     if ((rc = scan_genome(c, id, true, "kr_guide_hits_table first", &Gp))) return rc;
     const Genome& G = *Gp;
     auto& l = c->loc;
@@ -163,19 +137,13 @@ int64_t kr_guide_hits_scan(kr_ctx* c, int id) {
     u64 nw;
     const u64 ntiles = scan_tiles(G.n_bases, (u64)l.k, &nw);
     if (!ntiles || !gh.nguides) return 0;
-    NearGeom ng;
-    memset(&ng, 0, sizeof ng);
-    ng.k = (u32)l.k; ng.omit = (u32)l.omit; ng.M = (u32)gh.M; ng.np = (u32)gh.M + 1;
-    ng.lo[0] = ng.lo[1] = 0; ng.hi[0] = ng.hi[1] = (u32)l.k;     // no flank: every column lies inside
-    for (u32 j = 0; j <= ng.np; j++) ng.off[j] = (u32)((u64)j * l.k / ng.np);
-    for (u32 j = 0; j < ng.np; j++) ng.pw[j] = loc_pow((int)(ng.off[j + 1] - ng.off[j]) - 1);
+    NearGeom ng = near_geom((u32)l.k, (u32)l.omit, (u32)gh.M);
+    ng.hi[0] = ng.hi[1] = (u32)l.k;                               // no flank: every column lies inside [0, k)
     u64 total = 0;
-    switch (ng.np) {
-    case 1: rc = ghit_launch<1>(c, G, ng, ntiles, &total); break;
-    case 2: rc = ghit_launch<2>(c, G, ng, ntiles, &total); break;
-    case 3: rc = ghit_launch<3>(c, G, ng, ntiles, &total); break;
-    default: rc = ghit_launch<4>(c, G, ng, ntiles, &total); break;
-    }
+    // the near pass's scan kernels over the guides' table: the pairs (guide, strand, distance, position) into gh.pairs
+    rc = near_scan_pairs(c, G, gh.seed, ng, ntiles, gh.pairs, [&](u64 n) { return ensure(c, gh.hits, n * sizeof(kr_guide_hit)); },
+                         "kr_guide_hits_scan: 2^32 or more hits in one genome (fewer mismatches or guides)",
+                         "kr_guide_hits_scan: %llu hits do not fit the device (%s)", &total);
     if (!rc && total) rc = ghit_finish_hits(c, G, &total);
     if (rc) {
         gh.nhits = -1;
@@ -195,5 +163,5 @@ int64_t kr_guide_hits_windows(kr_ctx* c, uint8_t* rows, size_t cap_bytes) {
     int rc;
     if ((rc = scan_ctx(c))) return rc;
     auto& gh = c->ghit;
-    return scan_windows<kr_guide_hit>(c, gh.nhits, gh.gid, "kr_guide_hits_scan first", gh.hits, gh.rows, rows, cap_bytes);
+    return scan_windows(c, gh.nhits, gh.gid, "kr_guide_hits_scan first", (u32)c->loc.k, gh.rows, rows, cap_bytes, scan_cut_k<kr_guide_hit>(c, gh));
 }

@@ -1,6 +1,6 @@
 // h_locate.inc -- part of krisp_hip.hip (one translation unit): host side of the locate pass (k_locate.inc): a context that
 // only uploads genomes, the flank table of the surviving groups, the scan of one genome, its record separators.  What it
-// shares with the near-match and product passes is h_scan.inc.
+// shares with the five seed passes is h_scan.inc.
 // One genome is resident at a time (the caller uploads the next under the same id); beside it live the table (16 bytes a
 // slot, >= 2 slots a group), the flank text, the bitmap, the per-tile counts and the hits.
 
@@ -21,16 +21,8 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     l.omit = softmask_mode == KR_SOFT_OMIT;
     l.ngroups = l.slots = 0;
     l.nhits = -1;
-    c->near.slots = c->near.ntargets = 0;       // (a table of another geometry: kr_near_table again)
-    c->near.nhits = -1;
-    c->ghit.slots = c->ghit.nguides = 0;        // (likewise: kr_guide_hits_table again)
-    c->ghit.nhits = -1;
-    c->gbulge.slots = c->gbulge.nguides = 0;    // (likewise: kr_guide_bulges_table again -- its texts are rows of G letters)
-    c->gbulge.nhits = -1;
-    c->prod.slots = 0;                         // (likewise: kr_products_table again)
-    c->prod.nsites = c->prod.nhits = -1;
-    c->prim.slots = 0;                          // (another soft-mask mode: kr_primers_table again)
-    c->prim.nsites = c->prim.nhits = -1;
+    // a table of another geometry (the primer pass: of another soft-mask mode) is no table: kr_*_table again
+    c->near.reset(); c->ghit.reset(); c->gbulge.reset(); c->prod.reset(); c->prim.reset();
     c->wide.on = false;
     c->max_bases = max_bases;
     c->have_params = true;
@@ -131,7 +123,7 @@ int64_t kr_locate_windows(kr_ctx* c, uint8_t* rows, size_t cap_bytes) {
     int rc;
     if ((rc = scan_ctx(c))) return rc;
     auto& l = c->loc;
-    return scan_windows<kr_loc_hit>(c, l.nhits, l.gid, "kr_locate_scan first", l.hits, l.rows, rows, cap_bytes);
+    return scan_windows(c, l.nhits, l.gid, "kr_locate_scan first", (u32)l.k, l.rows, rows, cap_bytes, scan_cut_k<kr_loc_hit>(c, l));
 }
 
 int64_t kr_locate_seps(kr_ctx* c, int id, uint64_t* out, size_t cap) {

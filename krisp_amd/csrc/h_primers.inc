@@ -4,7 +4,8 @@
 // the texts bring their own lengths): one genome resident at a time.  Beside the genome live the entries' text (2 bytes a
 // letter of a text) and their offsets (8 bytes a text), the table (16 bytes a slot, >= 2 slots a distinct piece), the entry
 // list (8 (M + 1) bytes a text), the bitmap, the pair list (12 bytes a pair), the separators (8 bytes each), the sites
-// (16 + 4 bytes each) and the products (24 bytes each).
+// (16 + 4 bytes each) and the products (24 bytes each).  The scan behind the prologue, the join, the fetch and the sites are
+// h_products.inc's (prod_scan, prod_fetch, prod_sites), with this pass's kernels and the entries' offsets.
 #define PRIM_MIN_LEN 10             // the lengths kr_design_table takes for a primer
 #define PRIM_MAX_LEN 60
 
@@ -13,9 +14,7 @@ static void prim_geom(const kr_ctx* c, PrimGeom* pg) {
     memset(pg, 0, sizeof *pg);
     pg->smin = pm.smin; pg->maxlen = pm.maxlen;
     pg->omit = (u32)c->loc.omit; pg->M = (u32)pm.M; pg->nleft2 = (u32)(2 * pm.nleft);
-    const u32 NP = (u32)pm.M + 1;
-    for (u32 j = 0; j <= NP; j++) pg->off[j] = (u32)((u64)j * pg->smin / NP);
-    for (u32 j = 0; j < NP; j++) pg->pw[j] = loc_pow((int)(pg->off[j + 1] - pg->off[j]) - 1);
+    seed_pieces(pg->smin, (u32)pm.M + 1, pg->off, pg->pw);
 }
 
 int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets, uint64_t nleft, uint64_t nright,
@@ -25,7 +24,7 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
     auto& pm = c->prim;
     const int M = mismatches;
     const u64 nt = nleft + nright;
-    pm.slots = 0;
+    pm.seed.slots = 0;
     pm.nsites = pm.nhits = -1;
     if (M < 0 || M >= NEAR_MAXP)
         return fail(c, KR_ERR_PARAM, "kr_primers_table: 0 <= mismatches <= %d (got %d)", NEAR_MAXP - 1, M);
@@ -43,7 +42,7 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
         smin = std::min(smin, (u32)n);
         maxlen = std::max(maxlen, (u32)n);
     }
-    pm.M = M; pm.max_product = max_product; pm.nleft = nleft; pm.nright = nright; pm.npairs = npairs;
+    pm.M = M; pm.max_product = max_product; pm.nleft = nleft; pm.nright = nright; pm.plist.npairs = npairs;
     pm.smin = smin; pm.maxlen = maxlen;
     PrimGeom pg;
     prim_geom(c, &pg);
@@ -51,7 +50,7 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
     const u64 ne = 2 * nt;
     std::vector<uint8_t> arena;
     std::vector<u32> eoff, pidx;
-    std::vector<std::pair<u64, u32>> keyed, pk;
+    SeedKeys keyed;
     std::vector<u64> pkeys;
     try {
         eoff.resize(ne + 1);
@@ -64,156 +63,60 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
         }
         eoff[ne] = (u32)at;
         arena.resize(at + 16);
-        for (u64 t = 0; t < nt; t++) {
-            const u32 n = offsets[t + 1] - offsets[t];
-            const uint8_t* s = text + (offsets[t] - offsets[0]);
-            uint8_t* f = arena.data() + eoff[2 * t];
-            for (u32 i = 0; i < n; i++) {
-                f[i] = s[i];
-                f[n + i] = loc_comp(s[n - 1 - i]);
-            }
-        }
+        for (u64 t = 0; t < nt; t++)
+            seed_both_strands(arena.data() + eoff[2 * t], text + (offsets[t] - offsets[0]), offsets[t + 1] - offsets[t]);
         // every entry under the NP pieces of the first smin columns of its text as it reads on the forward strand
         keyed.reserve(ne * NP);
-        for (u64 e = 0; e < ne; e++)
-            for (u32 j = 0; j < NP; j++)
-                keyed.emplace_back(near_key(j, loc_hash(arena.data() + eoff[e] + pg.off[j], (int)(pg.off[j + 1] - pg.off[j]))), (u32)e);
-        pk.reserve(npairs);
-        for (u64 p = 0; p < npairs; p++) {
-            const u32 li = pairs[2 * p], rj = pairs[2 * p + 1];
-            if (li >= nleft || rj >= nright)
-                return fail(c, KR_ERR_PARAM, "kr_primers_table: pair %llu names text (%u, %u) of (%llu, %llu)", (unsigned long long)p, li,
-                            rj, (unsigned long long)nleft, (unsigned long long)nright);
+        for (u64 e = 0; e < ne; e++) seed_keys(keyed, arena.data() + eoff[e], pg.off, NP, 0, (u32)e);
+        rc = pair_list_sort(c, "kr_primers_table", pairs, npairs, nleft, nright, pkeys, pidx, [&](u64 p, u32 li, u32 rj) {
             const u32 n1 = offsets[li + 1] - offsets[li], n2 = offsets[nleft + rj + 1] - offsets[nleft + rj];
             if ((u64)max_product < (u64)n1 + n2)
                 return fail(c, KR_ERR_PARAM, "kr_primers_table: max_product %u is shorter than the two texts of pair %llu (%u + %u)",
                             max_product, (unsigned long long)p, n1, n2);
-            pk.emplace_back(((u64)li << 32) | rj, (u32)p);
-        }
-        std::sort(pk.begin(), pk.end());
-        for (u64 p = 1; p < npairs; p++)
-            if (pk[p].first == pk[p - 1].first)
-                return fail(c, KR_ERR_PARAM, "kr_primers_table: pair %u repeats the texts of pair %u", pk[p].second, pk[p - 1].second);
-        pidx.resize(npairs + 1);
-        pkeys.resize(npairs + 1);
+            return (int)KR_OK;
+        });
+        if (rc) return rc;
     } catch (const std::bad_alloc&) {
         return fail(c, KR_ERR_CAPACITY, "kr_primers_table: no host memory for the table of %llu texts", (unsigned long long)nt);
     }
-    for (u64 p = 0; p < npairs; p++) {
-        pkeys[p] = pk[p].first;
-        pidx[p] = pk[p].second;
-    }
-    const int64_t slots = seed_table_build(c, keyed, arena, pm.table, pm.arena, pm.list, pm.bitmap, "kr_primers_table", nt, "texts");
+    const int64_t slots = seed_table_build(c, keyed, arena, pm.seed, "kr_primers_table", nt, "texts");
     if (slots < 0) return slots;
-    if ((rc = ensure(c, pm.eoff, eoff.size() * 4)) || (rc = ensure(c, pm.pairkeys, pkeys.size() * 8)) ||
-        (rc = ensure(c, pm.pairidx, pidx.size() * 4)))
+    if ((rc = ensure(c, pm.eoff, eoff.size() * 4)))
         return fail(c, rc, "kr_primers_table: the table of %llu texts does not fit the device (%s)", (unsigned long long)nt, c->err.c_str());
+    if ((rc = pair_list_upload(c, pm.plist, pkeys, pidx, "kr_primers_table", nt))) return rc;
     HIPCHK(c, hipMemcpy(pm.eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(pm.pairkeys.p, pkeys.data(), pkeys.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(pm.pairidx.p, pidx.data(), pidx.size() * 4, hipMemcpyHostToDevice));
-    pm.slots = (u64)slots;
+    pm.seed.slots = (u64)slots;
     return slots;
 }
 
 extern "C++" {    // (a template inside the translation unit's extern "C" block)
 template <u32 NP>
-static int prim_sites_launch(kr_ctx* c, const Genome& G, const PrimGeom& pg, u64 nw, u64 ntiles, u64* total_out) {
-    auto& pm = c->prim;
-    const size_t lds = scan_lds_bytes(pg.maxlen, LOC_T * 8);      // (a 64-bit scan array)
-    const u32 grid = scan_grid(c, k_prim_scan<NP, false>, lds, ntiles);
-    auto launch = [&](auto kernel, u32* tc, const u64* to, kr_product_site* out, u32* fl) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(LOC_T), lds, c->stream, (const uint8_t*)G.bases.p, (u64)G.n_bases, pg,
-                           (const u32*)pm.bitmap.p, (const NearSlot*)pm.table.p, (u64)(pm.slots - 1), (const u32*)pm.list.p,
-                           (const uint8_t*)pm.arena.p, (const u32*)pm.eoff.p, nw, ntiles, tc, to, out, fl);
-    };
-    return scan_two_pass(
-        c, ntiles, "kr_primers_scan: 2^32 or more primer sites in one genome (fewer mismatches or pairs)",
-        [&](u32* tc, u32* fl) { launch(k_prim_scan<NP, false>, tc, nullptr, nullptr, fl); },
-        [&](u64 total) -> int {
-            int rc;
-            if ((rc = ensure(c, pm.sites, total * sizeof(kr_product_site))) || (rc = ensure(c, pm.rec, total * 4)))
-                return fail(c, rc, "kr_primers_scan: %llu primer sites do not fit the device (%s)", (unsigned long long)total,
-                            c->err.c_str());
-            return KR_OK;
-        },
-        [&](u32* tc, const u64* to, u32* fl) { launch(k_prim_scan<NP, true>, tc, to, (kr_product_site*)pm.sites.p, fl); },
-        total_out);
+static int prim_sites_np(kr_ctx* c, const Genome& G, const PrimGeom& pg, u64 nw, u64 ntiles, u64* ns) {
+    return prod_sites_launch(c, G, c->prim, pg, nw, ntiles, "kr_primers_scan",
+                             "kr_primers_scan: 2^32 or more primer sites in one genome (fewer mismatches or pairs)",
+                             k_prim_scan<NP, false>, k_prim_scan<NP, true>, ns, (const u32*)c->prim.eoff.p);
 }
 }  // extern "C++"
-
-// the join of the sites on the device: -> the number of products
-static int prim_join(kr_ctx* c, const PrimGeom& pg, u64 ns, u64* total_out) {
-    auto& pm = c->prim;
-    *total_out = 0;
-    if (!ns || !pm.npairs) return KR_OK;
-    const u64 nblocks = (ns + LOC_T - 1) / LOC_T;                 // (ns < 2^32: < 2^24 blocks)
-    auto launch = [&](auto kernel, u32* bc, const u64* bo, kr_product_hit* out, u32* fl) {
-        hipLaunchKernelGGL(kernel, dim3((u32)nblocks), dim3(LOC_T), 0, c->stream, (const kr_product_site*)pm.sites.p, ns,
-                           (const u32*)pm.rec.p, pg, (const u32*)pm.eoff.p, (const u64*)pm.pairkeys.p, (const u32*)pm.pairidx.p,
-                           (u32)pm.npairs, pm.max_product, bc, bo, out, fl);
-    };
-    return scan_two_pass(
-        c, nblocks, "kr_primers_scan: 2^32 or more products in one genome (a smaller max_product or fewer mismatches)",
-        [&](u32* bc, u32* fl) { launch(k_prim_join<false>, bc, nullptr, nullptr, fl); },
-        [&](u64 total) {
-            const int rc = ensure(c, pm.hits, total * sizeof(kr_product_hit));
-            return rc ? fail(c, rc, "kr_primers_scan: %llu products do not fit the device (%s)", (unsigned long long)total, c->err.c_str())
-                      : KR_OK;
-        },
-        [&](u32* bc, const u64* bo, u32* fl) { launch(k_prim_join<true>, bc, bo, (kr_product_hit*)pm.hits.p, fl); }, total_out);
-}
 
 int64_t kr_primers_scan(kr_ctx* c, int id) {
     const Genome* Gp;
     int rc;
-    if ((rc = scan_genome(c, id, c && c->prim.slots, "kr_primers_table first", &Gp))) return rc;
+    if ((rc = scan_genome(c, id, c && c->prim.seed.slots, "kr_primers_table first", &Gp))) return rc;
     const Genome& G = *Gp;
-    auto& pm = c->prim;
-    pm.nsites = pm.nhits = -1;
     PrimGeom pg;
     prim_geom(c, &pg);
-    u64 nw;                                                       // window starts of the shortest text
-    const u64 ntiles = scan_tiles(G.n_bases, pg.smin, &nw);
-    if (!ntiles || !(pm.nleft + pm.nright)) {
-        pm.nsites = pm.nhits = 0;
-        return 0;
-    }
-    u64 nseps = 0, ns = 0, np = 0;
-    // (the pass's own list: k_prod_rec reads it, and a kr_locate_seps of the caller writes loc.seps)
-    if ((rc = scan_seps(c, G, "kr_primers_scan", pm.seps, [&](u64 total) { return ensure(c, pm.seps, total * 8); }, &nseps))) return rc;
-    if (nseps >= (1ull << 32)) return fail(c, KR_ERR_CAPACITY, "kr_primers_scan: 2^32 or more records in one genome");
-    switch (pg.M + 1) {
-    case 1: rc = prim_sites_launch<1>(c, G, pg, nw, ntiles, &ns); break;
-    case 2: rc = prim_sites_launch<2>(c, G, pg, nw, ntiles, &ns); break;
-    case 3: rc = prim_sites_launch<3>(c, G, pg, nw, ntiles, &ns); break;
-    default: rc = prim_sites_launch<4>(c, G, pg, nw, ntiles, &ns); break;
-    }
-    if (rc) return rc;
-    if (ns) {
-        const u32 grid = scan_stride_grid(c, (ns + 255) / 256);
-        hipLaunchKernelGGL(k_prod_rec, dim3(grid), dim3(256), 0, c->stream, (const kr_product_site*)pm.sites.p, ns,
-                           (const u64*)pm.seps.p, nseps, (u32*)pm.rec.p);
-        if ((rc = prim_join(c, pg, ns, &np))) return rc;
-    }
-    pm.nsites = (int64_t)ns;
-    pm.nhits = (int64_t)np;
-    return (int64_t)np;
+    auto sites = [&](u64 nw, u64 ntiles, u64* ns) {
+        switch (pg.M + 1) {
+        case 1: return prim_sites_np<1>(c, G, pg, nw, ntiles, ns);
+        case 2: return prim_sites_np<2>(c, G, pg, nw, ntiles, ns);
+        case 3: return prim_sites_np<3>(c, G, pg, nw, ntiles, ns);
+        default: return prim_sites_np<4>(c, G, pg, nw, ntiles, ns);
+        }
+    };
+    // (window starts of the shortest text)
+    return prod_scan(c, G, c->prim, pg, pg.smin, "kr_primers_scan", sites, k_prim_join<false>, k_prim_join<true>, (const u32*)c->prim.eoff.p);
 }
 
-int64_t kr_primers_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) {
-    int rc;
-    if ((rc = scan_ctx(c))) return rc;
-    const int64_t n = scan_fetch(c, c->prim.nhits, "kr_primers_scan first", "product", c->prim.hits, out, cap, sizeof(kr_product_hit));
-    // the device lists them by opening site (position, then the sites' order there): positions ascend already, the
-    // products of one position are put in (length, strand, pair) order here
-    prod_sort_positions(out, n);
-    return n;
-}
+int64_t kr_primers_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) { return prod_fetch(c, true, "kr_primers_scan first", out, cap); }
 
-int64_t kr_primers_sites(kr_ctx* c, kr_product_site* out, size_t cap) {
-    int rc;
-    if ((rc = scan_ctx(c))) return rc;
-    const int64_t n = c->prim.nsites;
-    if (n >= 0 && !out) return n;                   // (the count alone)
-    return scan_fetch(c, n, "kr_primers_scan first", "site", c->prim.sites, out, cap, sizeof(kr_product_site));
-}
+int64_t kr_primers_sites(kr_ctx* c, kr_product_site* out, size_t cap) { return prod_sites(c, true, "kr_primers_scan first", out, cap); }

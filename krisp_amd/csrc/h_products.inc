@@ -5,6 +5,9 @@
 // the bitmap, the pair list (12 bytes a pair), the separators (8 bytes each), the sites (16 + 4 bytes each) and the
 // products (24 bytes each).
 
+// The primer-product pass (h_primers.inc) differs in its geometry, its kernels and one kernel argument more (eoff): the
+// scan behind the prologue, the join, the fetch and the sites are here for both, over kr_ctx::Prod (kr_ctx::Prim's base).
+
 static void prod_geom(const kr_ctx* c, ProdGeom* pg) {
     const auto& l = c->loc;
     const auto& pr = c->prod;
@@ -12,11 +15,9 @@ static void prod_geom(const kr_ctx* c, ProdGeom* pg) {
     pg->len[0] = (u32)l.L; pg->len[1] = (u32)l.R;
     pg->omit = (u32)l.omit; pg->M = (u32)pr.M; pg->nleft2 = (u32)(2 * pr.nleft);
     pg->maxlen = std::max(pg->len[0], pg->len[1]);
-    const u32 NP = (u32)pr.M + 1;
     for (int q = 0; q < 2; q++) {
         pg->end[q] = std::min<u32>(PROD_END, pg->len[q]);
-        for (u32 j = 0; j <= NP; j++) pg->off[q][j] = (u32)((u64)j * pg->len[q] / NP);
-        for (u32 j = 0; j < NP; j++) pg->pw[q][j] = loc_pow((int)(pg->off[q][j + 1] - pg->off[q][j]) - 1);
+        seed_pieces(pg->len[q], (u32)pr.M + 1, pg->off[q], pg->pw[q]);
     }
 }
 
@@ -38,158 +39,149 @@ int64_t kr_products_table(kr_ctx* c, const uint8_t* left, uint64_t nleft, const 
                     (1u << 24) - 1);
     if (npairs >= LOC_EMPTY) return fail(c, KR_ERR_CAPACITY, "kr_products_table: %llu pairs (the limit is %u)",
                                          (unsigned long long)npairs, LOC_EMPTY - 1);
-    pr.slots = 0;
+    pr.seed.slots = 0;
     pr.nsites = pr.nhits = -1;
-    pr.M = M; pr.max_product = max_product; pr.nleft = nleft; pr.nright = nright; pr.npairs = npairs;
+    pr.M = M; pr.max_product = max_product; pr.nleft = nleft; pr.nright = nright; pr.plist.npairs = npairs;
     ProdGeom pg;
     prod_geom(c, &pg);
     const u32 NP = (u32)M + 1;
     const bool one = Le == Re;                      // one length class: the left and right entries share their keys
-    const u64 ne = 2 * (nleft + nright), nk = ne * NP;
+    const u64 ne = 2 * (nleft + nright);
     std::vector<uint8_t> text;
-    std::vector<std::pair<u64, u32>> keyed;
+    SeedKeys keyed;
+    std::vector<u64> pkeys;
     std::vector<u32> pidx;
-    std::vector<std::pair<u64, u32>> pk;
     try {
         text.resize(2 * (nleft * Le + nright * Re) + 16);
         for (u64 e = 0; e < ne; e += 2) {
             const bool lf = e < 2 * nleft;
-            const int n = lf ? Le : Re;
-            const uint8_t* s = lf ? left + (e >> 1) * Le : right + ((e >> 1) - nleft) * Re;
-            uint8_t* f = text.data() + prod_text_at(pg, (u32)e);
-            for (int i = 0; i < n; i++) {
-                f[i] = s[i];
-                f[n + i] = loc_comp(s[n - 1 - i]);
-            }
+            seed_both_strands(text.data() + prod_text_at(pg, (u32)e), lf ? left + (e >> 1) * Le : right + ((e >> 1) - nleft) * Re,
+                              (size_t)(lf ? Le : Re));
         }
-        keyed.reserve(nk);
+        keyed.reserve(ne * NP);
         for (u64 e = 0; e < ne; e++) {
             const u32 q = prod_class(pg, (u32)e);
-            for (u32 j = 0; j < NP; j++)
-                keyed.emplace_back(near_key((one ? 0u : q) * NEAR_MAXP + j, loc_hash(text.data() + prod_text_at(pg, (u32)e) + pg.off[q][j],
-                                                                                     (int)(pg.off[q][j + 1] - pg.off[q][j]))),
-                                   (u32)e);
+            seed_keys(keyed, text.data() + prod_text_at(pg, (u32)e), pg.off[q], NP, (one ? 0u : q) * NEAR_MAXP, (u32)e);
         }
-        pk.reserve(npairs);
-        for (u64 p = 0; p < npairs; p++) {
-            if (pairs[2 * p] >= nleft || pairs[2 * p + 1] >= nright)
-                return fail(c, KR_ERR_PARAM, "kr_products_table: pair %llu names text (%u, %u) of (%llu, %llu)", (unsigned long long)p,
-                            pairs[2 * p], pairs[2 * p + 1], (unsigned long long)nleft, (unsigned long long)nright);
-            pk.emplace_back(((u64)pairs[2 * p] << 32) | pairs[2 * p + 1], (u32)p);
-        }
-        std::sort(pk.begin(), pk.end());
-        for (u64 p = 1; p < npairs; p++)
-            if (pk[p].first == pk[p - 1].first)
-                return fail(c, KR_ERR_PARAM, "kr_products_table: pair %u repeats the texts of pair %u", pk[p].second, pk[p - 1].second);
-        pidx.resize(npairs + 1);
+        if ((rc = pair_list_sort(c, "kr_products_table", pairs, npairs, nleft, nright, pkeys, pidx, [](u64, u32, u32) { return KR_OK; })))
+            return rc;
     } catch (const std::bad_alloc&) {
         return fail(c, KR_ERR_CAPACITY, "kr_products_table: no host memory for the table of %llu texts", (unsigned long long)(nleft + nright));
     }
-    std::vector<u64> pkeys(npairs + 1);
-    for (u64 p = 0; p < npairs; p++) {
-        pkeys[p] = pk[p].first;
-        pidx[p] = pk[p].second;
-    }
-    const int64_t slots = seed_table_build(c, keyed, text, pr.table, pr.arena, pr.list, pr.bitmap, "kr_products_table", nleft + nright,
-                                           "texts");
+    const int64_t slots = seed_table_build(c, keyed, text, pr.seed, "kr_products_table", nleft + nright, "texts");
     if (slots < 0) return slots;
-    if ((rc = ensure(c, pr.pairkeys, pkeys.size() * 8)) || (rc = ensure(c, pr.pairidx, pidx.size() * 4)))
-        return fail(c, rc, "kr_products_table: the table of %llu texts does not fit the device (%s)", (unsigned long long)(nleft + nright),
-                    c->err.c_str());
-    HIPCHK(c, hipMemcpy(pr.pairkeys.p, pkeys.data(), pkeys.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(pr.pairidx.p, pidx.data(), pidx.size() * 4, hipMemcpyHostToDevice));
-    pr.slots = (u64)slots;
+    if ((rc = pair_list_upload(c, pr.plist, pkeys, pidx, "kr_products_table", nleft + nright))) return rc;
+    pr.seed.slots = (u64)slots;
     return slots;
 }
 
-extern "C++" {    // (a template inside the translation unit's extern "C" block)
-template <u32 NP, u32 NC>
-static int prod_sites_launch(kr_ctx* c, const Genome& G, const ProdGeom& pg, u64 nw, u64 ntiles, u64* total_out) {
-    auto& pr = c->prod;
+extern "C++" {    // (templates inside the translation unit's extern "C" block)
+// the primer sites of genome G into st.sites, in two passes of the pass's scan kernels (count, emit) over its table.
+// who: the scan's entry point; over: what to say of 2^32 or more sites; eoff...: the kernels' arguments between the
+// entries' text and nw -- none, or the primer pass's offsets of the entries' text
+template <typename Geom, typename KC, typename KE, typename... E>
+static int prod_sites_launch(kr_ctx* c, const Genome& G, kr_ctx::Prod& st, const Geom& pg, u64 nw, u64 ntiles, const char* who,
+                             const char* over, KC count, KE emit, u64* total_out, E... eoff) {
+    const auto& sd = st.seed;
     const size_t lds = scan_lds_bytes(pg.maxlen, LOC_T * 8);      // (a 64-bit scan array)
-    const u32 grid = scan_grid(c, k_prod_scan<NP, NC, false>, lds, ntiles);
+    const u32 grid = scan_grid(c, count, lds, ntiles);
     auto launch = [&](auto kernel, u32* tc, const u64* to, kr_product_site* out, u32* fl) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(LOC_T), lds, c->stream, (const uint8_t*)G.bases.p, (u64)G.n_bases, pg,
-                           (const u32*)pr.bitmap.p, (const NearSlot*)pr.table.p, (u64)(pr.slots - 1), (const u32*)pr.list.p,
-                           (const uint8_t*)pr.arena.p, nw, ntiles, tc, to, out, fl);
+                           (const u32*)sd.bitmap.p, (const NearSlot*)sd.table.p, (u64)(sd.slots - 1), (const u32*)sd.list.p,
+                           (const uint8_t*)sd.arena.p, eoff..., nw, ntiles, tc, to, out, fl);
     };
     return scan_two_pass(
-        c, ntiles, "kr_products_scan: 2^32 or more primer sites in one genome (fewer mismatches or regions)",
-        [&](u32* tc, u32* fl) { launch(k_prod_scan<NP, NC, false>, tc, nullptr, nullptr, fl); },
+        c, ntiles, over, [&](u32* tc, u32* fl) { launch(count, tc, nullptr, nullptr, fl); },
         [&](u64 total) -> int {
             int rc;
-            if ((rc = ensure(c, pr.sites, total * sizeof(kr_product_site))) || (rc = ensure(c, pr.rec, total * 4)))
-                return fail(c, rc, "kr_products_scan: %llu primer sites do not fit the device (%s)", (unsigned long long)total,
-                            c->err.c_str());
+            if ((rc = ensure(c, st.sites, total * sizeof(kr_product_site))) || (rc = ensure(c, st.rec, total * 4)))
+                return fail(c, rc, "%s: %llu primer sites do not fit the device (%s)", who, (unsigned long long)total, c->err.c_str());
             return KR_OK;
         },
-        [&](u32* tc, const u64* to, u32* fl) { launch(k_prod_scan<NP, NC, true>, tc, to, (kr_product_site*)pr.sites.p, fl); },
-        total_out);
+        [&](u32* tc, const u64* to, u32* fl) { launch(emit, tc, to, (kr_product_site*)st.sites.p, fl); }, total_out);
 }
-}  // extern "C++"
 
-// the join of the sites on the device: -> the number of products
-static int prod_join(kr_ctx* c, const ProdGeom& pg, u64 ns, u64* total_out) {
-    auto& pr = c->prod;
+// the join of the ns sites on the device (the pass's join kernels: count, emit; eoff...: their arguments between the
+// geometry and the pair list) -> the number of products
+template <typename Geom, typename KC, typename KE, typename... E>
+static int prod_join(kr_ctx* c, kr_ctx::Prod& st, const Geom& pg, u64 ns, const char* who, KC count, KE emit, u64* total_out, E... eoff) {
     *total_out = 0;
-    if (!ns || !pr.npairs) return KR_OK;
+    if (!ns || !st.plist.npairs) return KR_OK;
     const u64 nblocks = (ns + LOC_T - 1) / LOC_T;                 // (ns < 2^32: < 2^24 blocks)
+    const std::string over = std::string(who) + ": 2^32 or more products in one genome (a smaller max_product or fewer mismatches)";
     auto launch = [&](auto kernel, u32* bc, const u64* bo, kr_product_hit* out, u32* fl) {
-        hipLaunchKernelGGL(kernel, dim3((u32)nblocks), dim3(LOC_T), 0, c->stream, (const kr_product_site*)pr.sites.p, ns,
-                           (const u32*)pr.rec.p, pg, (const u64*)pr.pairkeys.p, (const u32*)pr.pairidx.p, (u32)pr.npairs, pr.max_product,
-                           bc, bo, out, fl);
+        hipLaunchKernelGGL(kernel, dim3((u32)nblocks), dim3(LOC_T), 0, c->stream, (const kr_product_site*)st.sites.p, ns,
+                           (const u32*)st.rec.p, pg, eoff..., (const u64*)st.plist.pairkeys.p, (const u32*)st.plist.pairidx.p,
+                           (u32)st.plist.npairs, st.max_product, bc, bo, out, fl);
     };
     return scan_two_pass(
-        c, nblocks, "kr_products_scan: 2^32 or more products in one genome (a smaller max_product or fewer mismatches)",
-        [&](u32* bc, u32* fl) { launch(k_prod_join<false>, bc, nullptr, nullptr, fl); },
+        c, nblocks, over.c_str(), [&](u32* bc, u32* fl) { launch(count, bc, nullptr, nullptr, fl); },
         [&](u64 total) {
-            const int rc = ensure(c, pr.hits, total * sizeof(kr_product_hit));
-            return rc ? fail(c, rc, "kr_products_scan: %llu products do not fit the device (%s)", (unsigned long long)total, c->err.c_str())
-                      : KR_OK;
+            const int rc = ensure(c, st.hits, total * sizeof(kr_product_hit));
+            return rc ? fail(c, rc, "%s: %llu products do not fit the device (%s)", who, (unsigned long long)total, c->err.c_str()) : KR_OK;
         },
-        [&](u32* bc, const u64* bo, u32* fl) { launch(k_prod_join<true>, bc, bo, (kr_product_hit*)pr.hits.p, fl); }, total_out);
+        [&](u32* bc, const u64* bo, u32* fl) { launch(emit, bc, bo, (kr_product_hit*)st.hits.p, fl); }, total_out);
 }
 
-int64_t kr_products_scan(kr_ctx* c, int id) {
-    const Genome* Gp;
+// a product pass's scan behind scan_genome: the windows of `width` bases (the shortest text's), the separators, the sites
+// -- sites(nw, ntiles, &ns): the pass's choice of prod_sites_launch by its M --, their records, the join -> the products
+template <typename Geom, typename S, typename KC, typename KE, typename... E>
+static int64_t prod_scan(kr_ctx* c, const Genome& G, kr_ctx::Prod& st, const Geom& pg, u64 width, const char* who, S&& sites, KC join_count,
+                         KE join_emit, E... eoff) {
     int rc;
-    if ((rc = scan_genome(c, id, c && c->prod.slots, "kr_products_table first", &Gp))) return rc;
-    const Genome& G = *Gp;
-    auto& pr = c->prod;
-    pr.nsites = pr.nhits = -1;
-    ProdGeom pg;
-    prod_geom(c, &pg);
-    u64 nw;                                                       // window starts of the shorter class
-    const u64 ntiles = scan_tiles(G.n_bases, std::min(pg.len[0], pg.len[1]), &nw);
-    if (!ntiles || !(pr.nleft + pr.nright)) {
-        pr.nsites = pr.nhits = 0;
+    st.nsites = st.nhits = -1;
+    u64 nw;
+    const u64 ntiles = scan_tiles(G.n_bases, width, &nw);
+    if (!ntiles || !(st.nleft + st.nright)) {
+        st.nsites = st.nhits = 0;
         return 0;
     }
     u64 nseps = 0, ns = 0, np = 0;
     // (the pass's own list: k_prod_rec reads it, and a kr_locate_seps of the caller writes loc.seps)
-    if ((rc = scan_seps(c, G, "kr_products_scan", pr.seps, [&](u64 total) { return ensure(c, pr.seps, total * 8); }, &nseps))) return rc;
-    if (nseps >= (1ull << 32)) return fail(c, KR_ERR_CAPACITY, "kr_products_scan: 2^32 or more records in one genome");
-    const bool one = pg.len[0] == pg.len[1];
-    switch (pg.M + 1) {
-    case 1: rc = one ? prod_sites_launch<1, 1>(c, G, pg, nw, ntiles, &ns) : prod_sites_launch<1, 2>(c, G, pg, nw, ntiles, &ns); break;
-    case 2: rc = one ? prod_sites_launch<2, 1>(c, G, pg, nw, ntiles, &ns) : prod_sites_launch<2, 2>(c, G, pg, nw, ntiles, &ns); break;
-    case 3: rc = one ? prod_sites_launch<3, 1>(c, G, pg, nw, ntiles, &ns) : prod_sites_launch<3, 2>(c, G, pg, nw, ntiles, &ns); break;
-    default: rc = one ? prod_sites_launch<4, 1>(c, G, pg, nw, ntiles, &ns) : prod_sites_launch<4, 2>(c, G, pg, nw, ntiles, &ns); break;
-    }
-    if (rc) return rc;
+    if ((rc = scan_seps(c, G, who, st.seps, [&](u64 total) { return ensure(c, st.seps, total * 8); }, &nseps))) return rc;
+    if (nseps >= (1ull << 32)) return fail(c, KR_ERR_CAPACITY, "%s: 2^32 or more records in one genome", who);
+    if ((rc = sites(nw, ntiles, &ns))) return rc;
     if (ns) {
         const u32 grid = scan_stride_grid(c, (ns + 255) / 256);
-        hipLaunchKernelGGL(k_prod_rec, dim3(grid), dim3(256), 0, c->stream, (const kr_product_site*)pr.sites.p, ns,
-                           (const u64*)pr.seps.p, nseps, (u32*)pr.rec.p);
-        if ((rc = prod_join(c, pg, ns, &np))) return rc;
+        hipLaunchKernelGGL(k_prod_rec, dim3(grid), dim3(256), 0, c->stream, (const kr_product_site*)st.sites.p, ns,
+                           (const u64*)st.seps.p, nseps, (u32*)st.rec.p);
+        if ((rc = prod_join(c, st, pg, ns, who, join_count, join_emit, &np, eoff...))) return rc;
     }
-    pr.nsites = (int64_t)ns;
-    pr.nhits = (int64_t)np;
+    st.nsites = (int64_t)ns;
+    st.nhits = (int64_t)np;
     return (int64_t)np;
 }
 
-// the products of one position in (length, strand, pair) order (kr_products_fetch, kr_primers_fetch: the device lists
-// them by opening site -- position, then the sites' order there --, so positions ascend already)
+template <u32 NP, u32 NC>
+static int prod_sites_np(kr_ctx* c, const Genome& G, const ProdGeom& pg, u64 nw, u64 ntiles, u64* ns) {
+    return prod_sites_launch(c, G, c->prod, pg, nw, ntiles, "kr_products_scan",
+                             "kr_products_scan: 2^32 or more primer sites in one genome (fewer mismatches or regions)",
+                             k_prod_scan<NP, NC, false>, k_prod_scan<NP, NC, true>, ns);
+}
+}  // extern "C++"
+
+int64_t kr_products_scan(kr_ctx* c, int id) {
+    const Genome* Gp;
+    int rc;
+    if ((rc = scan_genome(c, id, c && c->prod.seed.slots, "kr_products_table first", &Gp))) return rc;
+    const Genome& G = *Gp;
+    ProdGeom pg;
+    prod_geom(c, &pg);
+    const bool one = pg.len[0] == pg.len[1];
+    auto sites = [&](u64 nw, u64 ntiles, u64* ns) {
+        switch (pg.M + 1) {
+        case 1: return one ? prod_sites_np<1, 1>(c, G, pg, nw, ntiles, ns) : prod_sites_np<1, 2>(c, G, pg, nw, ntiles, ns);
+        case 2: return one ? prod_sites_np<2, 1>(c, G, pg, nw, ntiles, ns) : prod_sites_np<2, 2>(c, G, pg, nw, ntiles, ns);
+        case 3: return one ? prod_sites_np<3, 1>(c, G, pg, nw, ntiles, ns) : prod_sites_np<3, 2>(c, G, pg, nw, ntiles, ns);
+        default: return one ? prod_sites_np<4, 1>(c, G, pg, nw, ntiles, ns) : prod_sites_np<4, 2>(c, G, pg, nw, ntiles, ns);
+        }
+    };
+    // (window starts of the shorter class)
+    return prod_scan(c, G, c->prod, pg, std::min(pg.len[0], pg.len[1]), "kr_products_scan", sites, k_prod_join<false>, k_prod_join<true>);
+}
+
+// the products of one position in (length, strand, pair) order (prod_fetch: the device lists them by opening site --
+// position, then the sites' order there --, so positions ascend already)
 static void prod_sort_positions(kr_product_hit* out, int64_t n) {
     auto less = [](const kr_product_hit& a, const kr_product_hit& b) {
         if (a.pos != b.pos) return a.pos < b.pos;
@@ -205,18 +197,25 @@ static void prod_sort_positions(kr_product_hit* out, int64_t n) {
     }
 }
 
-int64_t kr_products_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) {
+// kr_products_fetch and -- primers -- kr_primers_fetch
+static int64_t prod_fetch(kr_ctx* c, bool primers, const char* scan_first, kr_product_hit* out, size_t cap) {
     int rc;
     if ((rc = scan_ctx(c))) return rc;
-    const int64_t n = scan_fetch(c, c->prod.nhits, "kr_products_scan first", "product", c->prod.hits, out, cap, sizeof(kr_product_hit));
+    const kr_ctx::Prod& st = primers ? static_cast<const kr_ctx::Prod&>(c->prim) : c->prod;
+    const int64_t n = scan_fetch(c, st.nhits, scan_first, "product", st.hits, out, cap, sizeof(kr_product_hit));
     prod_sort_positions(out, n);
     return n;
 }
 
-int64_t kr_products_sites(kr_ctx* c, kr_product_site* out, size_t cap) {
+// kr_products_sites and -- primers -- kr_primers_sites
+static int64_t prod_sites(kr_ctx* c, bool primers, const char* scan_first, kr_product_site* out, size_t cap) {
     int rc;
     if ((rc = scan_ctx(c))) return rc;
-    const int64_t n = c->prod.nsites;
-    if (n >= 0 && !out) return n;                   // (the count alone)
-    return scan_fetch(c, n, "kr_products_scan first", "site", c->prod.sites, out, cap, sizeof(kr_product_site));
+    const kr_ctx::Prod& st = primers ? static_cast<const kr_ctx::Prod&>(c->prim) : c->prod;
+    if (st.nsites >= 0 && !out) return st.nsites;   // (the count alone)
+    return scan_fetch(c, st.nsites, scan_first, "site", st.sites, out, cap, sizeof(kr_product_site));
 }
+
+int64_t kr_products_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) { return prod_fetch(c, false, "kr_products_scan first", out, cap); }
+
+int64_t kr_products_sites(kr_ctx* c, kr_product_site* out, size_t cap) { return prod_sites(c, false, "kr_products_scan first", out, cap); }

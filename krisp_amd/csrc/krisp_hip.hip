@@ -44,7 +44,7 @@
 #include "k_inflate.inc"     // BGZF members inflated on the device, a lane per member (round 6)
 #include "k_gunzip.inc"      // one plain gzip member inflated on the device: chunks, block starts found by trial, windows
 #include "k_wide.inc"        // wide path kernels, copy kernel
-#include "k_scan.inc"        // what the three one-genome scans share: tile staging, block scan, two-pass epilogue, seed probe, separators
+#include "k_scan.inc"        // what the six one-genome scans share: tile staging, block scan, two-pass epilogue, seed probe, separators
 #include "k_locate.inc"      // the locate pass: flank-table scan of a genome's bases
 #include "k_near.inc"        // the near-match pass: pigeonhole seeds of the targets, scan within Hamming distance M
 #include "k_guide_hits.inc"  // the guide-hit pass: behind the near pass's scan a per-hit step (ghit_step.inc: column mask, PAM motifs), need_pam's selection
@@ -58,12 +58,13 @@
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
 #include "h_intersect.inc"   // kr_intersect, candidate lists, kr_collect
 #include "h_wide.inc"        // kr_wide_run
-#include "h_scan.inc"        // ... and on the host: two-pass driver, separator list, seed table, launch geometry, fetches
+#include "h_scan.inc"        // ... and on the host: two-pass driver, separator list, launch geometry, fetches; for the five seed passes the
+                             // pieces, entries and keys, the seed table, the near-scan launcher, the pair list (its header: which helper serves which)
 #include "h_locate.inc"      // kr_set_params_locate, kr_locate_*: where the surviving groups' windows lie
 #include "h_near.inc"        // kr_near_*: the windows of a genome within M substitutions of an ingroup window
 #include "h_guide_hits.inc"  // kr_guide_hits_*: the windows of a genome within M substitutions of a picked guide, with their motifs
 #include "h_guide_bulges.inc" // kr_guide_bulges_*: the windows of a genome within M substitutions and one bulge of a picked guide
-#include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome
+#include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome; the scan, join, fetch and sites of both product passes
 #include "h_primers.inc"     // kr_primers_*: in-silico PCR of designed primer pairs against a genome
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options
 #include "h_guides.inc"      // kr_guides_*: a CRISPR guide per region from its template, its outgroup rows and the guide options
