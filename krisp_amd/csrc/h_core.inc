@@ -57,6 +57,11 @@ struct Lane {
     DevBuf partial16, cursor, h16exc;   // fine histogram from the codes (k_hist16), pass-2 reservation cursors, counts beyond 16 bits
     DevBuf pass0, base64;    // sliced genomes: all keys partitioned by their top byte, the 64-bit bucket bases
     DevBuf slt, offa, cura;  // ... and their pass 1 by k_scatter2: small tables, offsets / cursors of the (slice, top byte) bins
+    // the lane's device buffers, named here alone (kr_destroy, and take_lane's retreat to one lane, release them)
+    void bufs(std::vector<DevBuf*>& v) {
+        v.insert(v.end(), {&codes, &bad, &partial8, &base1, &tmpkeys, &tp, &tiledesc, &tilehist, &wkeys, &pass0, &base64,
+                           &partial16, &cursor, &h16exc, &slt, &offa, &cura});
+    }
 };
 #define MAX_LANES 8
 
@@ -486,6 +491,27 @@ static void coarse_pool_release(kr_ctx* c) {
     c->cpool_free.clear();
 }
 
+// a slice's arrays and its pair of mailbox words
+static void release_slice(kr_ctx* c, Slice& S) {
+    release(c, S.keys);
+    release(c, S.off);
+    release(c, S.chunkstart);
+    release(c, S.chunkdesc);
+    release(c, S.ovf);
+    if (S.res >= 0) c->mb_free.push_back(S.res);
+}
+// a genome whose slices were planned for another slice count starts over with the context's
+static void reset_slices(kr_ctx* c, Genome& G) {
+    if ((int)G.sl.size() == c->nslices) return;
+    for (Slice& S : G.sl) release_slice(c, S);
+    G.sl.assign(c->nslices, Slice());
+}
+// what every new upload and every new sort makes of a genome's state
+static void genome_unsorted(Genome& G) {
+    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
+    G.count = -1;
+}
+
 static void release_genome(kr_ctx* c, Genome& G) {
     coarse_pool_return(c, G);
     if (G.up_done) { (void)hipEventDestroy(G.up_done); G.up_done = nullptr; }
@@ -493,14 +519,7 @@ static void release_genome(kr_ctx* c, Genome& G) {
     release(c, G.wkeys);
     release(c, G.wlcnt);
     release(c, G.hits);
-    for (Slice& S : G.sl) {
-        release(c, S.keys);
-        release(c, S.off);
-        release(c, S.chunkstart);
-        release(c, S.chunkdesc);
-        release(c, S.ovf);
-        if (S.res >= 0) c->mb_free.push_back(S.res);
-    }
+    for (Slice& S : G.sl) release_slice(c, S);
     G.sl.clear();
 }
 
@@ -574,6 +593,28 @@ static int join_lanes(kr_ctx* c) {
         HIPCHK(c, hipStreamWaitEvent(c->stream, ln.done, 0));
         ln.pending = false;
     }
+    return KR_OK;
+}
+
+// a lane's stream and `done` event, made when the lane is first used
+static int lane_open(kr_ctx* c, Lane& ln) {
+    if (ln.stream) return KR_OK;
+    HIPCHK(c, hipStreamCreate(&ln.stream));
+    HIPCHK(c, hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
+    return KR_OK;
+}
+// the scratch of lanes first .. MAX_LANES - 1 goes back
+static void release_lanes(kr_ctx* c, int first) {
+    std::vector<DevBuf*> lb;
+    for (int i = first; i < MAX_LANES; i++) c->lanes[i].bufs(lb);
+    for (DevBuf* b : lb) release(c, *b);
+}
+// k_hist16's list of counts beyond 16 bits: its count is cleared once, on `st` (k_chunk_table clears it after every use)
+static int ensure_h16exc(kr_ctx* c, Lane& ln, hipStream_t st) {
+    if (ln.h16exc.p) return KR_OK;
+    int rc;
+    if ((rc = ensure(c, ln.h16exc, (1 + 3 * (size_t)H16_EXC_CAP) * 4))) return rc;
+    HIPCHK(c, hipMemsetAsync(ln.h16exc.p, 0, 16, st));
     return KR_OK;
 }
 
@@ -661,9 +702,7 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
     bool ok = hipHostMalloc((void**)&c->mbox, MB_WORDS * 4 + PUB_CAP * sizeof(PubEnt), hipHostMallocMapped) == hipSuccess &&
               hipEventCreate(&c->t0) == hipSuccess && hipEventCreate(&c->t1) == hipSuccess &&
               hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; ok && i < 1; i++)         // (the other lanes get their streams when they are first used: ensure_lanes)
-        ok = hipStreamCreate(&c->lanes[i].stream) == hipSuccess &&
-             hipEventCreateWithFlags(&c->lanes[i].done, hipEventDisableTiming) == hipSuccess;
+    ok = ok && lane_open(c, c->lanes[0]) == KR_OK;      // (the other lanes get their streams when they are first used: ensure_lanes)
     if (!ok) {
         g_last_error = "stream / event creation failed";
         delete c;
@@ -681,12 +720,7 @@ void kr_destroy(kr_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     resolve_stages(c);
-    for (int i = 0; i < MAX_LANES; i++) {
-        Lane& ln = c->lanes[i];
-        DevBuf* lb[] = {&ln.codes, &ln.bad, &ln.partial8, &ln.base1, &ln.tmpkeys, &ln.tp, &ln.tiledesc, &ln.tilehist, &ln.wkeys,
-                        &ln.pass0, &ln.base64, &ln.partial16, &ln.cursor, &ln.h16exc, &ln.slt, &ln.offa, &ln.cura};
-        for (DevBuf* b : lb) release(c, *b);
-    }
+    release_lanes(c, 0);
     for (auto& kv : c->genomes) release_genome(c, kv.second);
     coarse_pool_release(c);
     DevBuf* all[] = {&c->candA, &c->candB, &c->chunkcnt,
@@ -1209,10 +1243,7 @@ static int ensure_lanes(kr_ctx* c, u64 maxcount) {
     c->lanes_ready = lanes_used(c);
     for (int i = 0; i < lanes_used(c); i++) {
         Lane& ln = c->lanes[i];
-        if (!ln.stream) {
-            HIPCHK(c, hipStreamCreate(&ln.stream));
-            HIPCHK(c, hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
-        }
+        if ((rc = lane_open(c, ln))) return rc;
         if ((rc = ensure(c, ln.codes, mw * 8))) return rc;
         if ((rc = ensure(c, ln.bad, mw * 4))) return rc;
         if ((rc = ensure(c, ln.partial8, (size_t)NWG * 256 * 4))) return rc;
@@ -1223,10 +1254,7 @@ static int ensure_lanes(kr_ctx* c, u64 maxcount) {
         if ((rc = ensure(c, ln.tilehist, ntmax * (nb >> 8) * 4))) return rc;
         if (USE_HIST16 && nb > 256) {
             if ((rc = ensure(c, ln.partial16, (size_t)H16_RANGES * nb * 2 + 64))) return rc;
-            if (!ln.h16exc.p) {
-                if ((rc = ensure(c, ln.h16exc, (1 + 3 * (size_t)H16_EXC_CAP) * 4))) return rc;
-                HIPCHK(c, hipMemsetAsync(ln.h16exc.p, 0, 16, ln.stream));       // (once: k_chunk_table clears the count after every use)
-            }
+            if ((rc = ensure_h16exc(c, ln, ln.stream))) return rc;
             if ((rc = ensure(c, ln.cursor, ((size_t)nb + 4) * 4))) return rc;
         }
     }
@@ -1253,26 +1281,16 @@ static void launch_scatter1(const Geom& g, hipStream_t st, const u64* codes, con
     // per thread (p1_fast_keys; KR_P1_FAST=0: the general one, A/B and tests)
     static const bool fast_on = [] { const char* e = getenv("KR_P1_FAST"); return e ? atoi(e) != 0 : true; }();
     const bool fast = fast_on && g.wmode == 0 && g.strands == 0 && g.rot == 0 && g.npc == 0 && (u32)((g.mR | g.mD) >> 32) == 0u;
-    if (fast && big)
-        hipLaunchKernelGGL((k_scatter1p<0, 1, 1>), dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
-    else if (fast)
-        hipLaunchKernelGGL((k_scatter1p<0, 0, 1>), dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
-    else if (g.wmode == 1)
-        hipLaunchKernelGGL(k_scatter1w<1>, dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, g);
-    else if (g.wmode && g.wcmode == 4)
+    if (g.wmode && g.wmode != 1 && g.wcmode == 4) {
         hipLaunchKernelGGL(k_scatter1l, dim3(NWG), dim3(P1_T), 0, st, base1, base64, rowoff, dst, g);
-    else if (g.wmode && g.wcmode == 2)
-        hipLaunchKernelGGL(k_scatter1w<3>, dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, g);
-    else if (g.wmode)
-        hipLaunchKernelGGL(k_scatter1w<2>, dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, g);
-    else if (g.strands && big)
-        hipLaunchKernelGGL((k_scatter1p<2, 1>), dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
-    else if (g.strands)
-        hipLaunchKernelGGL((k_scatter1p<2, 0>), dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
-    else if (big)
-        hipLaunchKernelGGL((k_scatter1p<0, 1>), dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
-    else
-        hipLaunchKernelGGL((k_scatter1p<0, 0>), dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
+    } else if (g.wmode) {
+        const auto kw = g.wmode == 1 ? k_scatter1w<1> : g.wcmode == 2 ? k_scatter1w<3> : k_scatter1w<2>;
+        hipLaunchKernelGGL(kw, dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, g);
+    } else {
+        const auto kp = fast ? (big ? k_scatter1p<0, 1, 1> : k_scatter1p<0, 0, 1>)
+                             : g.strands ? (big ? k_scatter1p<2, 1> : k_scatter1p<2, 0>) : (big ? k_scatter1p<0, 1> : k_scatter1p<0, 0>);
+        hipLaunchKernelGGL(kp, dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
+    }
 }
 
 // pass 2: tiles of 2 * P2_TILE keys, one per workgroup of 2 * P2_T threads (512-byte runs at fan-out
@@ -1283,21 +1301,32 @@ static void launch_scatter2(hipStream_t st, const u64* src, u64* dst, const uint
 }
 
 static void launch_hist8(kr_ctx* c, Genome& G, Lane& ln, hipStream_t st, const Geom& g) {
-    if (g.wmode == 1)
-        hipLaunchKernelGGL(k_hist8w<1>, dim3(NWG), dim3(P1_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p,
-                           G.nwords, (u32*)ln.partial8.p, g);
-    else if (g.wmode && g.wcmode == 2)
-        hipLaunchKernelGGL(k_hist8w<3>, dim3(NWG), dim3(P1_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p,
-                           G.nwords, (u32*)ln.partial8.p, g);
-    else if (g.wmode)
-        hipLaunchKernelGGL(k_hist8w<2>, dim3(NWG), dim3(P1_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p,
-                           G.nwords, (u32*)ln.partial8.p, g);
-    else if (g.strands)
-        hipLaunchKernelGGL(k_hist8<2>, dim3(NWG), dim3(P1_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p,
-                           G.nwords, (u32*)ln.partial8.p, g);
-    else
-        hipLaunchKernelGGL(k_hist8<0>, dim3(NWG), dim3(P1_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p,
-                           G.nwords, (u32*)ln.partial8.p, g);
+    const auto kh = g.wmode == 1 ? k_hist8w<1> : g.wmode ? (g.wcmode == 2 ? k_hist8w<3> : k_hist8w<2>) : g.strands ? k_hist8<2> : k_hist8<0>;
+    hipLaunchKernelGGL(kh, dim3(NWG), dim3(P1_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p, G.nwords,
+                       (u32*)ln.partial8.p, g);
+}
+
+// the pass-2 tile: 16 keys per thread; 1024-thread workgroups (16384-key tiles, one per CU) keep a tile's runs at 512 bytes
+// for fan-out 2^16 and 256 / 128 bytes for 2^17 / 2^18.  p2_tiles: the tiles of a slice of nmax keys at most, whose 256
+// top-byte buckets each end in a tile of their own
+static constexpr u32 P2_KEYS = 2 * P2_TILE;
+static u32 p2_tiles(u64 nmax) { return (u32)(nmax / P2_KEYS) + 257; }
+
+// the lane the next sort takes: count_slices looks at it, take_lane takes it -- the same one (genome_sort(., reuse_count)
+// finds count_slices' codes, bad bits and reduced histogram in its scratch)
+static Lane& peek_lane(kr_ctx* c) {
+    if (c->next_lane >= lanes_used(c)) c->next_lane = 0;
+    return c->lanes[c->next_lane];
+}
+
+// the context's geometry without slices: what pass 0, and the count in front of it, see of a key.  counting: the wide
+// path's cached composite keys are WRITTEN by this histogram (as a list, Geom.wlcnt, or 16 bytes per window start)
+static Geom pass0_geom(const kr_ctx* c, bool counting = false) {
+    Geom g0 = c->g;
+    g0.sbits = 0;
+    g0.slice = 0;
+    if (counting && g0.wmode == 2 && g0.wcache) g0.wcmode = g0.wlcnt ? 3 : 1;
+    return g0;
 }
 
 // exact key count of every slice under the current geometry (sizes the slice arrays):
@@ -1307,30 +1336,19 @@ static int count_slices(kr_ctx* c, Genome& G) {
     if ((rc = ensure_lanes(c, 16))) return rc;
     // the lane the genome's sort will take (genome_sort, right behind this call, finds the counts and the packed
     // codes in its scratch)
-    if (c->next_lane >= lanes_used(c)) c->next_lane = 0;
-    Lane& ln = c->lanes[c->next_lane];
+    Lane& ln = peek_lane(c);
     hipStream_t st = ln.stream;
     ln.pending = true;
     if (G.up_done && st != c->stream) HIPCHK(c, hipStreamWaitEvent(st, G.up_done, 0));
     launch_pack(c, G, ln, st);
-    if ((int)G.sl.size() != c->nslices) {
-        for (Slice& S : G.sl) {
-            release(c, S.keys); release(c, S.off); release(c, S.chunkstart); release(c, S.chunkdesc); release(c, S.ovf);
-            if (S.res >= 0) c->mb_free.push_back(S.res);
-        }
-        G.sl.assign(c->nslices, Slice());
-    }
+    reset_slices(c, G);
     std::vector<u32> tot(256);
     u64 maxcount = 0;
     G.nmax = 0;
-    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
+    genome_unsorted(G);
     coarse_pool_return(c, G);
-    G.count = -1;
     // ONE histogram of the top byte of the absolute keys: a slice is 2^(8 - sbits) of its buckets
-    Geom g0 = c->g;
-    g0.sbits = 0;
-    g0.slice = 0;
-    if (g0.wmode == 2 && g0.wcache) g0.wcmode = g0.wlcnt ? 3 : 1;
+    const Geom g0 = pass0_geom(c, true);
     {
         StageScope sc(c, KR_ST_HIST8, st);
         launch_hist8(c, G, ln, st, g0);
@@ -1384,9 +1402,8 @@ int kr_genome_upload(kr_ctx* c, int id, const uint8_t* bases, size_t n) {
     G.id = id;
     G.n_bases = n;
     G.nwords = (n + 31) / 32;
-    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
+    genome_unsorted(G);
     coarse_pool_return(c, G);
-    G.count = -1;
     int rc;
     if ((rc = ensure(c, G.bases, n + 64))) return rc;
     if (!G.up_done) HIPCHK(c, hipEventCreateWithFlags(&G.up_done, hipEventDisableTiming));
@@ -1410,13 +1427,7 @@ static int upload_finish(kr_ctx* c, Genome& G, int id, size_t n) {
     if (c->nslices == 1) {
         // one sort unit: its arrays are sized by the bound 2 n (exact unless the genome holds N /
         // soft-masked windows); no counting pass, no device -> host copy, no wait
-        if ((int)G.sl.size() != 1) {
-            for (Slice& S : G.sl) {
-                release(c, S.keys); release(c, S.off); release(c, S.chunkstart); release(c, S.chunkdesc); release(c, S.ovf);
-                if (S.res >= 0) c->mb_free.push_back(S.res);
-            }
-            G.sl.assign(1, Slice());
-        }
+        reset_slices(c, G);
         const u64 bound = 2 * (u64)n;
         if (bound >= KR_MAX_SLICE_KEYS)
             return fail(c, KR_ERR_CAPACITY, "genome %d: %llu keys in one sort unit (the limit is %llu)", id,
@@ -1443,20 +1454,14 @@ static int ensure_slice_lanes(kr_ctx* c, int helper) {
     const u64 maxcount = c->lane_maxcount;
     const u64 ntmax = maxcount / P2_TILE + 260;
     int rc;
-    for (int i = helper; i <= helper; i++) {
-        Lane& ln = c->lanes[i];
-        if (!ln.stream) {
-            HIPCHK(c, hipStreamCreate(&ln.stream));
-            HIPCHK(c, hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
-        }
-        if ((rc = ensure(c, ln.base1, (260 + 256) * 4))) return rc;
-        if ((rc = ensure(c, ln.tp, 260 * 4))) return rc;
-        if ((rc = ensure(c, ln.slt, 1024 * 4))) return rc;
-        if ((rc = ensure(c, ln.tiledesc, ntmax * 8))) return rc;
-        if ((rc = ensure(c, ln.tilehist, ntmax * (nb >> 8) * 4))) return rc;
-        if ((rc = ensure(c, ln.tmpkeys, (maxcount + 2) * 8))) return rc;
-    }
-    return KR_OK;
+    Lane& ln = c->lanes[helper];
+    if ((rc = lane_open(c, ln))) return rc;
+    if ((rc = ensure(c, ln.base1, (260 + 256) * 4))) return rc;
+    if ((rc = ensure(c, ln.tp, 260 * 4))) return rc;
+    if ((rc = ensure(c, ln.slt, 1024 * 4))) return rc;
+    if ((rc = ensure(c, ln.tiledesc, ntmax * 8))) return rc;
+    if ((rc = ensure(c, ln.tilehist, ntmax * (nb >> 8) * 4))) return rc;
+    return ensure(c, ln.tmpkeys, (maxcount + 2) * 8);
 }
 
 // The large buffers of `n` genomes of up to n_bases bases (or bytes of file text), made AHEAD of the uploads -- while host
@@ -1478,13 +1483,7 @@ int kr_reserve(kr_ctx* c, const int* ids, int n, size_t n_bases, int with_text) 
         G.id = ids[i];
         if ((rc = ensure(c, G.bases, n_bases + 64))) return rc;
         if (c->wide.on || c->g.wmode) continue;
-        if ((int)G.sl.size() != c->nslices) {
-            for (Slice& S : G.sl) {
-                release(c, S.keys); release(c, S.off); release(c, S.chunkstart); release(c, S.chunkdesc); release(c, S.ovf);
-                if (S.res >= 0) c->mb_free.push_back(S.res);
-            }
-            G.sl.assign(c->nslices, Slice());
-        }
+        reset_slices(c, G);
         if (per_slice >= KR_MAX_SLICE_KEYS) continue;           // (the upload will say so)
         for (Slice& S : G.sl)
             if ((rc = ensure(c, S.keys, (per_slice + 2) * 8))) return rc;
@@ -1513,28 +1512,61 @@ int kr_genome_partition(kr_ctx* c, int id) {
     return genome_sort(c, id, false, coarse_eligible(c));
 }
 
-// reuse_count: count_slices(G) has just run on this lane (single lane): the codes, the bad
-// bits and the workgroup histograms of the absolute top byte (already prefix-summed by
-// k_reduce8a) are still in the lane's scratch
-static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
-    if (!c) return KR_ERR_PARAM;
-    auto it = c->genomes.find(id);
-    if (it == c->genomes.end() || !it->second.uploaded) return fail(c, KR_ERR_STATE, "genome %d not uploaded", id);
-    if (it->second.sl.empty()) return fail(c, KR_ERR_STATE, "genome %d has no slice plan (wide windows: use kr_wide_run)", id);
-    HIPCHK(c, hipSetDevice(c->device));
-    Genome& G = it->second;
-    const u32 nb = 1u << c->g.b;
-    c->sorts_done++;
+// What one sort does: decided once (sort_plan), read by every pass.
+struct SortPlan {
+    bool reuse_count;   // count_slices(G) has just run on this lane (single lane): the codes, the bad bits and the workgroup
+                        // histograms of the absolute top byte (already prefix-summed by k_reduce8a) are still in the lane's scratch
+    bool coarse;        // kr_genome_partition on an eligible context: the sort stops behind pass 1
+    bool lazy;          // ... or at the fine buckets: no LDS sort
+    bool sliced, route2, fine16;
+    bool cached_keys;   // the wide path's composite keys are read back from the genome's cache
+    int cached_mode;    // ... (the key list, Geom.wlcnt, or 16 bytes per window start)
+    int nba;            // absolute top bits: (slice, top byte of the relative key)
+    u32 h16_ranges;
+    int nsl, helper;    // lanes the genome's slices take turns on: the genome's own, and nsl - 1 from lane `helper` on
+};
+
+static SortPlan sort_plan(const kr_ctx* c, const Genome& G, const Lane& ln, bool reuse_count, bool coarse) {
+    SortPlan p{};
+    p.reuse_count = reuse_count;
+    p.coarse = coarse;
+    p.cached_keys = reuse_count && c->g.wmode == 2 && c->g.wcache;
+    p.cached_mode = c->g.wlcnt ? 4 : 2;
+    p.sliced = c->nslices > 1;
+    // KR_OPT_LAZY_ORDER: keys of both strands -- the packed path's (left,right,diag) keys, the wide path's spectra and
+    // composite keys: what kr_intersect / kr_collect work on -- stop at the fine buckets; single-strand and custom-layout
+    // (kstream) sorts are read in order right away and end with the LDS sort as before.  KR_LAZY_WIDE=0: the wide path eager (A/B)
+    static const bool lazy_wide = [] { const char* e = getenv("KR_LAZY_WIDE"); return e ? atoi(e) != 0 : true; }();
+    p.lazy = c->lazy_order && (lazy_wide || (!c->wide.on && c->g.wmode == 0)) && !c->custom_layout && c->g.strands == 0 &&
+             !c->order_wanted && !(G.was_anchor && !c->i3_last_ua);       // (an anchor the fused kernel takes needs no order either)
+    // sliced, packed windows of both strands whose top 8 + 2 sb bits lie inside `left`: every slice's pass 1 is a
+    // k_scatter2 over its pass-0 buckets, counted from the codes once per genome (k_sort.inc, "Round 4"); else (the wide
+    // path's generators, single-strand modes, KR_SLICE_ROUTE=0) a slice counts its top byte per workgroup (k_hist8k)
+    // and scatters with private cursors (k_scatter1kp)
+    p.nba = 8 + c->g.sbits;
+    p.route2 = p.sliced && USE_HIST16 && c->slice_route && c->g.wmode == 0 && c->g.strands == 0 && 2 * c->g.L >= p.nba && p.nba <= 16;
+    // k_hist16's ranges: 16-bit counters need < 65536 keys per (range, top byte); 256 .. NWG ranges
+    p.h16_ranges = H16_RANGES;
+    if (p.route2)
+        while (p.h16_ranges < NWG && G.nmax / ((u64)p.h16_ranges * 256) > 30000) p.h16_ranges *= 2;
+    // fine offsets straight from the codes when the top b bits of a key lie inside `left`
+    p.fine16 = USE_HIST16 && c->g.b > 8 && !p.sliced && c->g.wmode == 0 && c->g.strands == 0 && 2 * c->g.L >= c->g.b;
+    // Round 4: the slices of a genome take turns on up to three lanes (their own stream and pass-1 / pass-2 scratch; the
+    // pass-0 array, the codes and the (slice, top byte) offsets are the genome's and only read), so the kernels of
+    // consecutive slices overlap on the device as the sorts of consecutive genomes do in the unsliced case.
+    p.nsl = p.route2 ? slice_lanes(c) : 1;
+    p.helper = SLICE_HELPER + SLICE_HELPERS * (int)(&ln - c->lanes);
+    return p;
+}
+
+// The sort's lane: more lanes first when the automatic count has grown, then the next in turn, marked busy and ordered
+// behind the genome's upload.
+static int take_lane(kr_ctx* c, Genome& G, Lane*& taken) {
     if (lanes_used(c) > c->lanes_ready) {         // (automatic lanes: the context has sorted enough genomes for more than one)
         int rcl = ensure_lanes(c, c->lane_maxcount);
         if (rcl && c->nlanes == 0) {
             // no room for the scratch of more lanes (HBM budget, a nearly full device): one lane it stays
-            for (int i = 1; i < MAX_LANES; i++) {
-                Lane& lx = c->lanes[i];
-                DevBuf* lb[] = {&lx.codes, &lx.bad, &lx.partial8, &lx.base1, &lx.tmpkeys, &lx.tp, &lx.tiledesc, &lx.tilehist,
-                                &lx.wkeys, &lx.pass0, &lx.base64, &lx.partial16, &lx.cursor, &lx.h16exc, &lx.slt, &lx.offa, &lx.cura};
-                for (DevBuf* b : lb) release(c, *b);
-            }
+            release_lanes(c, 1);
             c->nlanes = 1;
             c->lanes_ready = 1;
             c->next_lane = 0;
@@ -1543,257 +1575,290 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
         }
         if (rcl) return rcl;
     }
-    if (c->next_lane >= lanes_used(c)) c->next_lane = 0;
-    Lane& ln = c->lanes[c->next_lane];
+    Lane& ln = peek_lane(c);
     c->last_lane = c->next_lane;
     c->next_lane = (c->next_lane + 1) % lanes_used(c);
     ln.pending = true;
     hipStream_t st = ln.stream;
-    if (it->second.up_done && st != c->stream) HIPCHK(c, hipStreamWaitEvent(st, it->second.up_done, 0));
-    u64* codes = (u64*)ln.codes.p;
-    u32* bad = (u32*)ln.bad.p;
-    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
-    G.count = -1;
+    if (G.up_done && st != c->stream) HIPCHK(c, hipStreamWaitEvent(st, G.up_done, 0));
+    taken = &ln;
+    return KR_OK;
+}
+
+// The pool of placed pass-1 targets at the head of a sort: a buffer this sort cannot write goes back, a coarse sort
+// without one takes the fastest free one.
+static void coarse_pool_step(kr_ctx* c, Genome& G, bool coarse) {
     const size_t cbytes = ((size_t)c->lane_maxcount + 2) * 8;       // (a pooled buffer has the size of a lane's tmpkeys)
     if (G.ckeys.p && (!coarse || !c->coarse_pool || G.ckeys.bytes < cbytes)) coarse_pool_return(c, G);
     if (coarse) {
         G.partitions++;
         if (c->coarse_pool && !G.ckeys.p) (void)coarse_pool_take(c, G, cbytes);
     }
-    const bool cached_keys = reuse_count && c->g.wmode == 2 && c->g.wcache;
-    const int cached_mode = c->g.wlcnt ? 4 : 2;         // (the key list, Geom.wlcnt, or 16 bytes per window start)
-    const bool sliced = c->nslices > 1;
-    // KR_OPT_LAZY_ORDER: keys of both strands -- the packed path's (left,right,diag) keys, the wide path's spectra and
-    // composite keys: what kr_intersect / kr_collect work on -- stop at the fine buckets; single-strand and custom-layout
-    // (kstream) sorts are read in order right away and end with the LDS sort as before.  KR_LAZY_WIDE=0: the wide path eager (A/B)
-    static const bool lazy_wide = [] { const char* e = getenv("KR_LAZY_WIDE"); return e ? atoi(e) != 0 : true; }();
-    const bool lazy = c->lazy_order && (lazy_wide || (!c->wide.on && c->g.wmode == 0)) && !c->custom_layout && c->g.strands == 0 &&
-                      !c->order_wanted && !(G.was_anchor && !c->i3_last_ua);       // (an anchor the fused kernel takes needs no order either)
-    if (sliced) {
-        // the slices of the genome this lane sorted before may still run on its helper lane, out of this lane's arrays
-        for (int h = 0; h < SLICE_HELPERS; h++) {
-            Lane& hp = c->lanes[SLICE_HELPER + SLICE_HELPERS * (int)(&ln - c->lanes) + h];
-            if (hp.stream && hp.pending) {
-                HIPCHK(c, hipEventRecord(hp.done, hp.stream));
-                HIPCHK(c, hipStreamWaitEvent(st, hp.done, 0));
-            }
+}
+
+static void pass_pack(kr_ctx* c, Genome& G, Lane& ln) {
+    StageScope sc(c, KR_ST_PACK, ln.stream);
+    launch_pack(c, G, ln, ln.stream);
+}
+
+// Pass 0 of a sliced genome: all its keys, generated once, partitioned by their top byte; slice s is the contiguous
+// run of its 2^(8 - sbits) buckets.  route2: also the (slice, top byte) bins every slice's pass 1 will scatter by.
+static int pass0(kr_ctx* c, Genome& G, const SortPlan& p, Lane& ln) {
+    hipStream_t st = ln.stream;
+    int rc;
+    // the slices of the genome this lane sorted before may still run on its helper lane, out of this lane's arrays
+    for (int h = 0; h < SLICE_HELPERS; h++) {
+        Lane& hp = c->lanes[p.helper + h];
+        if (hp.stream && hp.pending) {
+            HIPCHK(c, hipEventRecord(hp.done, hp.stream));
+            HIPCHK(c, hipStreamWaitEvent(st, hp.done, 0));
         }
     }
-    // sliced, packed windows of both strands whose top 8 + 2 sb bits lie inside `left`: every slice's pass 1 is a
-    // k_scatter2 over its pass-0 buckets, counted from the codes once per genome (k_sort.inc, "Round 4"); else (the wide
-    // path's generators, single-strand modes, KR_SLICE_ROUTE=0) a slice counts its top byte per workgroup (k_hist8k)
-    // and scatters with private cursors (k_scatter1kp)
-    const int nba = 8 + c->g.sbits;                 // absolute top bits: (slice, top byte of the relative key)
-    const bool route2 = sliced && USE_HIST16 && c->slice_route && c->g.wmode == 0 && c->g.strands == 0 && 2 * c->g.L >= nba && nba <= 16;
-    u32 h16_ranges = H16_RANGES;
-    if (route2) {
-        // k_hist16's ranges: 16-bit counters need < 65536 keys per (range, top byte); 256 .. NWG ranges
-        while (h16_ranges < NWG && G.nmax / ((u64)h16_ranges * 256) > 30000) h16_ranges *= 2;
-        int rce;
-        if ((rce = ensure(c, ln.partial16, ((size_t)h16_ranges << nba) * 2 + 64))) return rce;
-        if (!ln.h16exc.p) {
-            if ((rce = ensure(c, ln.h16exc, (1 + 3 * (size_t)H16_EXC_CAP) * 4))) return rce;
-            HIPCHK(c, hipMemsetAsync(ln.h16exc.p, 0, 16, st));
-        }
-        if ((rce = ensure(c, ln.slt, 1024 * 4))) return rce;
-        if ((rce = ensure(c, ln.offa, (((size_t)1 << nba) + 4) * 4))) return rce;
-        if ((rce = ensure(c, ln.cura, (((size_t)1 << nba) + 4) * 4))) return rce;
+    if (p.route2) {
+        if ((rc = ensure(c, ln.partial16, ((size_t)p.h16_ranges << p.nba) * 2 + 64))) return rc;
+        if ((rc = ensure_h16exc(c, ln, st))) return rc;
+        if ((rc = ensure(c, ln.slt, 1024 * 4))) return rc;
+        if ((rc = ensure(c, ln.offa, (((size_t)1 << p.nba) + 4) * 4))) return rc;
+        if ((rc = ensure(c, ln.cura, (((size_t)1 << p.nba) + 4) * 4))) return rc;
     }
-    if (!reuse_count) {
-        StageScope sc(c, KR_ST_PACK, st);
-        launch_pack(c, G, ln, st);
+    if (!p.reuse_count) pass_pack(c, G, ln);
+    if ((rc = ensure(c, ln.pass0, (G.nmax + 2) * 8))) return rc;
+    if (!p.reuse_count) {
+        StageScope sc(c, KR_ST_HIST8, st);
+        launch_hist8(c, G, ln, st, pass0_geom(c, true));
     }
-    if (sliced) {
-        // pass 0: all keys of the genome, generated once, partitioned by their top byte; slice s
-        // is the contiguous run of its 2^(8 - sbits) buckets
-        if (ln.pass0.bytes < (G.nmax + 2) * 8) {
-            int rcp = ensure(c, ln.pass0, (G.nmax + 2) * 8);
-            if (rcp) return rcp;
-        }
-        Geom g0 = c->g;
-        g0.sbits = 0;
-        g0.slice = 0;
-        if (!reuse_count) {
-            if (g0.wmode == 2 && g0.wcache) g0.wcmode = g0.wlcnt ? 3 : 1;
-            StageScope sc(c, KR_ST_HIST8, st);
-            launch_hist8(c, G, ln, st, g0);
+    {
+        StageScope sc(c, KR_ST_REDUCE8, st);
+        if (!p.reuse_count)
+            hipLaunchKernelGGL(k_reduce8a, dim3(256), dim3(256), 0, st, (u32*)ln.partial8.p, (u32*)ln.base1.p + 260);
+        hipLaunchKernelGGL(k_bases64, dim3(1), dim3(64), 0, st, (const u32*)ln.base1.p + 260, (u64*)ln.base64.p);
+    }
+    Geom g0 = pass0_geom(c);
+    g0.wcmode = (g0.wmode == 2 && g0.wcache) ? p.cached_mode : 0;
+    g0.slice = (u32)c->g.sbits;          // (P0_DIGIT_BITS of k_scatter1p<., 1>: pass 0 partitions by the slice alone)
+    {
+        StageScope sc(c, KR_ST_SCATTER1, st);
+        launch_scatter1(g0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p, G.nwords, (const u32*)nullptr,
+                        (const u64*)ln.base64.p, (const u32*)ln.partial8.p, (u64*)ln.pass0.p, G.nmax);
+    }
+    if (!p.route2) return KR_OK;
+    // the (slice, top byte) bins of the whole genome from the codes: offsets relative to each slice's start
+    {
+        StageScope sc(c, KR_ST_HIST2, st);
+        hipLaunchKernelGGL(k_hist16, dim3(p.h16_ranges, 1), dim3(H16_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p,
+                           G.nwords, (const u32*)ln.partial8.p, (const u32*)ln.base1.p + 260,
+                           (unsigned short*)ln.partial16.p, (u32*)ln.h16exc.p, c->g.k, p.nba);
+    }
+    StageScope sc(c, KR_ST_SCAN2, st);
+    hipLaunchKernelGGL(k_bases_rel, dim3(1), dim3(256), 0, st, (const u32*)ln.base1.p + 260, 256u >> c->g.sbits,
+                       (u32*)ln.slt.p);
+    hipLaunchKernelGGL(k_hist16_off, dim3(256), dim3(1024), 0, st, (const unsigned short*)ln.partial16.p, p.h16_ranges,
+                       p.nba, (const u32*)ln.h16exc.p, (const u32*)ln.slt.p, (u32*)ln.offa.p, (u32*)ln.cura.p);
+    return KR_OK;
+}
+
+// The slices go to their lanes: pass 0 and the offsets are behind `slice_ready`, the helper lanes (made here when they
+// are first needed) wait for it.
+static int slice_lanes_start(kr_ctx* c, const SortPlan& p, Lane& ln) {
+    int rcs;
+    hipStream_t st = ln.stream;
+    hipEvent_t& ready = c->slice_ready[(int)(&ln - c->lanes)];
+    if (!ready) HIPCHK(c, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(ready, st));
+    for (int h = p.helper; h < p.helper + SLICE_HELPERS; h++) {
+        if ((rcs = ensure_slice_lanes(c, h))) return rcs;
+        HIPCHK(c, hipStreamWaitEvent(c->lanes[h].stream, ready, 0));
+        c->lanes[h].pending = true;
+    }
+    return KR_OK;
+}
+
+// Where a slice's pass 1 writes: the lane's scratch when a pass 2 follows, else the slice's keys -- or, for a coarse genome
+// that holds one, its placed buffer of the pool, whose last owner's kernels may still be at it on another stream.
+static int pass1_target(kr_ctx* c, Genome& G, const SortPlan& p, Lane& ls, Slice& S, u64*& pass1_dst) {
+    hipStream_t ss = ls.stream;
+    pass1_dst = (c->g.b > 8 && !p.coarse) ? (u64*)ls.tmpkeys.p : (u64*)S.keys.p;
+    if (!p.coarse || !G.ckeys.p) return KR_OK;
+    pass1_dst = (u64*)G.ckeys.p;
+    if (G.ckeys_busy && G.ckeys_busy != ss) coarse_pool_handover(c, G);      // (its own last pass 1, on another lane)
+    if (G.ckeys_wait) {
+        HIPCHK(c, hipStreamWaitEvent(ss, G.ckeys_ev, 0));
+        G.ckeys_wait = false;
+    }
+    G.ckeys_busy = ss;
+    c->cpool_partitions++;
+    return KR_OK;
+}
+
+// Pass 1 of slice s, route2: a k_scatter2 over the slice's pass-0 buckets by the bins pass0() counted.
+// (ln: the genome's lane, whose scratch holds what belongs to the genome; ls: the slice's lane and stream)
+static void pass1_route2(kr_ctx* c, const SortPlan& p, Lane& ln, Lane& ls, Slice& S, int s, const u64* src, u64* pass1_dst) {
+    hipStream_t ss = ls.stream;
+    const int b = c->g.b;
+    const u32 ntA = (u32)((S.nmax + P2_KEYS - 1) / P2_KEYS);
+    if (ntA) {
+        StageScope sc(c, KR_ST_SCATTER1, ss);
+        launch_scatter2(ss, src, pass1_dst, (const uint2*)nullptr, ntA, (const u32*)nullptr, (u32*)ln.cura.p, p.nba, c->g.sbits,
+                        (u32)S.nmax);
+    }
+    StageScope sc(c, KR_ST_REDUCE8, ss);
+    const u32 ntmax = b > 8 ? p2_tiles(S.nmax) : 0u;
+    hipLaunchKernelGGL(k_reduce8b, dim3(std::max(1u, (ntmax + 255) / 256)), dim3(256), 0, ss, (const u32*)nullptr,
+                       (u32*)ls.base1.p, (u32*)ls.tp.p, b > 8 ? P2_KEYS : 0u, ntmax, (uint2*)ls.tiledesc.p,
+                       (const u32*)ln.offa.p + (size_t)s * 256, (u32)S.nmax);
+}
+
+// Pass 1 of slice s, counted: the top byte's histogram per workgroup (of the slice's pass-0 run, or of the codes; not
+// after count_slices, whose histogram is still there), its reduction, the scatter with private cursors.
+static void pass1_counted(kr_ctx* c, Genome& G, const SortPlan& p, Lane& ln, Lane& ls, Slice& S, int s, const u64* src,
+                          u64* pass1_dst) {
+    hipStream_t ss = ls.stream;
+    Geom g = slice_geom(c, (u32)s);
+    if (p.cached_keys) g.wcmode = p.cached_mode;
+    if (p.sliced) {
+        StageScope sc(c, KR_ST_HIST8, ss);
+        hipLaunchKernelGGL(k_hist8k, dim3(NWG), dim3(P1_T), 0, ss, src, (u64)S.nmax, g.sbits, (u32*)ln.partial8.p);
+    } else if (!p.reuse_count) {
+        StageScope sc(c, KR_ST_HIST8, ss);
+        launch_hist8(c, G, ln, ss, g);
+    }
+    {
+        StageScope sc(c, KR_ST_REDUCE8, ss);
+        if (p.sliced || !p.reuse_count)
+            hipLaunchKernelGGL(k_reduce8a, dim3(256), dim3(256), 0, ss, (u32*)ln.partial8.p, (u32*)ls.base1.p + 260);
+        const u32 ntmax = (g.b > 8 && !p.coarse) ? p2_tiles(S.nmax) : 0u;
+        hipLaunchKernelGGL(k_reduce8b, dim3(std::max(1u, (ntmax + 255) / 256)), dim3(256), 0, ss,
+                           (const u32*)ls.base1.p + 260, (u32*)ls.base1.p, (u32*)ls.tp.p, ntmax ? P2_KEYS : 0u, ntmax,
+                           (uint2*)ls.tiledesc.p, (const u32*)nullptr, 0u);
+    }
+    StageScope sc(c, KR_ST_SCATTER1, ss);
+    if (p.sliced)
+        hipLaunchKernelGGL(k_scatter1kp, dim3(NWG), dim3(P1_T), 0, ss, src, (u64)S.nmax, g.sbits,
+                           (const u32*)ls.base1.p, (const u32*)ln.partial8.p, pass1_dst, (u32)S.nmax);
+    else
+        launch_scatter1(g, ss, (const u64*)ln.codes.p, (const u32*)ln.bad.p, G.nwords, (const u32*)ls.base1.p,
+                        (const u64*)nullptr, (const u32*)ln.partial8.p, pass1_dst, S.nmax);
+}
+
+// The coarse exit: the buckets' bases leave the lane's scratch; the words finalize() reads: no oversized bucket, the key count.
+static void coarse_exit(kr_ctx* c, Lane& ls, Slice& S) {
+    StageScope sc(c, KR_ST_REDUCE8, ls.stream);
+    hipLaunchKernelGGL(k_coarse_keep, dim3(1), dim3(320), 0, ls.stream, (const u32*)ls.base1.p, (u32*)S.off.p, 1u << c->g.b,
+                       (u32*)S.ovf.p);
+}
+
+// Pass 2 of a slice, from the lane's pass-1 array into the slice's keys: by fine offsets counted from the codes
+// (fine16), or from the pass-1 keys (k_hist2 / k_scan2); at fan-out 2^8 pass 1 was the whole partition and its bases
+// are the offsets.
+static int pass2(kr_ctx* c, Genome& G, const SortPlan& p, Lane& ln, Lane& ls, Slice& S) {
+    hipStream_t ss = ls.stream;
+    const int b = c->g.b;
+    const u32 nb = 1u << b;
+    if (b <= 8) {
+        HIPCHK(c, hipMemcpyAsync(S.off.p, ls.base1.p, 257 * 4, hipMemcpyDeviceToDevice, ss));
+        return KR_OK;
+    }
+    const u32 ntmax = p2_tiles(S.nmax);
+    if (p.fine16) {
+        {
+            StageScope sc(c, KR_ST_HIST2, ss);
+            const u32 parts = nb > H16_BINS ? nb / H16_BINS : 1;
+            hipLaunchKernelGGL(k_hist16, dim3(H16_RANGES, parts), dim3(H16_T), 0, ss, (const u64*)ln.codes.p,
+                               (const u32*)ln.bad.p, G.nwords, (const u32*)ln.partial8.p, (const u32*)ls.base1.p + 260,
+                               (unsigned short*)ln.partial16.p, (u32*)ln.h16exc.p, c->g.k, b);
         }
         {
-            StageScope sc(c, KR_ST_REDUCE8, st);
-            if (!reuse_count)
-                hipLaunchKernelGGL(k_reduce8a, dim3(256), dim3(256), 0, st, (u32*)ln.partial8.p, (u32*)ln.base1.p + 260);
-            hipLaunchKernelGGL(k_bases64, dim3(1), dim3(64), 0, st, (const u32*)ln.base1.p + 260, (u64*)ln.base64.p);
+            StageScope sc(c, KR_ST_SCAN2, ss);
+            hipLaunchKernelGGL(k_hist16_off, dim3(256), dim3(1024), 0, ss, (const unsigned short*)ln.partial16.p,
+                               (u32)H16_RANGES, b, (const u32*)ln.h16exc.p, (const u32*)ls.base1.p, (u32*)S.off.p,
+                               (u32*)ls.cursor.p);
         }
-        g0.wcmode = (g0.wmode == 2 && g0.wcache) ? cached_mode : 0;
-        (void)cached_keys;
-        g0.slice = (u32)c->g.sbits;          // (P0_DIGIT_BITS of k_scatter1p<., 1>: pass 0 partitions by the slice alone)
-        {
-            StageScope sc(c, KR_ST_SCATTER1, st);
-            launch_scatter1(g0, st, (const u64*)codes, (const u32*)bad, G.nwords, (const u32*)nullptr,
-                            (const u64*)ln.base64.p, (const u32*)ln.partial8.p, (u64*)ln.pass0.p, G.nmax);
-        }
-        if (route2) {
-            // the (slice, top byte) bins of the whole genome from the codes: offsets relative to each slice's start
-            {
-                StageScope sc(c, KR_ST_HIST2, st);
-                hipLaunchKernelGGL(k_hist16, dim3(h16_ranges, 1), dim3(H16_T), 0, st, (const u64*)codes, (const u32*)bad,
-                                   G.nwords, (const u32*)ln.partial8.p, (const u32*)ln.base1.p + 260,
-                                   (unsigned short*)ln.partial16.p, (u32*)ln.h16exc.p, c->g.k, nba);
-            }
-            StageScope sc(c, KR_ST_SCAN2, st);
-            hipLaunchKernelGGL(k_bases_rel, dim3(1), dim3(256), 0, st, (const u32*)ln.base1.p + 260, 256u >> c->g.sbits,
-                               (u32*)ln.slt.p);
-            hipLaunchKernelGGL(k_hist16_off, dim3(256), dim3(1024), 0, st, (const unsigned short*)ln.partial16.p, h16_ranges,
-                               nba, (const u32*)ln.h16exc.p, (const u32*)ln.slt.p, (u32*)ln.offa.p, (u32*)ln.cura.p);
-        }
+        StageScope sc(c, KR_ST_SCATTER2, ss);
+        launch_scatter2(ss, (const u64*)ls.tmpkeys.p, (u64*)S.keys.p, (const uint2*)ls.tiledesc.p, ntmax, (const u32*)nullptr,
+                        (u32*)ls.cursor.p, b);
+        return KR_OK;
     }
-    // Round 4: the slices of a genome take turns on up to three lanes (their own stream and pass-1 / pass-2 scratch; the
-    // pass-0 array, the codes and the (slice, top byte) offsets are the genome's and only read), so the kernels of
-    // consecutive slices overlap on the device as the sorts of consecutive genomes do in the unsliced case.
-    const int nsl = route2 ? slice_lanes(c) : 1;
-    const int lane_idx = (int)(&ln - c->lanes), helper = SLICE_HELPER + SLICE_HELPERS * lane_idx;
-    if (nsl > 1) {
-        int rcs;
-        hipEvent_t& ready = c->slice_ready[lane_idx];
-        if (!ready) HIPCHK(c, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(ready, st));                           // pass 0 and the offsets are behind this point
-        for (int h = helper; h < helper + SLICE_HELPERS; h++) {
-            if ((rcs = ensure_slice_lanes(c, h))) return rcs;
-            HIPCHK(c, hipStreamWaitEvent(c->lanes[h].stream, ready, 0));
-            c->lanes[h].pending = true;
-        }
+    {
+        StageScope sc(c, KR_ST_HIST2, ss);
+        hipLaunchKernelGGL(k_hist2<2 * P2_T>, dim3(ntmax), dim3(2 * P2_T), 0, ss, (const u64*)ls.tmpkeys.p,
+                           (const uint2*)ls.tiledesc.p, (u32*)ls.tilehist.p, b);
     }
+    {
+        StageScope sc(c, KR_ST_SCAN2, ss);
+        hipLaunchKernelGGL(k_scan2, dim3(256), dim3(1024), 0, ss, (u32*)ls.tilehist.p, (const u32*)ls.base1.p,
+                           (const u32*)ls.tp.p, (u32*)S.off.p, b);
+    }
+    StageScope sc(c, KR_ST_SCATTER2, ss);
+    launch_scatter2(ss, (const u64*)ls.tmpkeys.p, (u64*)S.keys.p, (const uint2*)ls.tiledesc.p, ntmax, (const u32*)ls.tilehist.p,
+                    (u32*)nullptr, b);
+    return KR_OK;
+}
+
+// k_localsort2 over `ntiles` descriptors of S's keys: what it cannot take it lists in S.ovf (segments from byte 16)
+static void launch_localsort(kr_ctx* c, Slice& S, const DevBuf& desc, u32 ntiles, hipStream_t st) {
+    hipLaunchKernelGGL(k_localsort2, dim3(std::min<u32>(ntiles, (u32)c->ls_grid)), dim3(LS_THREADS), 0, st, (u64*)S.keys.p,
+                       (const u32*)S.off.p, (const uint4*)desc.p, ntiles, c->g.b, (u32*)S.ovf.p, (uint4*)((char*)S.ovf.p + 16));
+}
+
+// The chunk table of a slice's fine buckets, and -- unless the order is left for later -- the LDS sort inside them.
+static void chunks_and_order(kr_ctx* c, const SortPlan& p, Lane& ln, Lane& ls, Slice& S) {
+    hipStream_t ss = ls.stream;
+    {
+        StageScope sc(c, KR_ST_CHUNKS, ss);
+        hipLaunchKernelGGL(k_chunk_table, dim3((S.nchunks + 255) / 256), dim3(256), 0, ss, (const u32*)S.off.p, 1u << c->g.b,
+                           S.nchunks, (uint4*)S.chunkdesc.p, (u32*)S.ovf.p, (p.fine16 || p.route2) ? (u32*)ln.h16exc.p : (u32*)nullptr);
+    }
+    if (p.lazy) {
+        c->lazy_skipped++;
+        return;
+    }
+    // (what finalize() will want to know -- S.ovf[0], S.off[nb] -- goes to the host mailbox when somebody asks:
+    // publish_slices, one launch for all slices asked about)
+    StageScope sc(c, KR_ST_LOCALSORT, ss);
+    launch_localsort(c, S, S.chunkdesc, S.nchunks, ss);
+}
+
+// The sort of one genome, enqueued on its lane(s): the table of contents of the passes above.
+static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
+    if (!c) return KR_ERR_PARAM;
+    auto it = c->genomes.find(id);
+    if (it == c->genomes.end() || !it->second.uploaded) return fail(c, KR_ERR_STATE, "genome %d not uploaded", id);
+    if (it->second.sl.empty()) return fail(c, KR_ERR_STATE, "genome %d has no slice plan (wide windows: use kr_wide_run)", id);
+    HIPCHK(c, hipSetDevice(c->device));
+    Genome& G = it->second;
+    c->sorts_done++;
+    int rc;
+    Lane* lane;
+    if ((rc = take_lane(c, G, lane))) return rc;
+    Lane& ln = *lane;
+    genome_unsorted(G);
+    coarse_pool_step(c, G, coarse);
+    const SortPlan p = sort_plan(c, G, ln, reuse_count, coarse);
+    if (p.sliced) {
+        if ((rc = pass0(c, G, p, ln))) return rc;
+    } else if (!reuse_count) {
+        pass_pack(c, G, ln);
+    }
+    if (p.nsl > 1 && (rc = slice_lanes_start(c, p, ln))) return rc;
     u64 region = 0;       // start of the current slice inside the pass-0 array
     for (int s = 0; s < c->nslices; s++) {
         Slice& S = G.sl[s];
-        Lane& ls = (nsl > 1 && s % nsl) ? c->lanes[helper + s % nsl - 1] : ln;       // the slice's scratch and stream
-        hipStream_t ss = ls.stream;
-        Geom g = slice_geom(c, (u32)s);
-        if (cached_keys) g.wcmode = cached_mode;
-        S.count = -1;
+        Lane& ls = (p.nsl > 1 && s % p.nsl) ? c->lanes[p.helper + s % p.nsl - 1] : ln;       // the slice's scratch and stream
         const u64* src = (const u64*)ln.pass0.p + region;
         region += S.nmax;
-        const u32 tile2 = 2 * P2_TILE;
-        u64* pass1_dst = (g.b > 8 && !coarse) ? (u64*)ls.tmpkeys.p : (u64*)S.keys.p;
-        if (coarse && G.ckeys.p) {
-            // a placed buffer of the pool: its last owner's kernels may still be at it on another stream
-            pass1_dst = (u64*)G.ckeys.p;
-            if (G.ckeys_busy && G.ckeys_busy != ss) coarse_pool_handover(c, G);      // (its own last pass 1, on another lane)
-            if (G.ckeys_wait) {
-                HIPCHK(c, hipStreamWaitEvent(ss, G.ckeys_ev, 0));
-                G.ckeys_wait = false;
-            }
-            G.ckeys_busy = ss;
-            c->cpool_partitions++;
-        }
-        if (route2) {
-            const u32 ntA = (u32)((S.nmax + tile2 - 1) / tile2);
-            if (ntA) {
-                StageScope sc(c, KR_ST_SCATTER1, ss);
-                launch_scatter2(ss, src, pass1_dst, (const uint2*)nullptr, ntA, (const u32*)nullptr, (u32*)ln.cura.p, nba, g.sbits,
-                                (u32)S.nmax);
-            }
-            StageScope sc(c, KR_ST_REDUCE8, ss);
-            const u32 ntmax = g.b > 8 ? (u32)(S.nmax / tile2) + 257 : 0u;
-            hipLaunchKernelGGL(k_reduce8b, dim3(std::max(1u, (ntmax + 255) / 256)), dim3(256), 0, ss, (const u32*)nullptr,
-                               (u32*)ls.base1.p, (u32*)ls.tp.p, g.b > 8 ? tile2 : 0u, ntmax, (uint2*)ls.tiledesc.p,
-                               (const u32*)ln.offa.p + (size_t)s * 256, (u32)S.nmax);
-        } else {
-        if (sliced) {
-            StageScope sc(c, KR_ST_HIST8, ss);
-            hipLaunchKernelGGL(k_hist8k, dim3(NWG), dim3(P1_T), 0, ss, src, (u64)S.nmax, g.sbits, (u32*)ln.partial8.p);
-        } else if (!reuse_count) {
-            StageScope sc(c, KR_ST_HIST8, ss);
-            launch_hist8(c, G, ln, ss, g);
-        }
-        // pass-2 tile: 16 keys per thread; 1024-thread workgroups (16384-key tiles, one per CU) keep
-        // a tile's runs at 512 bytes for fan-out 2^16 and 256 / 128 bytes for 2^17 / 2^18
-        {
-            StageScope sc(c, KR_ST_REDUCE8, ss);
-            if (sliced || !reuse_count)
-                hipLaunchKernelGGL(k_reduce8a, dim3(256), dim3(256), 0, ss, (u32*)ln.partial8.p, (u32*)ls.base1.p + 260);
-            const u32 ntmax = (g.b > 8 && !coarse) ? (u32)(S.nmax / tile2) + 257 : 0u;
-            hipLaunchKernelGGL(k_reduce8b, dim3(std::max(1u, (ntmax + 255) / 256)), dim3(256), 0, ss,
-                               (const u32*)ls.base1.p + 260, (u32*)ls.base1.p, (u32*)ls.tp.p, ntmax ? tile2 : 0u, ntmax,
-                               (uint2*)ls.tiledesc.p, (const u32*)nullptr, 0u);
-        }
-        {
-            StageScope sc(c, KR_ST_SCATTER1, ss);
-            if (sliced)
-                hipLaunchKernelGGL(k_scatter1kp, dim3(NWG), dim3(P1_T), 0, ss, src, (u64)S.nmax, g.sbits,
-                                   (const u32*)ls.base1.p, (const u32*)ln.partial8.p, pass1_dst, (u32)S.nmax);
-            else
-                launch_scatter1(g, ss, (const u64*)codes, (const u32*)bad, G.nwords, (const u32*)ls.base1.p,
-                                (const u64*)nullptr, (const u32*)ln.partial8.p, pass1_dst, S.nmax);
-        }
-        }
+        S.count = -1;
+        u64* pass1_dst;
+        if ((rc = pass1_target(c, G, p, ls, S, pass1_dst))) return rc;
+        if (p.route2) pass1_route2(c, p, ln, ls, S, s, src, pass1_dst);
+        else pass1_counted(c, G, p, ln, ls, S, s, src, pass1_dst);
         if (coarse) {
-            // (the buckets' bases leave the lane's scratch; the words finalize() reads: no oversized bucket, the key count)
-            StageScope sc(c, KR_ST_REDUCE8, ss);
-            hipLaunchKernelGGL(k_coarse_keep, dim3(1), dim3(320), 0, ss, (const u32*)ls.base1.p, (u32*)S.off.p, nb, (u32*)S.ovf.p);
+            coarse_exit(c, ls, S);
             continue;
         }
-        // fine offsets straight from the codes when the top b bits of a key lie inside `left`
-        const bool fine16 = USE_HIST16 && g.b > 8 && !sliced && g.wmode == 0 && g.strands == 0 && 2 * g.L >= g.b;
-        if (fine16) {
-            const u32 ntmax = (u32)(S.nmax / tile2) + 257;
-            {
-                StageScope sc(c, KR_ST_HIST2, ss);
-                const u32 parts = nb > H16_BINS ? nb / H16_BINS : 1;
-                hipLaunchKernelGGL(k_hist16, dim3(H16_RANGES, parts), dim3(H16_T), 0, ss, (const u64*)codes,
-                                   (const u32*)bad, G.nwords, (const u32*)ln.partial8.p, (const u32*)ls.base1.p + 260,
-                                   (unsigned short*)ln.partial16.p, (u32*)ln.h16exc.p, g.k, g.b);
-            }
-            {
-                StageScope sc(c, KR_ST_SCAN2, ss);
-                hipLaunchKernelGGL(k_hist16_off, dim3(256), dim3(1024), 0, ss,
-                                   (const unsigned short*)ln.partial16.p, (u32)H16_RANGES, g.b, (const u32*)ln.h16exc.p,
-                                   (const u32*)ls.base1.p,
-                                   (u32*)S.off.p, (u32*)ls.cursor.p);
-            }
-            {
-                StageScope sc(c, KR_ST_SCATTER2, ss);
-                launch_scatter2(ss, (const u64*)ls.tmpkeys.p, (u64*)S.keys.p, (const uint2*)ls.tiledesc.p, ntmax,
-                                (const u32*)nullptr, (u32*)ls.cursor.p, g.b);
-            }
-        } else if (g.b > 8) {
-            const u32 ntmax = (u32)(S.nmax / tile2) + 257;
-            {
-                StageScope sc(c, KR_ST_HIST2, ss);
-                hipLaunchKernelGGL(k_hist2<2 * P2_T>, dim3(ntmax), dim3(2 * P2_T), 0, ss, (const u64*)ls.tmpkeys.p,
-                                   (const uint2*)ls.tiledesc.p, (u32*)ls.tilehist.p, g.b);
-            }
-            {
-                StageScope sc(c, KR_ST_SCAN2, ss);
-                hipLaunchKernelGGL(k_scan2, dim3(256), dim3(1024), 0, ss, (u32*)ls.tilehist.p, (const u32*)ls.base1.p,
-                                   (const u32*)ls.tp.p, (u32*)S.off.p, g.b);
-            }
-            {
-                StageScope sc(c, KR_ST_SCATTER2, ss);
-                launch_scatter2(ss, (const u64*)ls.tmpkeys.p, (u64*)S.keys.p, (const uint2*)ls.tiledesc.p, ntmax,
-                                (const u32*)ls.tilehist.p, (u32*)nullptr, g.b);
-            }
-        } else {
-            HIPCHK(c, hipMemcpyAsync(S.off.p, ls.base1.p, 257 * 4, hipMemcpyDeviceToDevice, ss));
-        }
-        {
-            StageScope sc(c, KR_ST_CHUNKS, ss);
-            hipLaunchKernelGGL(k_chunk_table, dim3((S.nchunks + 255) / 256), dim3(256), 0, ss, (const u32*)S.off.p, nb,
-                               S.nchunks, (uint4*)S.chunkdesc.p, (u32*)S.ovf.p, (fine16 || route2) ? (u32*)ln.h16exc.p : (u32*)nullptr);
-        }
-        if (!lazy) {
-            StageScope sc(c, KR_ST_LOCALSORT, ss);
-            const u32 grid = std::min<u32>(S.nchunks, (u32)c->ls_grid);
-            hipLaunchKernelGGL(k_localsort2, dim3(grid), dim3(LS_THREADS), 0, ss, (u64*)S.keys.p,
-                               (const u32*)S.off.p, (const uint4*)S.chunkdesc.p, S.nchunks, g.b, (u32*)S.ovf.p,
-                               (uint4*)((char*)S.ovf.p + 16));
-            // (what finalize() will want to know -- S.ovf[0], S.off[nb] -- goes to the host mailbox when somebody
-            // asks: publish_slices, one launch for all slices asked about)
-        } else {
-            c->lazy_skipped++;
-        }
+        if ((rc = pass2(c, G, p, ln, ls, S))) return rc;
+        chunks_and_order(c, p, ln, ls, S);
     }
-    G.ordered = !lazy && !coarse;
+    G.ordered = !p.lazy && !coarse;
     G.sorted = !coarse;   // enqueued; oversized buckets (if any) are resolved by finalize()
     G.coarse = coarse;
     return KR_OK;
@@ -1833,9 +1898,7 @@ static int order_genome(kr_ctx* c, Genome& G, hipStream_t st) {
     for (Slice& S : G.sl) {
         HIPCHK(c, hipMemsetAsync(S.ovf.p, 0, 16, st));
         StageScope sc(c, KR_ST_LOCALSORT, st);
-        const u32 grid = std::min<u32>(S.nchunks, (u32)c->ls_grid);
-        hipLaunchKernelGGL(k_localsort2, dim3(grid), dim3(LS_THREADS), 0, st, (u64*)S.keys.p, (const u32*)S.off.p,
-                           (const uint4*)S.chunkdesc.p, S.nchunks, c->g.b, (u32*)S.ovf.p, (uint4*)((char*)S.ovf.p + 16));
+        launch_localsort(c, S, S.chunkdesc, S.nchunks, st);
         c->lazy_ordered++;
     }
     G.ordered = true;
@@ -1853,6 +1916,61 @@ static int ensure_ordered(kr_ctx* c, const std::vector<Genome*>& gs) {
     if (rc) return rc;
     for (Genome* G : gs)
         if ((rc = order_genome(c, *G, c->stream))) return rc;
+    return KR_OK;
+}
+
+// The merge fallback of finalize(): slice S of `total` keys has `novf` buckets the LDS sort could not take (listed in
+// S.ovf; more than OVF_MAX: the whole slice counts as one).  Their 4096-key tiles are sorted by the LDS sorter and merged
+// in global memory, through lane 0's pass-1 array, on stream `st`.
+static int repair_slice(kr_ctx* c, Slice& S, u32 novf, u32 total, hipStream_t st) {
+    StageScope sc(c, KR_ST_FALLBACK);
+    const u32 nb = 1u << c->g.b;
+    std::vector<uint4> segs;
+    uint4* dsegs = (uint4*)((char*)S.ovf.p + 16);
+    if (novf > OVF_MAX) {
+        segs.push_back(make_uint4(0, total, 0, nb));      // everything: bucket range [0, nb)
+    } else {
+        segs.resize(novf);
+        HIPCHK(c, hipMemcpy(segs.data(), dsegs, (size_t)novf * 16, hipMemcpyDeviceToHost));
+        for (auto& sg : segs) sg.w = sg.z + 1;               // bucket range [f, f + 1)
+    }
+    c->overflow_segments += (int64_t)segs.size();
+    // (1) sort the 4096-key tiles of every segment with the LDS sorter
+    std::vector<uint4> tiles;
+    u32 maxlen = 0;
+    for (auto& sg : segs) {
+        maxlen = std::max(maxlen, sg.y - sg.x);
+        for (u32 t = sg.x; t < sg.y; t += LS_CAP) tiles.push_back(make_uint4(t, std::min(t + LS_CAP, sg.y), sg.z, sg.w));
+    }
+    int rc;
+    if ((rc = ensure(c, c->fbdesc, tiles.size() * 16 + 16))) return rc;
+    if ((rc = ensure(c, c->fbsegs, (segs.size() + 1) * 16))) return rc;
+    HIPCHK(c, hipMemcpy(c->fbdesc.p, tiles.data(), tiles.size() * 16, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(S.ovf.p, 0, 16, st));
+    launch_localsort(c, S, c->fbdesc, (u32)tiles.size(), st);
+    c->fallback_launches++;
+    // (2) merge rounds: runs of `run` keys -> 2 * run, through the lane scratch and back
+    Lane& ln = c->lanes[0];
+    if ((rc = ensure(c, ln.tmpkeys, ((size_t)total + 2) * 8))) return rc;
+    for (u64 run = LS_CAP; run < maxlen; run *= 2) {
+        std::vector<uint4> act;
+        u32 ntiles = 0;
+        for (auto& sg : segs) {
+            u32 len = sg.y - sg.x;
+            if (len <= run) continue;
+            act.push_back(make_uint4(sg.x, sg.y, ntiles, 0));
+            ntiles += (len + MG_TILE - 1) / MG_TILE;
+        }
+        if (act.empty()) break;
+        HIPCHK(c, hipMemcpy(c->fbsegs.p, act.data(), act.size() * 16, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_seg_merge, dim3(ntiles), dim3(MG_T), 0, st, (const u64*)S.keys.p,
+                           (u64*)ln.tmpkeys.p, (const uint4*)c->fbsegs.p, (u32)act.size(), (u32)run);
+        hipLaunchKernelGGL(k_seg_copy, dim3(ntiles), dim3(256), 0, st, (const u64*)ln.tmpkeys.p,
+                           (u64*)S.keys.p, (const uint4*)c->fbsegs.p, (u32)act.size());
+        HIPCHK(c, hipStreamSynchronize(st));      // fbsegs is rewritten next round
+        c->fallback_launches += 2;
+    }
+    HIPCHK(c, hipGetLastError());
     return KR_OK;
 }
 
@@ -1878,7 +1996,6 @@ static int finalize(kr_ctx* c, const std::vector<Genome*>& gs, bool already_sync
         int rcj = join_lanes(c);
         if (rcj) return rcj;
     }
-    const u32 nb = 1u << c->g.b;
     std::vector<u32> novf(todo.size()), total(todo.size());
     if (!already_synced) {
         for (size_t i0 = 0; i0 < todo.size(); i0 += PUB_CAP) {
@@ -1897,56 +2014,8 @@ static int finalize(kr_ctx* c, const std::vector<Genome*>& gs, bool already_sync
         S.count = total[i];
         if (novf[i]) {
             if (repaired) *repaired = true;
-            StageScope sc(c, KR_ST_FALLBACK);
-            const u32 nb = 1u << c->g.b;
-            std::vector<uint4> segs;
-            uint4* dsegs = (uint4*)((char*)S.ovf.p + 16);
-            if (novf[i] > OVF_MAX) {
-                segs.push_back(make_uint4(0, total[i], 0, nb));      // everything: bucket range [0, nb)
-            } else {
-                segs.resize(novf[i]);
-                HIPCHK(c, hipMemcpy(segs.data(), dsegs, (size_t)novf[i] * 16, hipMemcpyDeviceToHost));
-                for (auto& sg : segs) sg.w = sg.z + 1;               // bucket range [f, f + 1)
-            }
-            c->overflow_segments += (int64_t)segs.size();
-            // (1) sort the 4096-key tiles of every segment with the LDS sorter
-            std::vector<uint4> tiles;
-            u32 maxlen = 0;
-            for (auto& sg : segs) {
-                maxlen = std::max(maxlen, sg.y - sg.x);
-                for (u32 t = sg.x; t < sg.y; t += LS_CAP) tiles.push_back(make_uint4(t, std::min(t + LS_CAP, sg.y), sg.z, sg.w));
-            }
-            int rc;
-            if ((rc = ensure(c, c->fbdesc, tiles.size() * 16 + 16))) return rc;
-            if ((rc = ensure(c, c->fbsegs, (segs.size() + 1) * 16))) return rc;
-            HIPCHK(c, hipMemcpy(c->fbdesc.p, tiles.data(), tiles.size() * 16, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemsetAsync(S.ovf.p, 0, 16, st));
-            hipLaunchKernelGGL(k_localsort2, dim3(std::min<u32>((u32)tiles.size(), (u32)c->ls_grid)), dim3(LS_THREADS), 0,
-                               st, (u64*)S.keys.p, (const u32*)S.off.p, (const uint4*)c->fbdesc.p, (u32)tiles.size(),
-                               c->g.b, (u32*)S.ovf.p, dsegs);
-            c->fallback_launches++;
-            // (2) merge rounds: runs of `run` keys -> 2 * run, through the lane scratch and back
-            Lane& ln = c->lanes[0];
-            if ((rc = ensure(c, ln.tmpkeys, ((size_t)total[i] + 2) * 8))) return rc;
-            for (u64 run = LS_CAP; run < maxlen; run *= 2) {
-                std::vector<uint4> act;
-                u32 ntiles = 0;
-                for (auto& sg : segs) {
-                    u32 len = sg.y - sg.x;
-                    if (len <= run) continue;
-                    act.push_back(make_uint4(sg.x, sg.y, ntiles, 0));
-                    ntiles += (len + MG_TILE - 1) / MG_TILE;
-                }
-                if (act.empty()) break;
-                HIPCHK(c, hipMemcpy(c->fbsegs.p, act.data(), act.size() * 16, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(k_seg_merge, dim3(ntiles), dim3(MG_T), 0, st, (const u64*)S.keys.p,
-                                   (u64*)ln.tmpkeys.p, (const uint4*)c->fbsegs.p, (u32)act.size(), (u32)run);
-                hipLaunchKernelGGL(k_seg_copy, dim3(ntiles), dim3(256), 0, st, (const u64*)ln.tmpkeys.p,
-                                   (u64*)S.keys.p, (const uint4*)c->fbsegs.p, (u32)act.size());
-                HIPCHK(c, hipStreamSynchronize(st));      // fbsegs is rewritten next round
-                c->fallback_launches += 2;
-            }
-            HIPCHK(c, hipGetLastError());
+            int rc = repair_slice(c, S, novf[i], total[i], st);
+            if (rc) return rc;
         }
     }
     for (Genome* G : tg) {
@@ -1967,10 +2036,7 @@ int64_t kr_genome_load_sorted(kr_ctx* c, int id, const uint64_t* keys, size_t n)
     G.n_bases = 0;
     G.nwords = 0;
     G.nmax = n;
-    for (Slice& S : G.sl) {
-        release(c, S.keys); release(c, S.off); release(c, S.chunkstart); release(c, S.chunkdesc); release(c, S.ovf);
-        if (S.res >= 0) c->mb_free.push_back(S.res);
-    }
+    for (Slice& S : G.sl) release_slice(c, S);         // (whatever their number: the arrays are sized anew below)
     G.sl.assign(c->nslices, Slice());
     const u32 nb = 1u << c->g.b;
     const int sbits = c->g.sbits;
@@ -2091,9 +2157,7 @@ int64_t kr_genome_keys_in_order(kr_ctx* c, int id, uint64_t* out, size_t cap) {
         release(c, tsum); release(c, tpos);
         return rc;
     }
-    Geom g = c->g;
-    g.sbits = 0;
-    g.slice = 0;
+    const Geom g = pass0_geom(c);
     hipLaunchKernelGGL(k_order_count, dim3(ntiles), dim3(256), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p, npos, g,
                        (u32*)tsum.p);
     hipLaunchKernelGGL(k_scan64, dim3(1), dim3(1024), 0, st, (const u32*)tsum.p, (u64*)tpos.p, ntiles);
