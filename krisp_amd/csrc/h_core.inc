@@ -167,6 +167,7 @@ struct kr_ctx {
     u32 scan_cap = 0;           // KR_SCAN_GRID env (tests: a few workgroups walk many tiles of a scan; 0 = scan_grid()'s occupancy x the CUs)
     int64_t scan_dbg[3] = {0, 0, 0};      // kr_debug_scan: tiles and grid of the latest scan_grid(), blocks of the latest scan_two_pass
     int slice_route = 1;        // KR_SLICE_ROUTE env (A/B, tests): 0 = every slice counts its keys again before its pass 1 (k_hist8k / k_scatter1kp)
+    typedef std::vector<DevBuf*> Bufs;      // bufs(): a state's device buffers, named there alone (kr_destroy releases them)
     // wide windows (kr_set_params_wide / kr_wide_run)
     struct Wide {
         bool on = false;
@@ -180,6 +181,7 @@ struct kr_ctx {
             u32 n = 0, mznb = 0;
             bool canon = false;         // Dict.canon: n canonical keys stand for nfull flanks (their reverse complements included)
             u32 nfull = 0;
+            void bufs(Bufs& v) { v.insert(v.end(), {&keys, &idx, &slots, &mzT, &mzB}); }
             Dict view() const {
                 Dict d{};
                 d.keys = (const u64*)keys.p;
@@ -232,10 +234,18 @@ struct kr_ctx {
         u32 nfin = 0;
         u64 ngroups = 0;                // (left,right) groups present in all genomes (= nfin unless the list is canonical)
         int64_t nhits = -1;
+        // what the locate, count and emit passes of a run allocate: the first to go when memory is short (wide_make_room)
+        void locate_bufs(Bufs& v) { v.insert(v.end(), {&masks, &keep, &cnt, &hitoff, &cursor, &hits, &cibuf, &loc}); }
+        void bufs(Bufs& v) {
+            fin.bufs(v);
+            locate_bufs(v);
+            v.insert(v.end(), {&loccur, &tsum, &tpos, &wcount, &flbuf, &rows, &rowtab});
+            for (auto& flank : fd)
+                for (DictBufs& d : flank) d.bufs(v);
+        }
     } wide;
     // the one-genome scans (h_scan.inc), all in the locate context.  bufs(): a pass's device buffers, named here alone
     // (kr_destroy releases them); reset(): what another geometry leaves of a pass (kr_set_params_locate: no table, no result)
-    typedef std::vector<DevBuf*> Bufs;
     // the seed table of a seed pass on the device (seed_table_build): the entries' text, the slots, the entry list, the
     // membership bitmap; slots = 0: no table
     struct SeedTable {
@@ -500,6 +510,12 @@ static void release_slice(kr_ctx* c, Slice& S) {
     release(c, S.ovf);
     if (S.res >= 0) c->mb_free.push_back(S.res);
 }
+// a genome's sorted keys go back (its slice plan with them: kr_wide_run makes one per phase)
+static void genome_drop_sorted(kr_ctx* c, Genome& G) {
+    for (Slice& S : G.sl) release_slice(c, S);
+    G.sl.clear();
+    G.sorted = G.finalized = G.ordered = false;
+}
 // a genome whose slices were planned for another slice count starts over with the context's
 static void reset_slices(kr_ctx* c, Genome& G) {
     if ((int)G.sl.size() == c->nslices) return;
@@ -618,6 +634,15 @@ static int ensure_h16exc(kr_ctx* c, Lane& ln, hipStream_t st) {
     return KR_OK;
 }
 
+// the exclusive scan of n counts, tiled: sums of tiles of 2048 into tsum, their scan into tpos (a word per tile and
+// four more each), the positions into out -- out[n] is the total; out may be `in`
+static void launch_excl_scan(hipStream_t st, const u32* in, u32 n, u32* tsum, u32* tpos, u32* out) {
+    const u32 ntiles = (n + 2047) / 2048;
+    hipLaunchKernelGGL(k_tile_sums, dim3(ntiles), dim3(256), 0, st, in, n, tsum);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)tsum, tpos, ntiles);
+    hipLaunchKernelGGL(k_tile_apply, dim3(ntiles), dim3(256), 0, st, in, n, (const u32*)tpos, ntiles, out);
+}
+
 extern "C" {
 
 const char* kr_last_error(kr_ctx* c) { return c ? c->err.c_str() : g_last_error.c_str(); }
@@ -730,18 +755,8 @@ void kr_destroy(kr_ctx* c) {
                      &c->tx_tsum, &c->tx_tpos, &c->candP, &c->touchdesc, &c->touchovf, &c->co_state, &c->co_tab};
     for (DevBuf* b : all) release(c, *b);
     {
-        auto& w = c->wide;
-        DevBuf* wb[] = {&w.fin.keys, &w.fin.idx, &w.fin.slots, &w.masks, &w.keep, &w.cnt, &w.hitoff, &w.cursor, &w.hits,
-                        &w.cibuf, &w.loc, &w.loccur, &w.tsum, &w.tpos, &w.wcount, &w.flbuf, &w.rows, &w.rowtab};
-        for (DevBuf* b : wb) release(c, *b);
-        for (int f = 0; f < 2; f++)
-            for (int q = 0; q < 2 * FR_MAXP - 1; q++) {
-                auto& d = w.fd[f][q];
-                release(c, d.keys); release(c, d.idx); release(c, d.slots); release(c, d.mzT); release(c, d.mzB);
-            }
-    }
-    {
-        kr_ctx::Bufs sb;                // the one-genome scans': every pass hands over its own
+        kr_ctx::Bufs sb;                // the wide path's and the one-genome scans': every pass hands over its own
+        c->wide.bufs(sb);
         c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb);
         for (DevBuf* b : sb) release(c, *b);
         auto& ds = c->design;
@@ -774,7 +789,7 @@ static Geom slice_geom(const kr_ctx* c, u32 slice) {
 }
 
 // absolute + relative geometry of (L, D, R) windows sorted in 4^sb slices with fan-out 2^b
-#define KR_RETRY_DENSE (-1000)       // internal (count_slices -> wide_phase): a key-list segment was too short, take the dense form
+#define KR_RETRY_DENSE (-1000)       // internal (count_slices -> phase_sort_intersect): a key-list segment was too short, take the dense form
 static Geom make_geom(int L, int D, int R, int omit, int sb, int b) {
     Geom g{};
     const int k = L + D + R;
@@ -1364,7 +1379,7 @@ static int count_slices(kr_ctx* c, Genome& G) {
     if (g0.wcmode == 3) {
         u64 listed = 0;
         for (u32 v : seglen) {
-            if (v > g0.wlcap) return KR_RETRY_DENSE;      // (a segment too short for its workgroup's keys: wide_phase takes the dense form)
+            if (v > g0.wlcap) return KR_RETRY_DENSE;      // (a segment too short for its workgroup's keys: phase_sort_intersect takes the dense form)
             listed += v;
         }
         c->wide.keys_listed += listed;

@@ -187,10 +187,7 @@ static int64_t upload_text_impl(kr_ctx* c, int id, const uint8_t* text, size_t n
         const uint8_t* dt = (const uint8_t*)c->tx_text.p;
         hipLaunchKernelGGL(k_tx_firstline, dim3(1), dim3(1024), 0, st, dt, nt, universal_newlines, ts);
         hipLaunchKernelGGL(k_tx_starts_count, dim3(ntiles), dim3(256), 0, st, dt, nt, universal_newlines, (u32*)c->tx_tile.p);
-        hipLaunchKernelGGL(k_tile_sums, dim3(nt2), dim3(256), 0, st, (const u32*)c->tx_tile.p, ntiles, (u32*)c->tx_tsum.p);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const u32*)c->tx_tsum.p, (u32*)c->tx_tpos.p, nt2);
-        hipLaunchKernelGGL(k_tile_apply, dim3(nt2), dim3(256), 0, st, (const u32*)c->tx_tile.p, ntiles, (const u32*)c->tx_tpos.p,
-                           nt2, (u32*)c->tx_tilepos.p);
+        launch_excl_scan(st, (const u32*)c->tx_tile.p, ntiles, (u32*)c->tx_tsum.p, (u32*)c->tx_tpos.p, (u32*)c->tx_tilepos.p);
         hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, (const u32*)c->tx_tilepos.p + ntiles, (const u32*)nullptr,
                            (const u32*)nullptr, (u32*)mb);
         HIPCHK(c, hipStreamSynchronize(st));
