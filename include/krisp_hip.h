@@ -553,6 +553,39 @@ int64_t kr_guide_bulges_fetch(kr_ctx*, kr_guide_bulge_hit* out, size_t cap);
  * the reverse complement for strand 1), then 0.  Returns the number of rows; rows == NULL: size query */
 int64_t kr_guide_bulges_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
 
+/* ---- guide hits inside the designed primers' products (krisp_fasta --out_assay_hits) -----------------------------------
+ * No seam in the reference.  An amplification-plus-Cas assay gives a signal where a region's primers amplify a product
+ * AND that region's guide binds between the two primer sites.  DESIGN §21 holds the definition; tests/assay_reference.py
+ * restates it.  A product P is a product of kr_primers_scan, a hit H a hit of kr_guide_hits_scan (after need_pam's
+ * selection), both of one genome in one locate context (kr_set_params_locate with L+D+R = the protospacer length G; the
+ * primer pass reads only the soft-mask mode).  P's interior is [P.pos + len(first), P.pos + P.length - len(second)), with
+ * first = the left text on strand 0 and the right text on strand 1: the bases between the two primer sites.  An assay hit
+ * is a (P, H) with interior.lo <= H.pos, H.pos + G <= interior.hi and (P.pair, H.guide) a link.  On the device it is
+ * csrc/k_assay.inc: a thread per product, a binary search into the position-ordered hit list, a walk over the hits of the
+ * interior, a binary search into the links; counted, scanned, written: no atomics, the same bytes on every run.
+ *
+ * kr_assay_table: n rows of two u32 (row of the primer table's `pairs`, row of the guide-hit table), strictly ascending
+ * as 64-bit keys (pair << 32 | guide).  KR_ERR_STATE without both tables; KR_ERR_PARAM for an index out of range, rows
+ * that are not ascending and unique, null links with n != 0.  kr_primers_table, kr_guide_hits_table and
+ * kr_set_params_locate drop it.  Returns n. */
+int64_t kr_assay_table(kr_ctx*, const uint32_t* links, uint64_t n);
+/* one assay hit, 48 bytes: the product's pos, length, pair, strand and four mismatch figures as kr_product_hit holds
+ * them, then the hit's hit_strand, hit_mismatches, hit_pam, hit_pos, columns, guide as kr_guide_hit holds them; hit = the
+ * hit's index in the list of kr_guide_hits_fetch / row of kr_guide_hits_windows */
+typedef struct { uint64_t pos; uint32_t length, pair; uint8_t strand, left_mm, right_mm, left_end_mm, right_end_mm, hit_strand,
+                 hit_mismatches, hit_pam; uint64_t hit_pos; uint64_t columns; uint32_t guide, hit; } kr_assay_hit;
+/* joins the products of the latest kr_primers_scan with the hits of the latest kr_guide_hits_scan.  KR_ERR_STATE without
+ * a link table, unless both scans were of genome `id`, or when either table changed since its scan.  Returns the number
+ * of assay hits, kept on the device; no products, no hits or no links: 0 without a launch.  Neither list is written: the
+ * fetches, sites and windows of both passes give the same bytes after it as before it.  A thread walks the hits of its
+ * product's interior alone: the cost is products x hits in range (limits).  KR_ERR_CAPACITY for 2^32 assay
+ * hits or more, or a list that does not fit. */
+int64_t kr_assay_join(kr_ctx*, int id);
+/* the assay hits of the latest join in (pos, length, strand, pair, hit_pos, hit_strand, guide) order: the device lists
+ * them by product as it lists the products, a product's by hit as it lists the hits; the rows of one product position
+ * are ordered here.  Returns their number; out == NULL: the number only.  KR_ERR_STATE before a join */
+int64_t kr_assay_fetch(kr_ctx*, kr_assay_hit* out, size_t cap);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

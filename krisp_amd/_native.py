@@ -35,6 +35,9 @@ GUIDE_RECORD = np.dtype([("found", "<u4"), ("strand", "<u4"), ("start", "<u4"), 
                          ("sum_mismatches", "<u4"), ("gc", "<u4"), ("candidates", "<u4"), ("pad", "<u4")])    # kr_guide_record
 GUIDE_HIT_RAW = np.dtype([("guide", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("pam", "u1"), ("pad", "u1"), ("pos", "<u8"),
                           ("columns", "<u8")])                                 # kr_guide_hit
+ASSAY_HIT_RAW = np.dtype([("pos", "<u8"), ("length", "<u4"), ("pair", "<u4"), ("strand", "u1"), ("left_mm", "u1"), ("right_mm", "u1"),
+                          ("left_end_mm", "u1"), ("right_end_mm", "u1"), ("hit_strand", "u1"), ("hit_mismatches", "u1"),
+                          ("hit_pam", "u1"), ("hit_pos", "<u8"), ("columns", "<u8"), ("guide", "<u4"), ("hit", "<u4")])   # kr_assay_hit
 GUIDE_BULGE_HIT_RAW = np.dtype([("guide", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("pam", "u1"), ("bulge", "i1"),
                                 ("pos", "<u8"), ("columns", "<u8"), ("bulge_column", "<u4"), ("length", "<u4")])   # kr_guide_bulge_hit
 WIDE_DICT_LEFT, WIDE_DICT_RIGHT, WIDE_GROUPS, WIDE_HITS, WIDE_COUNTS, WIDE_SLOT_BITS, WIDE_NGROUPS, WIDE_BATCH_USED, WIDE_LOCATED, WIDE_KEYS_LISTED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -144,6 +147,9 @@ SYMBOLS = [
     ("kr_guide_bulges_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_guide_bulges_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_bulges_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_assay_table", _c.c_int64, [_P, _P, _c.c_uint64]),
+    ("kr_assay_join", _c.c_int64, [_P, _c.c_int]),
+    ("kr_assay_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_render_windows", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("kr_fasta_to_bases", _c.c_int64, [_P, _c.c_size_t, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
@@ -863,6 +869,36 @@ class Engine:
         out = np.empty(max(n, 1), dtype=PRODUCT_SITE)
         if n:
             self._check(self.lib.kr_primers_sites(self.ctx, _ptr(out), n), "kr_primers_sites")
+        return out[:n]
+
+    def primers_scan(self, gid):
+        """scans uploaded genome gid against the primer table and leaves the products on the device -> their number
+        (kr_primers_scan)"""
+        return self._check(self.lib.kr_primers_scan(self.ctx, gid), "kr_primers_scan")
+
+    def guide_hits_scan(self, gid):
+        """scans uploaded genome gid against the guides' table and leaves the hits on the device -> their number
+        (kr_guide_hits_scan)"""
+        return self._check(self.lib.kr_guide_hits_scan(self.ctx, gid), "kr_guide_hits_scan")
+
+    def assay_table(self, links):
+        """links: [n, 2] rows of (row of primers_table's pairs, row of guide_hits_table's texts), strictly ascending; both
+        tables stand in this context -> n (kr_assay_table)"""
+        lk = np.ascontiguousarray(links, dtype=np.uint32).reshape(-1, 2)
+        return self._check(self.lib.kr_assay_table(self.ctx, _ptr(lk) if lk.size else None, len(lk)), "kr_assay_table")
+
+    def assay_join(self, gid):
+        """joins the products of the latest primers scan with the hits of the latest guide-hit scan, both of genome gid, on
+        the device -> the number of assay hits (kr_assay_join)"""
+        return self._check(self.lib.kr_assay_join(self.ctx, gid), "kr_assay_join")
+
+    def assay_hits(self):
+        """ASSAY_HIT_RAW array of the latest assay_join() in (pos, length, strand, pair, hit_pos, hit_strand, guide) order
+        (kr_assay_fetch)"""
+        n = self._check(self.lib.kr_assay_fetch(self.ctx, None, 0), "kr_assay_fetch")
+        out = np.empty(max(n, 1), dtype=ASSAY_HIT_RAW)
+        if n:
+            self._check(self.lib.kr_assay_fetch(self.ctx, _ptr(out), n), "kr_assay_fetch")
         return out[:n]
 
     def design_table(self, params):

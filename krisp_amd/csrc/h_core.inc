@@ -325,9 +325,20 @@ struct kr_ctx {
     // mixed lengths, smin .. maxlen, entry e's text at eoff[e]
     struct Prim : Prod {
         u32 smin = 0, maxlen = 0;
-        DevBuf eoff;
-        void bufs(Bufs& v) { Prod::bufs(v); v.push_back(&eoff); }
+        int gid = -1;                   // the genome of the latest kr_primers_scan
+        DevBuf eoff, plen;              // plen: pair p's two text lengths (left | right << 16), what the assay join reads
+        void bufs(Bufs& v) { Prod::bufs(v); v.insert(v.end(), {&eoff, &plen}); }
     } prim;
+    // the assay join (kr_assay_*: h_assay.inc), in the same context: the links (primer pair << 32 | guide, ascending) and the
+    // assay hits of the latest join of prim's products with ghit's hits.  on: a link table stands (it may be empty)
+    struct Assay {
+        bool on = false;
+        u64 nlinks = 0;
+        int64_t nhits = -1;
+        DevBuf links, hits;
+        void bufs(Bufs& v) { v.insert(v.end(), {&links, &hits}); }
+        void reset() { on = false; nlinks = 0; nhits = -1; }
+    } assay;
     // the primer design pass (kr_design_*: h_design.inc): no genome, no geometry of another pass
     struct Design {
         bool on = false;
@@ -757,7 +768,7 @@ void kr_destroy(kr_ctx* c) {
     {
         kr_ctx::Bufs sb;                // the wide path's and the one-genome scans': every pass hands over its own
         c->wide.bufs(sb);
-        c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb);
+        c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb); c->assay.bufs(sb);
         for (DevBuf* b : sb) release(c, *b);
         auto& ds = c->design;
         DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec, &ds.hprec};

@@ -75,6 +75,7 @@ int64_t kr_guide_hits_table(kr_ctx* c, const uint8_t* texts, uint64_t nguides, i
     }
     gh.seed.slots = 0;                              // (from here on the device's copy of an earlier table is written over)
     gh.nhits = -1;
+    c->assay.reset();                               // (its links name this table's guides)
     const int64_t slots = seed_table_build(c, keyed, text, gh.seed, "kr_guide_hits_table", nguides, "guides");
     if (slots < 0) return slots;
     gh.M = M;
@@ -134,6 +135,7 @@ int64_t kr_guide_hits_scan(kr_ctx* c, int id) {
     auto& gh = c->ghit;
     gh.nhits = 0;
     gh.gid = id;
+    c->assay.nhits = -1;                            // (a join of the earlier list is no join of this one)
     u64 nw;
     const u64 ntiles = scan_tiles(G.n_bases, (u64)l.k, &nw);
     if (!ntiles || !gh.nguides) return 0;

@@ -26,6 +26,7 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
     const u64 nt = nleft + nright;
     pm.seed.slots = 0;
     pm.nsites = pm.nhits = -1;
+    c->assay.reset();                               // (its links name this table's pairs)
     if (M < 0 || M >= NEAR_MAXP)
         return fail(c, KR_ERR_PARAM, "kr_primers_table: 0 <= mismatches <= %d (got %d)", NEAR_MAXP - 1, M);
     if ((nt && (!text || !offsets)) || (!pairs && npairs)) return fail(c, KR_ERR_PARAM, "kr_primers_table: null table");
@@ -49,7 +50,7 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
     const u32 NP = (u32)M + 1;
     const u64 ne = 2 * nt;
     std::vector<uint8_t> arena;
-    std::vector<u32> eoff, pidx;
+    std::vector<u32> eoff, pidx, plen;
     SeedKeys keyed;
     std::vector<u64> pkeys;
     try {
@@ -68,8 +69,10 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
         // every entry under the NP pieces of the first smin columns of its text as it reads on the forward strand
         keyed.reserve(ne * NP);
         for (u64 e = 0; e < ne; e++) seed_keys(keyed, arena.data() + eoff[e], pg.off, NP, 0, (u32)e);
+        plen.assign(npairs + 1, 0u);
         rc = pair_list_sort(c, "kr_primers_table", pairs, npairs, nleft, nright, pkeys, pidx, [&](u64 p, u32 li, u32 rj) {
             const u32 n1 = offsets[li + 1] - offsets[li], n2 = offsets[nleft + rj + 1] - offsets[nleft + rj];
+            plen[p] = n1 | (n2 << 16);
             if ((u64)max_product < (u64)n1 + n2)
                 return fail(c, KR_ERR_PARAM, "kr_primers_table: max_product %u is shorter than the two texts of pair %llu (%u + %u)",
                             max_product, (unsigned long long)p, n1, n2);
@@ -81,10 +84,11 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
     }
     const int64_t slots = seed_table_build(c, keyed, arena, pm.seed, "kr_primers_table", nt, "texts");
     if (slots < 0) return slots;
-    if ((rc = ensure(c, pm.eoff, eoff.size() * 4)))
+    if ((rc = ensure(c, pm.eoff, eoff.size() * 4)) || (rc = ensure(c, pm.plen, plen.size() * 4)))
         return fail(c, rc, "kr_primers_table: the table of %llu texts does not fit the device (%s)", (unsigned long long)nt, c->err.c_str());
     if ((rc = pair_list_upload(c, pm.plist, pkeys, pidx, "kr_primers_table", nt))) return rc;
     HIPCHK(c, hipMemcpy(pm.eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(pm.plen.p, plen.data(), plen.size() * 4, hipMemcpyHostToDevice));
     pm.seed.slots = (u64)slots;
     return slots;
 }
@@ -103,6 +107,8 @@ int64_t kr_primers_scan(kr_ctx* c, int id) {
     int rc;
     if ((rc = scan_genome(c, id, c && c->prim.seed.slots, "kr_primers_table first", &Gp))) return rc;
     const Genome& G = *Gp;
+    c->prim.gid = id;
+    c->assay.nhits = -1;                            // (a join of the earlier list is no join of this one)
     PrimGeom pg;
     prim_geom(c, &pg);
     auto sites = [&](u64 nw, u64 ntiles, u64* ns) {

@@ -52,6 +52,7 @@
 
 #include "k_products.inc"    // the product pass: sites of the flanks within M substitutions, joined into PCR products
 #include "k_primers.inc"     // the primer-product pass: sites of primer texts of mixed lengths, joined into PCR products
+#include "k_assay.inc"       // the assay join: the guide hits inside the primer products' interiors, a thread per product
 #include "k_design.inc"      // the primer design pass: a wavefront per region, integer thermodynamics, the best pair
 #include "k_coarse.inc"      // a genome that stopped behind pass 1 against a short candidate list: LDS table per top byte, hit list
 #include "k_guides.inc"      // the guide pass: a wavefront per region, the window next to a PAM that differs most from the outgroup rows
@@ -66,6 +67,7 @@
 #include "h_guide_bulges.inc" // kr_guide_bulges_*: the windows of a genome within M substitutions and one bulge of a picked guide
 #include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome; the scan, join, fetch and sites of both product passes
 #include "h_primers.inc"     // kr_primers_*: in-silico PCR of designed primer pairs against a genome
+#include "h_assay.inc"       // kr_assay_*: the link table, the join of the two lists on the device, its rows
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options
 #include "h_guides.inc"      // kr_guides_*: a CRISPR guide per region from its template, its outgroup rows and the guide options
 #include "h_pgzip.inc"       // one gzip member inflated on several threads (host only)

@@ -2046,6 +2046,156 @@ def write_guide_bulge_hits(path, rows, bulged, files):
 # ----------------------------------------------------------------------------
 # stage functions (reference signatures)
 # ----------------------------------------------------------------------------
+# ----------------------------------------------------------------------------
+# the guide hits inside the designed primers' products (--out_assay_hits)
+# ----------------------------------------------------------------------------
+ASSAY_HIT_HEADER = ("region\tfile\trecord\trecord_index\tproduct_start\tproduct_end\tproduct_strand\tlength\tleft_mismatches\t"
+                    "right_mismatches\tleft_end_mismatches\tright_end_mismatches\tguide_start\tguide_end\tguide_strand\t"
+                    "guide_mismatches\tmismatch_columns\tpam5_match\tpam3_match\torientation\tsequence")
+# (start, end, strand: the product's -- the names _fill_shared writes)
+ASSAY_HIT = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"), ("end", "<i8"),
+                      ("strand", "U1"), ("length", "<u4"), ("left_mismatches", "<u4"), ("right_mismatches", "<u4"),
+                      ("left_end_mismatches", "<u4"), ("right_end_mismatches", "<u4"), ("guide_start", "<i8"), ("guide_end", "<i8"),
+                      ("guide_strand", "U1"), ("guide_mismatches", "<u4"), ("mismatch_columns", "O"), ("pam5_match", "<u4"),
+                      ("pam3_match", "<u4"), ("orientation", "O"), ("sequence", "O")])
+
+
+def assay_links(pairs_regions, text_regions):
+    """The links of the assay join: pairs_regions[p] = the regions of primer pair p (primer_pairs), text_regions[t] = the
+    regions of guide text t (guide_texts), both in one numbering.  A link is a (p, t) that some region has both of; a
+    region with a pair and no guide, or a guide and no pair, makes none.  -> (the links as uint32 [n, 2], strictly
+    ascending, the regions of link i as a list of ascending lists)"""
+    pair_of = {int(r): p for p, rs in enumerate(pairs_regions) for r in rs}
+    by_link = {}
+    for t, rs in enumerate(text_regions):
+        for r in rs:
+            if int(r) in pair_of:
+                by_link.setdefault((pair_of[int(r)], t), []).append(int(r))
+    keys = sorted(by_link)
+    return np.array(keys, dtype=np.uint32).reshape(-1, 2), [sorted(by_link[k]) for k in keys]
+
+
+def assay_orientation(s_d, s_p, s_h):
+    """'design' when a hit on strand s_h of a product on strand s_p lies on the strand of the product that the design put
+    the guide on (s_d = the region's guide strand in the --out_guides record), 'reverse' otherwise"""
+    return "design" if (int(s_h) ^ int(s_p)) == int(s_d) else "reverse"
+
+
+def assay_hits_refusal(design_primers, out_guides, amp_size, primer_mismatches, max_product, guide_size, guide_mismatches, pam5, pam3,
+                       need_pam):
+    """why --out_assay_hits does not run with these options and figures (one line), or None: it needs --design-primers and
+    --out_guides, and takes what primer_products_refusal and guide_hits_refusal take"""
+    if not design_primers:
+        return "--out_assay_hits needs --design-primers (the primer pairs whose products it looks into)"
+    if not out_guides:
+        return "--out_assay_hits needs --out_guides (the guides it looks for inside the products)"
+    why = primer_products_refusal(amp_size, primer_mismatches, max_product)
+    if why is None:
+        why = guide_hits_refusal(guide_size, guide_mismatches, pam5, pam3, need_pam)
+    return why
+
+
+def assay_hits(left, right, pairs, pairs_regions, texts, text_regions, region_strand, ingroup_files, outgroup_files, guide_size,
+               primer_mismatches=1, max_product=1000, guide_mismatches=2, pam5="", pam3="", need_pam=False, omit_soft=False,
+               device=0):
+    """Where the assay of a region gives a signal: every product of the region's primer pair, in every input
+    genome, that carries a window within `guide_mismatches` substitutions of the region's protospacer between its two
+    primer sites.  left, right, pairs, pairs_regions = primer_pairs(...); texts, text_regions = guide_texts(...) with the
+    regions numbered alike; region_strand[r] = the guide strand of region r in the --out_guides record.  One pass over the
+    inputs on one device: the primer table, the guide-hit table and the links stand in ONE locate context, every file is
+    uploaded once, scanned by both passes (kr_primers_scan, kr_guide_hits_scan) and their lists are joined by position on
+    the device (kr_assay_join); only the assay hits and the windows' text come back.  A product is exactly a product of
+    primer_products, a hit exactly a hit of guide_hits (need_pam's selection included; bulged hits take no part).  Returns
+    an ASSAY_HIT array: start / end / strand / length and the four mismatch figures are the product's, guide_* and
+    mismatch_columns, pam5_match, pam3_match, sequence the hit's, orientation = assay_orientation.  An assay hit of a link
+    that several regions share is a row for each.  Rows in (region, file in command-line order, record_index, start, end,
+    '+' before '-' for the product, guide_start, '+' before '-' for the guide) order.  ValueError for figures the passes
+    do not take."""
+    why = primer_products_refusal(None, primer_mismatches, max_product)
+    if why is None:
+        why = guide_hits_refusal(guide_size, guide_mismatches, pam5, pam3, need_pam)
+    if why is None and len(texts) != len(text_regions):
+        why = f"assay_hits: {len(texts)} texts, the regions of {len(text_regions)}"
+    if why is None and len(pairs) != len(pairs_regions):
+        why = f"assay_hits: {len(pairs)} pairs, the regions of {len(pairs_regions)}"
+    G = guide_size
+    if why is None and any(len(t) != G for t in texts):
+        why = f"assay_hits: every text has --guide-size = {G} letters"
+    if why is not None:
+        raise ValueError(why)
+    pairs = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    for i, j in pairs.tolist():
+        if max_product < len(left[i]) + len(right[j]):
+            raise ValueError(f"--max-product must be at least a pair's two primers together, {len(left[i]) + len(right[j])} "
+                             f"bases (got {max_product})")
+    links, link_regions = assay_links(pairs_regions, text_regions)
+    if len(links) == 0:
+        return np.empty(0, dtype=ASSAY_HIT)
+    files = list(ingroup_files) + list(outgroup_files)
+    t_bytes = np.frombuffer(b"".join(bytes(t) for t in texts), dtype=np.uint8).reshape(-1, G)
+    link_key = (links[:, 0].astype(np.int64) << 32) | links[:, 1]
+    # the regions of link i: reg[start[i] : start[i + 1]]
+    count = np.array([len(r) for r in link_regions], dtype=np.int64)
+    start = np.concatenate([[0], np.cumsum(count)])
+    reg = np.array([x for r in link_regions for x in r], dtype=np.uint32)
+    region_strand = np.asarray(region_strand, dtype=np.int64)
+
+    def table(eng):
+        eng.primers_table(list(left) + list(right), len(left), pairs, primer_mismatches, max_product)
+        eng.guide_hits_table(t_bytes, guide_mismatches, pam5, pam3, need_pam)
+        eng.assay_table(links)
+
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, 0, G, 0, G, omit_soft, device, table):
+        eng.primers_scan(0)
+        eng.guide_hits_scan(0)
+        if eng.assay_join(0) == 0:
+            continue
+        hits = eng.assay_hits()
+        text = _rows_text(eng.guide_hit_windows(G)[hits["hit"].astype(np.int64)], G, rna)
+        seps, ids = names()
+        # an assay hit of link i is a row for every region of i
+        li = np.searchsorted(link_key, (hits["pair"].astype(np.int64) << 32) | hits["guide"])
+        each = count[li]
+        rep = np.repeat(np.arange(len(hits)), each)
+        within = np.arange(len(rep)) - np.repeat(np.cumsum(each) - each, each)
+        h = hits[rep]
+        part = np.empty(len(h), dtype=ASSAY_HIT)
+        _fill_shared(part, path, seps, ids, h["pos"].astype(np.int64), h["strand"])
+        part["region"] = reg[start[li[rep]] + within]
+        part["length"] = h["length"]
+        part["end"] = part["start"] + part["length"]
+        part["left_mismatches"] = h["left_mm"]
+        part["right_mismatches"] = h["right_mm"]
+        part["left_end_mismatches"] = h["left_end_mm"]
+        part["right_end_mismatches"] = h["right_end_mm"]
+        # (the window lies inside the product: on its record)
+        part["guide_start"] = part["start"] + (h["hit_pos"].astype(np.int64) - h["pos"].astype(np.int64))
+        part["guide_end"] = part["guide_start"] + G
+        part["guide_strand"] = np.where(h["hit_strand"] == 0, "+", "-")
+        part["guide_mismatches"] = h["hit_mismatches"]
+        part["mismatch_columns"] = [_mask_columns(m) for m in h["columns"].tolist()]
+        part["pam5_match"] = h["hit_pam"] & 1
+        part["pam3_match"] = (h["hit_pam"] >> 1) & 1
+        design = (h["hit_strand"].astype(np.int64) ^ h["strand"]) == region_strand[part["region"].astype(np.int64)]
+        part["orientation"] = np.where(design, "design", "reverse").astype(object)
+        part["sequence"] = text[rep]
+        order = np.lexsort((part["guide_strand"] == "-", part["guide_start"], part["strand"] == "-", part["end"], part["start"],
+                            part["record_index"], part["region"]))
+        parts.append((fi, part[order], part["region"][order]))
+    return _sorted_parts(parts, ASSAY_HIT)
+
+
+def write_assay_hits(path, rows):
+    """the TSV of --out_assay_hits: ASSAY_HIT_HEADER, then a line per row"""
+    names = ("region", "file", "record", "record_index", "start", "end", "strand", "length", "left_mismatches", "right_mismatches",
+             "left_end_mismatches", "right_end_mismatches", "guide_start", "guide_end", "guide_strand", "guide_mismatches",
+             "mismatch_columns", "pam5_match", "pam3_match", "orientation", "sequence")
+    with open(path, "w") as f:
+        f.write(ASSAY_HIT_HEADER + "\n")
+        f.writelines("\t".join(str(v) for v in row) + "\n" for row in zip(*(rows[n].tolist() for n in names)))
+
+
 def _hit_windows(sel, text, k):
     """member windows of kr_wide_run hits of ONE genome as an (n, k) byte matrix: cut from the text
     the host holds, soft-mask mapped, reverse complemented for strand 1"""
@@ -2486,6 +2636,18 @@ def build_parser():
                         "--guide-hit-mismatches <= 2; one more pass over the inputs.  (default: 0, no bulges)")
     p.add_argument("--guide-hits-need-pam", action="store_true",
                    help="--out_guide_hits lists a window only where --pam5 and --pam3 lie beside it (needs one of the two)")
+    p.add_argument("--out_assay_hits", type=str, metavar="PATH",
+                   help="With --design-primers and --out_guides: also write where a region's assay would give a signal, in every\n"
+                        "genome, the outgroups included: every product of the region's primer pair (as --out_primer_products\n"
+                        "lists them: --primer-mismatches, --max-product) that carries a window within --guide-hit-mismatches\n"
+                        "substitutions of the region's protospacer (as --out_guide_hits lists them: --guide-hits-need-pam)\n"
+                        "wholly between its two primer sites.  A tab-separated file: region, file, record, record_index,\n"
+                        "product_start, product_end, product_strand, length, the four primer mismatch columns, guide_start,\n"
+                        "guide_end, guide_strand, guide_mismatches, mismatch_columns, pam5_match, pam3_match, orientation (design:\n"
+                        "the guide lies on the strand of the product the design put it on; reverse otherwise), sequence.  The\n"
+                        "designed locus of an ingroup genome is a row without mismatches; the rows to look at are the others.\n"
+                        "Both searches and their join run on the device over one read of every input.  Bulged hits\n"
+                        "(--guide-hit-bulges) take no part: the unbulged hits alone are joined.  (default: no join)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -2592,8 +2754,8 @@ def main(argv=None):
         print("ERROR: --out_primer_products needs --design-primers", file=sys.stderr)
         sys.exit(2)
     for opt, val in (("--primer-mismatches", args.primer_mismatches), ("--max-product", args.max_product)):
-        if val is not None and args.out_products is None and args.out_primer_products is None:
-            print(f"ERROR: {opt} needs --out_products or --out_primer_products", file=sys.stderr)
+        if val is not None and args.out_products is None and args.out_primer_products is None and args.out_assay_hits is None:
+            print(f"ERROR: {opt} needs --out_products or --out_primer_products or --out_assay_hits", file=sys.stderr)
             sys.exit(2)
     if args.out_primer_products is not None:
         if args.primer_mismatches is None:
@@ -2637,7 +2799,10 @@ def main(argv=None):
     for opt, val in (("--guide-hit-mismatches", args.guide_hit_mismatches), ("--guide-hits-need-pam", args.guide_hits_need_pam or None),
                      ("--guide-hit-bulges", args.guide_hit_bulges)):
         if val is not None and args.out_guide_hits is None:
-            print(f"ERROR: {opt} needs --out_guide_hits", file=sys.stderr)
+            if opt != "--guide-hit-bulges" and args.out_assay_hits is not None:
+                continue                 # (the assay join takes the two figures; bulged hits take no part in it)
+            print(f"ERROR: {opt} needs --out_guide_hits" + (" or --out_assay_hits" if opt != "--guide-hit-bulges" else ""),
+                  file=sys.stderr)
             sys.exit(2)
     if args.out_guide_hits is not None:
         if args.guide_hit_mismatches is None:
@@ -2646,6 +2811,19 @@ def main(argv=None):
             args.guide_hit_bulges = 0
         why = guide_hits_refusal(args.guide_size, args.guide_hit_mismatches, args.pam5, args.pam3, args.guide_hits_need_pam,
                                  bulges=args.guide_hit_bulges)
+        if why is not None:
+            print("ERROR: " + why, file=sys.stderr)
+            sys.exit(2)
+    if args.out_assay_hits is not None:
+        if args.primer_mismatches is None:
+            args.primer_mismatches = 1
+        if args.max_product is None:
+            args.max_product = 1000
+        if args.guide_hit_mismatches is None:
+            args.guide_hit_mismatches = 2
+        why = assay_hits_refusal(args.design_primers, args.out_guides is not None, args.amp_size, args.primer_mismatches,
+                                 args.max_product, args.guide_size, args.guide_hit_mismatches, args.pam5, args.pam3,
+                                 args.guide_hits_need_pam)
         if why is not None:
             print("ERROR: " + why, file=sys.stderr)
             sys.exit(2)
@@ -2782,6 +2960,22 @@ def main(argv=None):
                 bulged = guide_bulge_hits(texts, text_regions, args.files, args.outgroup, args.guide_size,
                                           bulges=args.guide_hit_bulges, **how)
                 write_guide_bulge_hits(args.out_guide_hits, rows, bulged, list(args.files) + list(args.outgroup))
+        if args.out_assay_hits is not None:
+            # (one genome at a time on one device, written by rank 0: both scans and their join over one read of each file)
+            if args.verbose:
+                print("Searching every genome for the guides' hits inside the designed primers' products ... ", file=sys.stderr)
+            left, right, pairs, pairs_regions = primer_pairs(templates[0], records)
+            texts, text_regions = guide_texts(templates[0], guides, args.guide_size, regions=regions)
+            # the guide strand of every region with a pair and a guide, under the region's number in both files
+            region_strand = np.full(int(found.sum()), -1, dtype=np.int64)
+            picked = found & (guides["found"] != 0)
+            region_strand[regions[picked]] = guides["strand"][picked]
+            write_assay_hits(args.out_assay_hits,
+                             assay_hits(left, right, pairs, pairs_regions, texts, text_regions, region_strand, args.files,
+                                        args.outgroup, args.guide_size, primer_mismatches=args.primer_mismatches,
+                                        max_product=args.max_product, guide_mismatches=args.guide_hit_mismatches, pam5=args.pam5,
+                                        pam3=args.pam3, need_pam=args.guide_hits_need_pam, omit_soft=args.omit_soft,
+                                        device=locate_device))
     if args.verbose:
         print(f"=> Found {len(groups):,} regions in {prettyTime(time.time() - t0)} "
               f"({stats['kmers']:,} k-mers, device {stats['device_s']:.3f} s)", file=sys.stderr)
