@@ -239,6 +239,11 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _motif_bytes(m):
+    """a PAM / PFS motif as the guide tables take it"""
+    return m if isinstance(m, bytes) else str(m).encode("ascii", "replace")
+
+
 def fasta_to_bases(data, universal_newlines, one_shot=True):
     """bytes of a FASTA / sequence file -> (uint8 upload buffer, records, special chars, rna, fasta)
     through the library's one-pass host parser (GIL released: callers may use threads)."""
@@ -445,6 +450,34 @@ class Engine:
             e.code = int(rc)
             raise e
         return rc
+
+    def _scan_fetch(self, scan, fetch, gid, dtype):
+        """scan(ctx, gid) -> the number of records n the scan left on the device, fetch(ctx, out, n) -> `dtype`[n]"""
+        n = self._check(getattr(self.lib, scan)(self.ctx, gid), scan)
+        out = np.empty(max(n, 1), dtype=dtype)
+        self._check(getattr(self.lib, fetch)(self.ctx, _ptr(out), n), fetch)
+        return out[:n]
+
+    def _sized_fetch(self, fn, dtype_or_width, *lead):
+        """a list whose length the library tells: fn(ctx, *lead, NULL, 0) -> the number of entries n, then
+        fn(ctx, *lead, out, size) fills them.  dtype_or_width: the entries' dtype (size = n) -> dtype[n], or the width
+        of text rows (size = the bytes) -> uint8 [n, width]"""
+        call = getattr(self.lib, fn)
+        n = self._check(call(self.ctx, *lead, None, 0), fn)
+        rows = isinstance(dtype_or_width, (int, np.integer))
+        out = np.empty((max(n, 1), dtype_or_width), dtype=np.uint8) if rows else np.empty(max(n, 1), dtype=dtype_or_width)
+        if n:
+            self._check(call(self.ctx, *lead, _ptr(out), out.nbytes if rows else n), fn)
+        return out[:n]
+
+    def _guide_texts(self, texts, who):
+        """texts -> uint8 [n, L+D+R] as the guide tables of method `who` read it; ValueError for another shape"""
+        t = np.ascontiguousarray(texts, dtype=np.uint8)
+        # (the library reads len(t) rows of L+D+R bytes: another shape would be read past its end)
+        k = sum(self.params) if self.params is not None else None
+        if t.size and (t.ndim != 2 or (k is not None and t.shape[1] != k)):
+            raise ValueError(f"{who}: texts is a matrix with a row of L+D+R = {k} letters per guide (got shape {t.shape})")
+        return t
 
     # ---- configuration
     def upload_text(self, gid, text, universal_newlines, one_shot=True):
@@ -700,10 +733,7 @@ class Engine:
 
     def wide_windows(self, k):
         """the member windows of the latest wide_run as text, cut on the device (kr_wide_fetch_windows): uint8 [nhits, k]"""
-        n = self._check(self.lib.kr_wide_fetch_windows(self.ctx, None, 0), "kr_wide_fetch_windows")
-        out = np.empty((max(n, 1), k), dtype=np.uint8)
-        self._check(self.lib.kr_wide_fetch_windows(self.ctx, _ptr(out), out.nbytes), "kr_wide_fetch_windows")
-        return out[:n]
+        return self._sized_fetch("kr_wide_fetch_windows", k)
 
     # ---- locations (krisp_fasta --out_locations)
     def set_params_locate(self, L, D, R, omit_soft=False, max_bases=0):
@@ -719,26 +749,15 @@ class Engine:
 
     def locate(self, gid):
         """LOC_HIT array of uploaded genome gid against the table: position order, strand 0 before 1 (kr_locate_scan)"""
-        n = self._check(self.lib.kr_locate_scan(self.ctx, gid), "kr_locate_scan")
-        out = np.empty(max(n, 1), dtype=LOC_HIT)
-        self._check(self.lib.kr_locate_fetch(self.ctx, _ptr(out), n), "kr_locate_fetch")
-        return out[:n]
+        return self._scan_fetch("kr_locate_scan", "kr_locate_fetch", gid, LOC_HIT)
 
     def locate_windows(self, k):
         """the latest locate()'s windows as text, cut on the device: uint8 [nhits, k] (kr_locate_windows)"""
-        n = self._check(self.lib.kr_locate_windows(self.ctx, None, 0), "kr_locate_windows")
-        out = np.empty((max(n, 1), k), dtype=np.uint8)
-        if n:
-            self._check(self.lib.kr_locate_windows(self.ctx, _ptr(out), out.nbytes), "kr_locate_windows")
-        return out[:n]
+        return self._sized_fetch("kr_locate_windows", k)
 
     def locate_seps(self, gid):
         """the positions of genome gid's record separators, ascending (kr_locate_seps)"""
-        n = self._check(self.lib.kr_locate_seps(self.ctx, gid, None, 0), "kr_locate_seps")
-        out = np.empty(max(n, 1), dtype=np.uint64)
-        if n:
-            self._check(self.lib.kr_locate_seps(self.ctx, gid, _ptr(out), n), "kr_locate_seps")
-        return out[:n]
+        return self._sized_fetch("kr_locate_seps", np.uint64, gid)
 
     def near_table(self, targets, mismatches):
         """targets: uint8 [n, L+D+R] (upper case, T for U), in a locate context -> slots of the seed table (kr_near_table)"""
@@ -747,75 +766,44 @@ class Engine:
 
     def near(self, gid):
         """NEAR_HIT array of uploaded genome gid against the seed table, in position order (kr_near_scan)"""
-        n = self._check(self.lib.kr_near_scan(self.ctx, gid), "kr_near_scan")
-        out = np.empty(max(n, 1), dtype=NEAR_HIT)
-        self._check(self.lib.kr_near_fetch(self.ctx, _ptr(out), n), "kr_near_fetch")
-        return out[:n]
+        return self._scan_fetch("kr_near_scan", "kr_near_fetch", gid, NEAR_HIT)
 
     def near_windows(self, k):
         """the latest near()'s windows as text, cut on the device: uint8 [nhits, k] (kr_near_windows)"""
-        n = self._check(self.lib.kr_near_windows(self.ctx, None, 0), "kr_near_windows")
-        out = np.empty((max(n, 1), k), dtype=np.uint8)
-        if n:
-            self._check(self.lib.kr_near_windows(self.ctx, _ptr(out), out.nbytes), "kr_near_windows")
-        return out[:n]
+        return self._sized_fetch("kr_near_windows", k)
 
     def guide_hits_table(self, texts, mismatches, pam5="", pam3="", need_pam=False):
         """texts: uint8 [n, G] protospacers in A, C, G, T, in a locate context with L+D+R = G; pam5 / pam3: the motifs in
         IUPAC letters, read 5'->3' on the guide's strand -> slots of the seed table (kr_guide_hits_table)"""
-        t = np.ascontiguousarray(texts, dtype=np.uint8)
-        # (the library reads len(t) rows of L+D+R bytes: another shape would be read past its end)
-        k = sum(self.params) if self.params is not None else None
-        if t.size and (t.ndim != 2 or (k is not None and t.shape[1] != k)):
-            raise ValueError(f"guide_hits_table: texts is a matrix with a row of L+D+R = {k} letters per guide (got shape {t.shape})")
-        as_bytes = lambda m: m if isinstance(m, bytes) else str(m).encode("ascii", "replace")      # noqa: E731
-        return self._check(self.lib.kr_guide_hits_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches, as_bytes(pam5),
-                                                        as_bytes(pam3), 1 if need_pam else 0), "kr_guide_hits_table")
+        t = self._guide_texts(texts, "guide_hits_table")
+        return self._check(self.lib.kr_guide_hits_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches, _motif_bytes(pam5),
+                                                        _motif_bytes(pam3), 1 if need_pam else 0), "kr_guide_hits_table")
 
     def guide_hits(self, gid):
         """GUIDE_HIT_RAW array of uploaded genome gid against the guides' table, in position order (kr_guide_hits_scan)"""
-        n = self._check(self.lib.kr_guide_hits_scan(self.ctx, gid), "kr_guide_hits_scan")
-        out = np.empty(max(n, 1), dtype=GUIDE_HIT_RAW)
-        self._check(self.lib.kr_guide_hits_fetch(self.ctx, _ptr(out), n), "kr_guide_hits_fetch")
-        return out[:n]
+        return self._scan_fetch("kr_guide_hits_scan", "kr_guide_hits_fetch", gid, GUIDE_HIT_RAW)
 
     def guide_hit_windows(self, G):
         """the latest guide_hits()'s windows as the guide's strand reads them, cut on the device: uint8 [nhits, G]
         (kr_guide_hits_windows)"""
-        n = self._check(self.lib.kr_guide_hits_windows(self.ctx, None, 0), "kr_guide_hits_windows")
-        out = np.empty((max(n, 1), G), dtype=np.uint8)
-        if n:
-            self._check(self.lib.kr_guide_hits_windows(self.ctx, _ptr(out), out.nbytes), "kr_guide_hits_windows")
-        return out[:n]
+        return self._sized_fetch("kr_guide_hits_windows", G)
 
     def guide_bulges_table(self, texts, mismatches, bulges, pam5="", pam3="", need_pam=False):
         """as guide_hits_table, for the bulged search with bulges of 1 .. `bulges` bases (1 or 2): the seed table of the
         guides' halves -> its slots (kr_guide_bulges_table).  A state of its own beside guide_hits_table's"""
-        t = np.ascontiguousarray(texts, dtype=np.uint8)
-        # (the library reads len(t) rows of L+D+R bytes: another shape would be read past its end)
-        k = sum(self.params) if self.params is not None else None
-        if t.size and (t.ndim != 2 or (k is not None and t.shape[1] != k)):
-            raise ValueError(f"guide_bulges_table: texts is a matrix with a row of L+D+R = {k} letters per guide (got shape {t.shape})")
-        as_bytes = lambda m: m if isinstance(m, bytes) else str(m).encode("ascii", "replace")      # noqa: E731
+        t = self._guide_texts(texts, "guide_bulges_table")
         return self._check(self.lib.kr_guide_bulges_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches, bulges,
-                                                          as_bytes(pam5), as_bytes(pam3), 1 if need_pam else 0), "kr_guide_bulges_table")
+                                                          _motif_bytes(pam5), _motif_bytes(pam3), 1 if need_pam else 0), "kr_guide_bulges_table")
 
     def guide_bulges(self, gid):
         """GUIDE_BULGE_HIT_RAW array of uploaded genome gid against the guides' table: the bulged hits, in the order of the
         seed pairs that own them (kr_guide_bulges_scan)"""
-        n = self._check(self.lib.kr_guide_bulges_scan(self.ctx, gid), "kr_guide_bulges_scan")
-        out = np.empty(max(n, 1), dtype=GUIDE_BULGE_HIT_RAW)
-        self._check(self.lib.kr_guide_bulges_fetch(self.ctx, _ptr(out), n), "kr_guide_bulges_fetch")
-        return out[:n]
+        return self._scan_fetch("kr_guide_bulges_scan", "kr_guide_bulges_fetch", gid, GUIDE_BULGE_HIT_RAW)
 
     def guide_bulge_windows(self, width):
         """the latest guide_bulges()'s windows as the guide's strand reads them, cut on the device: uint8 [nhits, width],
         width = G + bulges; row i holds hit i's `length` letters, then 0 (kr_guide_bulges_windows)"""
-        n = self._check(self.lib.kr_guide_bulges_windows(self.ctx, None, 0), "kr_guide_bulges_windows")
-        out = np.empty((max(n, 1), width), dtype=np.uint8)
-        if n:
-            self._check(self.lib.kr_guide_bulges_windows(self.ctx, _ptr(out), out.nbytes), "kr_guide_bulges_windows")
-        return out[:n]
+        return self._sized_fetch("kr_guide_bulges_windows", width)
 
     def products_table(self, left, right, pairs, mismatches, max_product):
         """left: uint8 [nl, L], right: uint8 [nr, R] (upper case, T for U), pairs: [np, 2] rows of (left, right), in a
@@ -829,18 +817,11 @@ class Engine:
 
     def products(self, gid):
         """PRODUCT_HIT array of uploaded genome gid in (pos, length, strand, pair) order (kr_products_scan)"""
-        n = self._check(self.lib.kr_products_scan(self.ctx, gid), "kr_products_scan")
-        out = np.empty(max(n, 1), dtype=PRODUCT_HIT)
-        self._check(self.lib.kr_products_fetch(self.ctx, _ptr(out), n), "kr_products_fetch")
-        return out[:n]
+        return self._scan_fetch("kr_products_scan", "kr_products_fetch", gid, PRODUCT_HIT)
 
     def product_sites(self):
         """the latest products()'s primer sites as the device lists them: PRODUCT_SITE, position order (kr_products_sites)"""
-        n = self._check(self.lib.kr_products_sites(self.ctx, None, 0), "kr_products_sites")
-        out = np.empty(max(n, 1), dtype=PRODUCT_SITE)
-        if n:
-            self._check(self.lib.kr_products_sites(self.ctx, _ptr(out), n), "kr_products_sites")
-        return out[:n]
+        return self._sized_fetch("kr_products_sites", PRODUCT_SITE)
 
     def primers_table(self, texts, nleft, pairs, mismatches, max_product):
         """texts: a list of bytes (upper case, T for U), each of its own length 10 .. 60, the first nleft of them left
@@ -857,19 +838,12 @@ class Engine:
 
     def primer_products(self, gid):
         """PRODUCT_HIT array of uploaded genome gid in (pos, length, strand, pair) order (kr_primers_scan)"""
-        n = self._check(self.lib.kr_primers_scan(self.ctx, gid), "kr_primers_scan")
-        out = np.empty(max(n, 1), dtype=PRODUCT_HIT)
-        self._check(self.lib.kr_primers_fetch(self.ctx, _ptr(out), n), "kr_primers_fetch")
-        return out[:n]
+        return self._scan_fetch("kr_primers_scan", "kr_primers_fetch", gid, PRODUCT_HIT)
 
     def primer_sites(self):
         """the latest primer_products()'s primer sites as the device lists them: PRODUCT_SITE, position order
         (kr_primers_sites)"""
-        n = self._check(self.lib.kr_primers_sites(self.ctx, None, 0), "kr_primers_sites")
-        out = np.empty(max(n, 1), dtype=PRODUCT_SITE)
-        if n:
-            self._check(self.lib.kr_primers_sites(self.ctx, _ptr(out), n), "kr_primers_sites")
-        return out[:n]
+        return self._sized_fetch("kr_primers_sites", PRODUCT_SITE)
 
     def primers_scan(self, gid):
         """scans uploaded genome gid against the primer table and leaves the products on the device -> their number
@@ -895,11 +869,7 @@ class Engine:
     def assay_hits(self):
         """ASSAY_HIT_RAW array of the latest assay_join() in (pos, length, strand, pair, hit_pos, hit_strand, guide) order
         (kr_assay_fetch)"""
-        n = self._check(self.lib.kr_assay_fetch(self.ctx, None, 0), "kr_assay_fetch")
-        out = np.empty(max(n, 1), dtype=ASSAY_HIT_RAW)
-        if n:
-            self._check(self.lib.kr_assay_fetch(self.ctx, _ptr(out), n), "kr_assay_fetch")
-        return out[:n]
+        return self._sized_fetch("kr_assay_fetch", ASSAY_HIT_RAW)
 
     def design_table(self, params):
         """params: thermo.Params, the model's integers and the primer options (kr_design_table)"""

@@ -24,6 +24,12 @@ def effective_geometry(L, D, R):
     return L, D, R
 
 
+def _is_wide(L, D, R):
+    """an effective geometry the packed path does not carry: an amplicon longer than one 64-bit key, or more diagnostic
+    bases than the device's mask format holds"""
+    return L + D + R > 32 or D > 16
+
+
 def keys_to_matrix(keys, L, D, R, rna=False):
     """keys (uint64, MSB aligned) -> uint8 matrix [n, k] of the string left|right|diag."""
     k = L + D + R

@@ -15,6 +15,7 @@ import bz2
 import gzip
 import os
 import time
+from pathlib import Path
 
 import numpy as np
 
@@ -25,6 +26,22 @@ _IUPAC = frozenset("RYMKSWBVDHrymkswbvdh")
 _PLAIN = np.zeros(256, dtype=bool)
 for _ch in b"ACGTNacgtn\n":
     _PLAIN[_ch] = True
+
+
+_FASTA_EXT = ("gz", "bz2", "fna", "fasta", "fa", "ffn", "frn")
+
+
+def basename(filename):
+    """shared.py:34-55: file name without fasta / compression endings."""
+    parts = Path(filename).name.split(".")
+    while parts[-1] in _FASTA_EXT:
+        parts.pop()
+    return ".".join(parts)
+
+
+def simplename(filename):
+    """shared.py:58-73: ... truncated at the first dot -- the genome's label."""
+    return basename(filename).split(".")[0]
 
 
 # white space as the reference's str.strip() sees it on its decoded (UTF-8) lines: ASCII 9-13, 28-31 and ' ', and the

@@ -1,0 +1,956 @@
+"""The report passes of `krisp_fasta`: what runs after the diagnostic regions are found, on one device, one genome at a
+time -- where the regions lie (--out_locations), their near matches (--out_near), the products of their flanks
+(--out_products), a primer pair per region and its products (--design-primers, --out_primer_products), a guide per
+region and its hits (--out_guides, --out_guide_hits, --guide-hit-bulges) and the guide hits inside the primers' products
+(--out_assay_hits) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
+command line and its callers reach the passes there."""
+import os
+
+import numpy as np
+
+from . import amplicon, codec, fasta
+from .codec import _is_wide
+from .fasta import simplename
+
+
+def _engine(device):
+    """a context under KRISP_HBM_BUDGET (bytes; tests and shared devices: kr_create's HBM budget)"""
+    from . import _native
+    return _native.Engine(device=device, hbm_budget=int(os.environ.get("KRISP_HBM_BUDGET", "0")))
+
+
+# ----------------------------------------------------------------------------
+# locations of the surviving groups' windows (--out_locations)
+# ----------------------------------------------------------------------------
+LOCATION_HEADER = "region\tfile\trecord\trecord_index\tstart\tend\tstrand\tsequence"
+LOCATION = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"),
+                     ("end", "<i8"), ("strand", "U1"), ("sequence", "O")])
+
+
+def _group_flanks(groups, L, R):
+    """the (left, right) flank text of every group, in the groups' order -> uint8 [groups, L + R], upper case, T for U.
+    RecordGroups and WindowGroups give theirs from the device's records / windows: no Amplicon is made."""
+    if isinstance(groups, amplicon.RecordGroups):
+        keys = groups.records["key"]
+        if len(keys) == 0:
+            return np.empty((0, L + R), dtype=np.uint8)
+        pre = keys & codec.prefix_mask(L, R)
+        first = np.flatnonzero(np.concatenate([[True], pre[1:] != pre[:-1]]))
+        return np.ascontiguousarray(codec.keys_to_matrix(keys[first], groups.L, groups.D, groups.R)[:, :L + R])
+    if isinstance(groups, amplicon.WindowGroups):
+        rows = groups.rows
+        if len(rows) == 0:
+            return np.empty((0, L + R), dtype=np.uint8)
+        fl = np.concatenate([rows[:, :L], rows[:, rows.shape[1] - R:]], axis=1)
+        return np.ascontiguousarray(np.unique(fl, axis=0))      # (groups_from_windows orders groups by these bytes)
+    text = "".join(g[0].left + g[0].right for g in groups).replace("U", "T").encode("ascii")
+    return np.frombuffer(text, dtype=np.uint8).reshape(-1, L + R)
+
+
+LOCATE_MAX_BASES = (1 << 33) - 65     # the packed path's limit (KR_MAX_BASES)
+
+
+def _scan_genomes(files, Le, De, Re, k, omit_soft, device, table):
+    """The per-file loop of the passes that scan one genome at a time (locate_regions, near_matches, predict_products,
+    primer_products): a locate context on `device`, table(eng) once, then every file uploaded alone as genome 0.
+    Yields (eng, file index, path, RNA, names): names() -> (the record separators, the record IDs), their count checked.
+    (The next file is read and inflated on a host thread while the device holds the current one: two texts at most.)"""
+    from concurrent.futures import ThreadPoolExecutor
+    with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
+        eng.set_params_locate(Le, De, Re, omit_soft, max_bases=LOCATE_MAX_BASES)
+        table(eng)
+        ahead = pool.submit(fasta.read_text, files[0]) if files else None
+        for fi, path in enumerate(files):
+            text, universal = ahead.result()
+            ahead = pool.submit(fasta.read_text, files[fi + 1]) if fi + 1 < len(files) else None
+            while True:
+                try:
+                    n, rna, _ = fasta.ingest_on_device(eng, 0, text, universal, k, omit_soft)
+                    break
+                except fasta.GzipTextLonger:
+                    text, universal = fasta.read_text(path)     # (that file is read on the host from now on: read_text knows it)
+
+            def names():
+                seps = eng.locate_seps(0).astype(np.int64)
+                # the record IDs: from the text the host holds, or -- a file the device inflated -- from the file read again
+                ids = fasta.record_ids(path) if isinstance(text, fasta.BgzfFile) else fasta.record_ids_text(text, universal)
+                nrec = len(seps) + 1 if n else 0
+                if n and len(ids) != nrec:
+                    raise RuntimeError(f"{path}: {len(ids)} record IDs, but the device's bases hold {nrec} records")
+                return seps, ids
+
+            yield eng, fi, path, rna, names
+            del text, names
+
+
+def _record_coords(seps, pos):
+    """positions in the device's bases -> (index of the record, 0-based start in it); seps = the separators, ascending"""
+    ri = np.searchsorted(seps, pos)
+    rec_start = np.where(ri > 0, seps[np.maximum(ri - 1, 0)] + 1, 0) if len(seps) else 0
+    return ri, pos - rec_start
+
+
+def _fill_shared(part, path, seps, ids, pos, strand):
+    """the columns every pass's dtype has: file, record, record_index, start, strand ('end' is the pass's own)"""
+    ri, start = _record_coords(seps, pos)
+    part["file"] = path
+    part["record"] = np.asarray(ids, dtype=object)[ri]
+    part["record_index"] = ri
+    part["start"] = start
+    part["strand"] = np.where(strand == 0, "+", "-")
+
+
+def _rows_text(rows, k, rna):
+    """(n, k) window bytes -> the n texts as objects, U for T in an RNA genome"""
+    if rna:
+        rows = np.where(rows == ord("T"), np.uint8(ord("U")), rows)
+    return np.ascontiguousarray(rows).view(f"S{k}").ravel().astype(f"U{k}").astype(object)
+
+
+def _sorted_parts(parts, dtype):
+    """parts = [(file index, the file's rows, their sort key)] -> one array ordered by the key, then the file's index
+    (stable: a file's rows of one key keep their order)"""
+    if not parts:
+        return np.empty(0, dtype=dtype)
+    out = np.concatenate([p for _, p, _ in parts])
+    fidx = np.concatenate([np.full(len(p), fi, dtype=np.int64) for fi, p, _ in parts])
+    return out[np.lexsort((fidx, np.concatenate([key for _, _, key in parts])))]
+
+
+def _fan_out(index, regions):
+    """A hit of table row t is a row for every region that owns t.  index: the table row of every hit, regions[t]: the
+    regions of row t (a list of lists) -> (rep, region): output row j repeats hit rep[j] for region[j]; a hit's rows
+    stand together, in the order of its table row's list"""
+    count = np.array([len(r) for r in regions], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(count)])
+    flat = np.array([x for r in regions for x in r], dtype=np.uint32)
+    each = count[index]
+    rep = np.repeat(np.arange(len(index)), each)
+    within = np.arange(len(rep)) - np.repeat(np.cumsum(each) - each, each)
+    return rep, flat[first[index[rep]] + within]
+
+
+def _fill_product(part, hits):
+    """the product's columns from PRODUCT_HIT-shaped hits, after _fill_shared: length, end and the four mismatch figures"""
+    part["length"] = hits["length"]
+    part["end"] = part["start"] + part["length"]
+    part["left_mismatches"] = hits["left_mm"]
+    part["right_mismatches"] = hits["right_mm"]
+    part["left_end_mismatches"] = hits["left_end_mm"]
+    part["right_end_mismatches"] = hits["right_end_mm"]
+
+
+def _mask_columns(mask):
+    """a column mask -> the 1-based columns that differ, ascending and comma-separated; '-' for none"""
+    return ",".join(str(c + 1) for c in range(64) if (mask >> c) & 1) or "-"
+
+
+def _fill_guide_hit(part, hits, count="mismatches", src_count="mismatches", src_pam="pam"):
+    """a guide hit's columns: the mismatch count (part[count] from hits[src_count]), the columns that differ and the two
+    motif bits of hits[src_pam]"""
+    part[count] = hits[src_count]
+    part["mismatch_columns"] = [_mask_columns(m) for m in hits["columns"].tolist()]
+    part["pam5_match"] = hits[src_pam] & 1
+    part["pam3_match"] = (hits[src_pam] >> 1) & 1
+
+
+def _text_matrix(texts, G, who):
+    """the guide texts of pass `who` -> uint8 [texts, G]; ValueError unless every text has G letters"""
+    if any(len(t) != G for t in texts):
+        raise ValueError(f"{who}: every text has --guide-size = {G} letters")
+    return np.frombuffer(b"".join(bytes(t) for t in texts), dtype=np.uint8).reshape(-1, G)
+
+
+def _check_max_product(max_product, left, right, pairs):
+    """ValueError unless max_product holds the two primers of every pair"""
+    for i, j in pairs.tolist():
+        if max_product < len(left[i]) + len(right[j]):
+            raise ValueError(f"--max-product must be at least a pair's two primers together, {len(left[i]) + len(right[j])} "
+                             f"bases (got {max_product})")
+
+
+def _write_tsv(path, header, rows, names=None):
+    """`header`, then a line per row of the structured array `rows`: its fields `names` (default: all, in the dtype's
+    order), each an int or a str, tab-separated"""
+    names = rows.dtype.names if names is None else names
+    with open(path, "w") as f:
+        f.write(header + "\n")
+        f.writelines("\t".join(str(v) for v in row) + "\n" for row in zip(*(rows[n].tolist() for n in names)))
+
+
+def locate_regions(groups, ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=False, device=0):
+    """Where every window of every group lies: `groups` as find_regions / find_regions_multi_device /
+    find_regions_distributed returned them (lists, amplicon.RecordGroups, amplicon.WindowGroups), the same files and
+    geometry.  A separate pass over the inputs on one device (kr_locate_*): each genome is uploaded alone and scanned
+    against a hash table of the groups' (left, right) flanks.  Returns a LOCATION array, one row per window and strand:
+    region = the group's index, file = the path as given, record / record_index = the record's ID and its index among
+    the records the reader yields (fasta.read_records), start / end = 0-based half-open coordinates on the record's
+    forward strand, strand '+' (the window as written) or '-' (its reverse complement), sequence = the k-mer as the
+    alignment lists it for that genome.  Rows in (region, file in command-line order, record_index, start, strand) order.
+    For every group, genome label and sequence there are as many rows as the label occurs in that Amplicon's labels."""
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    flanks = _group_flanks(groups, Le, Re)
+    if len(flanks) == 0:
+        return np.empty(0, dtype=LOCATION)
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device, lambda eng: eng.locate_table(flanks)):
+        hits = eng.locate(0)
+        rows = eng.locate_windows(k)
+        seps, ids = names()             # (checked for a genome without hits too)
+        if len(hits) == 0:
+            continue
+        part = np.empty(len(hits), dtype=LOCATION)
+        _fill_shared(part, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        part["region"] = hits["group"]
+        part["end"] = part["start"] + k
+        part["sequence"] = _rows_text(rows, k, rna)
+        parts.append((fi, part, part["region"]))       # (a file's rows are in (position, strand) order already)
+    return _sorted_parts(parts, LOCATION)
+
+
+def write_locations(path, locs):
+    """the TSV of --out_locations: LOCATION_HEADER, then a line per row"""
+    _write_tsv(path, LOCATION_HEADER, locs, LOCATION.names)
+
+
+# ----------------------------------------------------------------------------
+# near matches of the ingroup windows in every genome (--out_near)
+# ----------------------------------------------------------------------------
+NEAR_HEADER = "region\ttarget\tfile\trecord\trecord_index\tstart\tend\tstrand\tmismatches\tflank_mismatches\tsequence"
+NEAR = np.dtype([("region", "<u4"), ("target", "O"), ("file", "O"), ("record", "O"), ("record_index", "<i8"),
+                 ("start", "<i8"), ("end", "<i8"), ("strand", "U1"), ("mismatches", "<u4"), ("flank_mismatches", "<u4"),
+                 ("sequence", "O")])
+NEAR_MAX_MISMATCHES = 3
+
+
+def near_refusal(L, R, amplicon_len, mismatches):
+    """why the near-match pass does not take this geometry and distance (one line), or None"""
+    k = amplicon_len
+    if mismatches < 0 or mismatches > NEAR_MAX_MISMATCHES:
+        return f"--near-mismatches must lie between 0 and {NEAR_MAX_MISMATCHES} (got {mismatches})"
+    if mismatches >= k:
+        return f"--near-mismatches must be smaller than the amplicon length {k} (got {mismatches})"
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    if _is_wide(Le, De, Re):
+        return (f"--out_near takes amplicons of at most 32 bases with at most 16 diagnostic bases (got {Le}/{De}/{Re}): for "
+                "longer amplicons near matches are a question of primers, not of Hamming distance")
+    return None
+
+
+def near_targets(groups, ingroup_labels):
+    """The targets of the near-match pass: for group i, the sequence (U written as T) of every Amplicon that has at least
+    one ingroup label -- of every Amplicon when ingroup_labels is None (a run without outgroup) --, equal texts once,
+    ordered by their bytes.  `groups` in any form find_regions* returns.  -> list of (i, text), ordered by (i, text)."""
+    ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
+    out = []
+    for i, g in enumerate(groups):
+        texts = {a.sequence.replace("U", "T").replace("u", "t") for a in g
+                 if ingroup is None or not ingroup.isdisjoint(a.labels)}
+        out.extend((i, t) for t in sorted(texts, key=lambda t: t.encode("ascii")))
+    return out
+
+
+def near_matches(groups, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1, omit_soft=False, device=0):
+    """Every window of every input genome within Hamming distance `mismatches` of a target (near_targets: the ingroup
+    windows of the diagnostic regions), on both strands, wherever it lies -- what the exact k-mer intersection cannot
+    see: a window whose conserved FLANK differs by a substitution or two.  `groups` as find_regions* returned them, the
+    same files and geometry.  A separate pass over the inputs on one device in the manner of locate_regions
+    (kr_near_*: pigeonhole seeds filter, a byte comparison decides).  Returns a NEAR array: region, target (DNA letters),
+    file, record, record_index, start, end, strand, sequence as in LOCATION; mismatches = the differing columns,
+    flank_mismatches = those of them in the conserved flanks.  Rows in (region, target, file in command-line order,
+    record_index, start, '+' before '-') order.  Packed geometries only, 0 <= mismatches <= 3 (ValueError otherwise)."""
+    why = near_refusal(L, R, amplicon_len, mismatches)
+    if why is not None:
+        raise ValueError(why)
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    ingroup = [simplename(f) for f in ingroup_files] if len(outgroup_files) else None
+    targets = near_targets(groups, ingroup)
+    if not targets:
+        return np.empty(0, dtype=NEAR)
+    t_region = np.array([i for i, _ in targets], dtype=np.uint32)
+    t_text = np.array([t for _, t in targets], dtype=object)
+    t_bytes = np.frombuffer("".join(t for _, t in targets).encode("ascii"), dtype=np.uint8).reshape(-1, k)
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device,
+                                                   lambda eng: eng.near_table(t_bytes, mismatches)):
+        hits = eng.near(0)
+        if len(hits) == 0:
+            continue
+        rows = eng.near_windows(k)
+        seps, ids = names()
+        pos = hits["pos"].astype(np.int64)
+        tg = hits["target"].astype(np.int64)
+        part = np.empty(len(hits), dtype=NEAR)
+        _fill_shared(part, path, seps, ids, pos, hits["strand"])
+        part["region"] = t_region[tg]
+        part["target"] = t_text[tg]
+        part["end"] = part["start"] + k
+        part["mismatches"] = hits["mismatches"]
+        part["flank_mismatches"] = hits["flank_mismatches"]
+        part["sequence"] = _rows_text(rows, k, rna)
+        # (a file's hits come in position order; within the table they go by target, then position, then strand)
+        order = np.lexsort((hits["strand"], pos, tg))
+        parts.append((fi, part[order], tg[order]))
+    return _sorted_parts(parts, NEAR)
+
+
+def write_near(path, rows):
+    """the TSV of --out_near: NEAR_HEADER, then a line per row"""
+    _write_tsv(path, NEAR_HEADER, rows, NEAR.names)
+
+
+# ----------------------------------------------------------------------------
+# predicted PCR products of the regions' flanks in every genome (--out_products)
+# ----------------------------------------------------------------------------
+PRODUCT_HEADER = ("region\tfile\trecord\trecord_index\tstart\tend\tstrand\tlength\tleft_mismatches\tright_mismatches\t"
+                  "left_end_mismatches\tright_end_mismatches")
+PRODUCT = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"),
+                    ("end", "<i8"), ("strand", "U1"), ("length", "<i8"), ("left_mismatches", "<u4"), ("right_mismatches", "<u4"),
+                    ("left_end_mismatches", "<u4"), ("right_end_mismatches", "<u4")])
+PRODUCT_MAX_MISMATCHES = 3
+PRODUCT_MIN_PRIMER = 10      # bases of a flank from which it is searched as a primer (a condition, not a measurement)
+PRODUCT_END = 5              # the "last five 3' bases" of --max_end_gc: where the end mismatches are counted
+
+
+def products_refusal(L, R, amplicon_len, mismatches, max_product):
+    """why the product pass does not take this geometry, distance and product length (one line), or None"""
+    k = amplicon_len
+    if mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES:
+        return f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    if min(Le, Re) < PRODUCT_MIN_PRIMER:
+        return (f"--out_products takes conserved flanks of at least {PRODUCT_MIN_PRIMER} bases each (got {Le}/{De}/{Re}): a "
+                "shorter text with a mismatch or two binds nearly everywhere")
+    if max_product < Le + Re:
+        return f"--max-product must be at least the two flanks together, {Le + Re} bases (got {max_product})"
+    if max_product >= 1 << 31:
+        return f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    return None
+
+
+def predict_products(groups, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1, max_product=1000,
+                     omit_soft=False, device=0):
+    """In-silico PCR of every region's conserved flanks against every input genome: a product is a window within
+    `mismatches` substitutions of the left flank and one within as many of the right flank on ONE record, facing each
+    other ('+': left ... right as written; '-': rc(right) ... rc(left)), not overlapping, at most `max_product` bases
+    from the first base of the first to the last base of the second -- whatever lies between them.  What the exact
+    k-mer intersection cannot see: a genome whose flank differs by a substitution, or whose diagnostic stretch is longer
+    or shorter, still amplifies.  `groups` as find_regions* returned them, the same files and geometry.  A separate pass
+    over the inputs on one device in the manner of locate_regions (kr_products_*).  Returns a PRODUCT array: region, file,
+    record, record_index, start, end, strand as in LOCATION (end - start = length); left / right_mismatches = the distance
+    of the left flank's and the right flank's window, left / right_end_mismatches = those of them in the PRODUCT_END
+    columns at the primer's 3' end (the last of the left flank, the first of the right).  Rows in (region, file in
+    command-line order, record_index, start, end, '+' before '-') order.  Flanks of at least PRODUCT_MIN_PRIMER bases,
+    0 <= mismatches <= 3 (ValueError otherwise)."""
+    why = products_refusal(L, R, amplicon_len, mismatches, max_product)
+    if why is not None:
+        raise ValueError(why)
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    flanks = _group_flanks(groups, Le, Re)
+    if len(flanks) == 0:
+        return np.empty(0, dtype=PRODUCT)
+    # (distinct texts once: regions that overlap share a flank; region i is pair i)
+    left, li = np.unique(flanks[:, :Le], axis=0, return_inverse=True)
+    right, ri_ = np.unique(flanks[:, Le:], axis=0, return_inverse=True)
+    pairs = np.stack([li.ravel(), ri_.ravel()], axis=1).astype(np.uint32)
+    parts = []
+    for eng, fi, path, _rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device,
+                                                    lambda eng: eng.products_table(left, right, pairs, mismatches, max_product)):
+        hits = eng.products(0)
+        if len(hits) == 0:
+            continue
+        seps, ids = names()
+        part = np.empty(len(hits), dtype=PRODUCT)
+        _fill_shared(part, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        part["region"] = hits["pair"]
+        _fill_product(part, hits)
+        # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start))
+        parts.append((fi, part, part["region"]))
+    return _sorted_parts(parts, PRODUCT)
+
+
+def write_products(path, rows):
+    """the TSV of --out_products and of --out_primer_products: PRODUCT_HEADER, then a line per row"""
+    _write_tsv(path, PRODUCT_HEADER, rows, PRODUCT.names)
+
+
+# ----------------------------------------------------------------------------
+# a primer pair per region, designed on the device (--design-primers)
+# ----------------------------------------------------------------------------
+def design_templates(groups, ingroup_labels):
+    """the templates of the groups (primers.design_template) -> (uint8 [groups, L + D + R], L, D, R)"""
+    from . import primers
+    ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
+    texts, geo = [], (0, 0, 0)
+    for g in groups:
+        geo = (len(g[0].left), len(g[0].diag), len(g[0].right))
+        texts.append(primers.design_template(g, ingroup))
+    k = sum(geo)
+    if any(len(t) != k for t in texts):
+        raise ValueError("design_templates: groups of more than one geometry")
+    rows = np.frombuffer("".join(texts).encode("ascii"), dtype=np.uint8).reshape(len(texts), k) if texts else \
+        np.empty((0, max(k, 1)), dtype=np.uint8)
+    return (rows,) + geo
+
+
+def design_primers(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(70, 150), primer_size=(25, 35), max_sec_tm=40,
+                   gc_clamp=1, max_end_gc=4, device=0, hairpins=False, templates=None):
+    """A primer pair for every region, on the device (kr_design_*): on the consensus of the region's ingroup
+    Amplicons -- the template --primer3 designs on -- a left primer inside the left flank and a right primer inside the
+    right flank, lengths within `primer_size`; nearest-neighbour Tm within `tm` (degrees Celsius), GC percent within `gc`,
+    no run of five equal bases, the last `gc_clamp` 3' bases G or C, at most `max_end_gc` G or C among the last five; the
+    duplex figures (the highest Tm of a run of Watson-Crick pairs in an ungapped antiparallel alignment: self_any, self_end,
+    pair_any, pair_end) at most `max_sec_tm`; the product within `amp_size`; of the passing pairs the one of least
+    penalty, ties to the smallest (left_start, left_len, right_start, right_len).  Every figure is an integer
+    (krisp_amd/thermo.py holds the model); no gapped or mismatched duplexes: this is not Primer3.  hairpins=True holds
+    every primer to `max_sec_tm` for its hairpin figure too (the highest Tm of a stem of two or more pairs
+    around a loop of three or more bases) and returns it.
+    `groups` as find_regions* returned them.  Returns a _native.DESIGN_RECORD array, one row per group (found = 0: no
+    pair); with hairpins a DESIGN_RECORD_HP array, the same fields and left_hairpin, right_hairpin.  ValueError for figures
+    the pass does not take (thermo.refusal).  templates = design_templates(groups, ingroup_labels) where the caller has them
+    already."""
+    from . import thermo
+    opts = dict(tm=tuple(tm), gc=tuple(gc), amp_size=tuple(amp_size), primer_size=tuple(primer_size), max_sec_tm=max_sec_tm,
+                gc_clamp=gc_clamp, max_end_gc=max_end_gc)
+    why = thermo.refusal(**opts)
+    if why is not None:
+        raise ValueError(why)
+    rows, L, D, R = design_templates(groups, ingroup_labels) if templates is None else templates
+    if len(rows) == 0:
+        from . import _native
+        return np.empty(0, dtype=_native.DESIGN_RECORD_HP if hairpins else _native.DESIGN_RECORD)
+    with _engine(device) as eng:
+        eng.design_table(thermo.params(**opts))
+        if hairpins:
+            eng.design_hairpins(thermo.hairpin_params())
+        return eng.design(rows, L, D, R)
+
+
+# ----------------------------------------------------------------------------
+# predicted PCR products of the designed primer pairs in every genome (--design-primers --out_primer_products)
+# ----------------------------------------------------------------------------
+def primer_products_refusal(amp_size, mismatches, max_product):
+    """why the primer-product pass does not take this distance and product length (one line), or None"""
+    if mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES:
+        return f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    if amp_size is not None and max_product < amp_size[1]:
+        return (f"--max-product must be at least the upper bound of --amp_size, {amp_size[1]} bases (got {max_product}): the "
+                "designed product itself would not be found")
+    if max_product >= 1 << 31:
+        return f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    return None
+
+
+def primer_pairs(rows, records):
+    """The table of the primer-product pass from the templates (design_templates) and design_primers' records: the
+    regions with found = 0 take no part, a region's left text is template[left_start, left_start + left_len) and its
+    right text template[right_start, right_start + right_len) (the template's text under the right primer), equal texts
+    are listed once (ordered by their bytes), equal (left, right) pairs of different regions once.  -> (left texts, right
+    texts, pairs [np, 2], regions of pair p as a list of lists): a region is named by its rank among the regions with
+    a pair."""
+    lt, rt = [], []
+    for row, r in zip(rows, records):
+        if not int(r["found"]):
+            continue
+        ls, ll, rs, rl = (int(r[f]) for f in ("left_start", "left_len", "right_start", "right_len"))
+        lt.append(bytes(row[ls:ls + ll]))
+        rt.append(bytes(row[rs:rs + rl]))
+    left, right = sorted(set(lt)), sorted(set(rt))
+    li = {t: i for i, t in enumerate(left)}
+    ri = {t: i for i, t in enumerate(right)}
+    regions = {}
+    for rank, (a, b) in enumerate(zip(lt, rt)):
+        regions.setdefault((li[a], ri[b]), []).append(rank)
+    keys = sorted(regions)
+    return left, right, np.array(keys, dtype=np.uint32).reshape(-1, 2), [regions[k] for k in keys]
+
+
+def primer_products(groups, records, ingroup_labels, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1,
+                    max_product=1000, omit_soft=False, device=0):
+    """In-silico PCR of the primer pairs design_primers picked (`records`, one per group) against every input genome:
+    predict_products with the designed primers in the place of the flanks.  A primer lies anywhere inside its flank, has a
+    length of its own within --primer_size and its own 3' end: a site is a window of the PRIMER'S length within
+    `mismatches` substitutions of it, left / right_end_mismatches count the PRODUCT_END columns at the primer's own 3' end,
+    and a product is a left primer's site and a right primer's on one record, facing each other, not overlapping, at most
+    `max_product` bases from end to end.  The texts are cut from design_templates(groups, ingroup_labels); regions without
+    a pair take no part.  A separate pass over the inputs on one device in the manner of locate_regions (kr_primers_*).
+    Returns a PRODUCT array whose `region` is the region's rank among the regions with a pair -- its data row in the CSV
+    of --design-primers when the renderer was not stopped --, the other columns and the rows' order as predict_products
+    gives them.  Neighbouring regions that get the same pair each have their rows.  ValueError for figures the pass does
+    not take."""
+    why = primer_products_refusal(None, mismatches, max_product)
+    if why is None and len(records) != len(groups):
+        why = f"primer_products: {len(records)} records for {len(groups)} groups"
+    if why is not None:
+        raise ValueError(why)
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    rows, _, _, _ = design_templates(groups, ingroup_labels)
+    left, right, pairs, regions = primer_pairs(rows, records)
+    if len(pairs) == 0:
+        return np.empty(0, dtype=PRODUCT)
+    _check_max_product(max_product, left, right, pairs)
+    parts = []
+    for eng, fi, path, _rna, names in _scan_genomes(files, Le, De, Re, k, omit_soft, device,
+                                                    lambda eng: eng.primers_table(left + right, len(left), pairs, mismatches,
+                                                                                  max_product)):
+        hits = eng.primer_products(0)
+        if len(hits) == 0:
+            continue
+        seps, ids = names()
+        # a hit of pair p is a row for every region of p
+        rep, region = _fan_out(hits["pair"].astype(np.int64), regions)
+        hits = hits[rep]
+        part = np.empty(len(hits), dtype=PRODUCT)
+        _fill_shared(part, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        part["region"] = region
+        _fill_product(part, hits)
+        # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start))
+        parts.append((fi, part, part["region"]))
+    return _sorted_parts(parts, PRODUCT)
+
+
+# ----------------------------------------------------------------------------
+# a CRISPR guide per region, picked on the device (--out_guides)
+# ----------------------------------------------------------------------------
+GUIDE_HEADER = "region\tstrand\tstart\tend\tpam5\tpam3\tprotospacer\tgc_percent\tmin_mismatches\tsum_mismatches\tcandidates"
+GUIDE_MIN_SIZE, GUIDE_MAX_SIZE, GUIDE_MAX_MOTIF = 12, 40, 8
+# the IUPAC code as 4-bit sets: A = 1, C = 2, G = 4, T = 8
+IUPAC_MASK = {"A": 1, "C": 2, "G": 4, "T": 8, "U": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11,
+              "V": 7, "N": 15}
+_GUIDE_COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def motif_masks(motif):
+    """a PAM / PFS motif in IUPAC letters (either case, U as T) -> its 4-bit masks, one per letter; ValueError for a
+    letter outside the code"""
+    out = []
+    for ch in motif.upper():
+        if ch not in IUPAC_MASK:
+            raise ValueError(f"{ch!r} in the motif {motif!r} is no letter of the IUPAC code")
+        out.append(IUPAC_MASK[ch])
+    return out
+
+
+def guides_refusal(amplicon_len, guide_size, pam5, pam3, gc, min_mismatches):
+    """why the guide pass does not take these figures (one line), or None"""
+    if guide_size < GUIDE_MIN_SIZE or guide_size > GUIDE_MAX_SIZE:
+        return f"--guide-size must lie between {GUIDE_MIN_SIZE} and {GUIDE_MAX_SIZE} (got {guide_size})"
+    if amplicon_len is not None and guide_size > amplicon_len:
+        return f"--guide-size must not exceed the amplicon length {amplicon_len} (got {guide_size})"
+    for opt, motif in (("--pam5", pam5), ("--pam3", pam3)):
+        if len(motif) > GUIDE_MAX_MOTIF:
+            return f"{opt} takes at most {GUIDE_MAX_MOTIF} letters (got {motif!r})"
+        try:
+            motif_masks(motif)
+        except ValueError as e:
+            return f"{opt}: {e}"
+    if gc[0] > gc[1]:
+        return f"--guide-gc: the upper bound lies below the lower ({gc[0]} .. {gc[1]})"
+    if min_mismatches < 0 or min_mismatches > guide_size:
+        return f"--guide-min-mismatches must lie between 0 and --guide-size, {guide_size} (got {min_mismatches})"
+    return None
+
+
+def guide_rows(groups, ingroup_labels, templates=None):
+    """The rows of the guide pass: per group its template (primers.design_template), then one row per
+    Amplicon of the group the template leaves out -- the outgroup rows, left + diag + right, upper case, U written as T.
+    No ingroup_labels (a run without --outgroup): no outgroup rows.  templates = design_templates(groups, ingroup_labels)
+    where the caller has them already.  -> (uint8 [rows, L + D + R], uint64 [groups + 1] row offsets, L, D, R)"""
+    trows, L, D, R = design_templates(groups, ingroup_labels) if templates is None else templates
+    ingroup = None if ingroup_labels is None else frozenset(ingroup_labels)
+    k = L + D + R
+    parts, off = [], [0]
+    for gi, g in enumerate(groups):
+        texts = []
+        if ingroup is not None and len(g) > 1:
+            texts = [(a.left + a.diag + a.right).upper().replace("U", "T") for a in g if not set(a.labels) <= ingroup]
+        if any(len(t) != k for t in texts):
+            raise ValueError("guide_rows: groups of more than one geometry")
+        parts.append(bytes(trows[gi]))
+        parts.extend(t.encode("ascii") for t in texts)
+        off.append(off[-1] + 1 + len(texts))
+    if len(off) - 1 != len(trows):
+        raise ValueError(f"guide_rows: {len(trows)} templates for {len(off) - 1} groups")
+    rows = np.frombuffer(b"".join(parts), dtype=np.uint8).reshape(off[-1], k) if parts else np.empty((0, max(k, 1)), dtype=np.uint8)
+    return rows, np.array(off, dtype=np.uint64), L, D, R
+
+
+def design_guides(groups, ingroup_labels, guide_size=28, pam5="", pam3="", gc=(30, 70), min_mismatches=1, bounds=None, device=0,
+                  templates=None):
+    """A CRISPR guide for every region, on the device (kr_guides_*): the window of `guide_size` columns of the
+    region's template -- on either strand -- whose 5' neighbours match the motif `pam5` and whose 3' neighbours match `pam3`
+    (IUPAC letters, read 5'->3' on the guide's strand; "" = none), that holds only bases, has a GC percent within `gc` and
+    no run of five equal bases, and that differs from every outgroup row of the region (guide_rows) in at least
+    `min_mismatches` columns; of those the one whose least number of differences to an outgroup row is greatest, then
+    whose sum over the outgroup rows is greatest, then the best centred on the diagnostic stretch, '+' before '-', the
+    leftmost.  bounds: [groups, 2] columns [lo, hi) that window and motifs must lie in (default: the whole template).
+    Every figure is an integer: no seed weights, no folding of the guide, no gapped matches, no off-target search.
+    Returns a _native.GUIDE_RECORD array, one row per group (found = 0: no guide).  ValueError for figures the pass does
+    not take (guides_refusal)."""
+    from . import _native
+    why = guides_refusal(None, guide_size, pam5, pam3, tuple(gc), min_mismatches)
+    if why is not None:
+        raise ValueError(why)
+    rows, off, L, D, R = guide_rows(groups, ingroup_labels, templates)
+    n = len(off) - 1
+    if n == 0:
+        return np.empty(0, dtype=_native.GUIDE_RECORD)
+    k = L + D + R
+    if guide_size > k:
+        raise ValueError(f"--guide-size must not exceed the amplicon length {k} (got {guide_size})")
+    if bounds is None:
+        bounds = np.tile(np.array([0, k], dtype=np.uint32), (n, 1))
+    with _engine(device) as eng:
+        eng.guides_table(guide_size, motif_masks(pam5), motif_masks(pam3), tuple(gc), min_mismatches)
+        return eng.guides(rows, off, bounds, L, D)
+
+
+def _guide_rc(text):
+    return text[::-1].translate(_GUIDE_COMPLEMENT)
+
+
+def write_guides(path, templates, records, guide_size, pam5_len=0, pam3_len=0, regions=None):
+    """the TSV of --out_guides: GUIDE_HEADER, then a line per region with a guide.  templates: the regions' template rows
+    (design_templates), records: theirs (design_guides, or any array with GUIDE_RECORD's fields), regions: the number each
+    region is listed under (default: its index).  start / end = the window's template columns, 0-based and half-open;
+    pam5, pam3 and protospacer as read 5'->3' on the guide's strand"""
+    from . import thermo
+    g, a, b = guide_size, pam5_len, pam3_len
+    with open(path, "w") as f:
+        f.write(GUIDE_HEADER + "\n")
+        for i, (row, r) in enumerate(zip(templates, records)):
+            if not int(r["found"]):
+                continue
+            t = bytes(row).decode("ascii")
+            p = int(r["start"])
+            if int(r["strand"]) == 0:
+                strand, proto, m5, m3 = "+", t[p:p + g], t[p - a:p], t[p + g:p + g + b]
+            else:
+                strand, proto, m5, m3 = "-", _guide_rc(t[p:p + g]), _guide_rc(t[p + g:p + g + a]), _guide_rc(t[p - b:p])
+            region = i if regions is None else int(regions[i])
+            f.write(f"{region}\t{strand}\t{p}\t{p + g}\t{m5}\t{m3}\t{proto}\t{thermo.gc_percent(int(r['gc']), g)}\t"
+                    f"{int(r['min_mismatches'])}\t{int(r['sum_mismatches'])}\t{int(r['candidates'])}\n")
+
+
+# ----------------------------------------------------------------------------
+# the picked guides searched in every genome (--out_guide_hits)
+# ----------------------------------------------------------------------------
+GUIDE_HIT_HEADER = ("region\tfile\trecord\trecord_index\tstart\tend\tstrand\tmismatches\tmismatch_columns\tpam5_match\t"
+                    "pam3_match\tsequence")
+GUIDE_HIT = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"),
+                      ("end", "<i8"), ("strand", "U1"), ("mismatches", "<u4"), ("mismatch_columns", "O"), ("pam5_match", "<u4"),
+                      ("pam3_match", "<u4"), ("sequence", "O")])
+
+
+def guide_texts(templates, records, guide_size, regions=None):
+    """The table of a guide-hit pass from the regions' template rows (design_templates) and design_guides' records: the
+    regions with found = 0 take no part; a region's text is its protospacer as read 5'->3' on the guide's strand
+    (template[start, start + guide_size), its reverse complement for strand 1); equal texts are listed once, ordered by
+    their bytes.  regions: the number each region is listed under in the --out_guides file (default: its index).
+    -> (the distinct texts as bytes, the regions of text t as a list of lists, ascending)"""
+    g = guide_size
+    by_text = {}
+    for i, (row, r) in enumerate(zip(templates, records)):
+        if not int(r["found"]):
+            continue
+        p = int(r["start"])
+        t = bytes(row[p:p + g]).decode("ascii")
+        if int(r["strand"]):
+            t = _guide_rc(t)
+        by_text.setdefault(t.encode("ascii"), []).append(i if regions is None else int(regions[i]))
+    texts = sorted(by_text)
+    return texts, [sorted(by_text[t]) for t in texts]
+
+
+GUIDE_HIT_MAX_MISMATCHES = 3
+
+
+GUIDE_HIT_MAX_BULGES = 2
+GUIDE_BULGE_MIN_SIZE = 20           # with --guide-hit-bulges: the seeds are the guides' halves, (guide size - bulges) / 2 letters
+GUIDE_BULGE_MAX_MISMATCHES = 2      # ... and each is searched within the mismatches: shorter or looser, nearly every window is a seed
+
+
+def guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam, bulges=0):
+    """why the guide-hit pass does not take these figures (one line), or None.  bulges: --guide-hit-bulges"""
+    if bulges < 0 or bulges > GUIDE_HIT_MAX_BULGES:
+        return f"--guide-hit-bulges must lie between 0 and {GUIDE_HIT_MAX_BULGES} (got {bulges})"
+    if bulges and guide_size < GUIDE_BULGE_MIN_SIZE:
+        return (f"--guide-hit-bulges needs --guide-size >= {GUIDE_BULGE_MIN_SIZE} (got {guide_size}): the bulged search seeds with "
+                "half-guides, and halves of fewer than 9 letters lie within the mismatches of nearly every window (DESIGN §20, cost)")
+    if bulges and mismatches > GUIDE_BULGE_MAX_MISMATCHES:
+        return (f"--guide-hit-bulges needs --guide-hit-mismatches <= {GUIDE_BULGE_MAX_MISMATCHES} (got {mismatches}): a half-guide "
+                "within 3 mismatches seeds millions of windows per guide and genome (DESIGN §20, cost)")
+    if guide_size < GUIDE_MIN_SIZE or guide_size > GUIDE_MAX_SIZE:
+        return f"--guide-size must lie between {GUIDE_MIN_SIZE} and {GUIDE_MAX_SIZE} (got {guide_size})"
+    if mismatches < 0 or mismatches > GUIDE_HIT_MAX_MISMATCHES:
+        return f"--guide-hit-mismatches must lie between 0 and {GUIDE_HIT_MAX_MISMATCHES} (got {mismatches})"
+    for opt, motif in (("--pam5", pam5), ("--pam3", pam3)):
+        if len(motif) > GUIDE_MAX_MOTIF:
+            return f"{opt} takes at most {GUIDE_MAX_MOTIF} letters (got {motif!r})"
+        try:
+            motif_masks(motif)
+        except ValueError as e:
+            return f"{opt}: {e}"
+    if need_pam and not pam5 and not pam3:
+        return "--guide-hits-need-pam needs a motif: --pam5 or --pam3"
+    return None
+
+
+def guide_hits(texts, text_regions, ingroup_files, outgroup_files, guide_size, mismatches=2, pam5="", pam3="", need_pam=False,
+               omit_soft=False, device=0):
+    """Every window of every input genome within Hamming distance `mismatches` of a picked guide's protospacer, on both
+    strands, wherever it lies: the specificity pass of --out_guides.  texts, text_regions = guide_texts(...):
+    the distinct protospacers and the regions that carry each.  A separate pass over the inputs on one device in the manner
+    of near_matches (kr_guide_hits_*: the near pass's scan, a per-hit step for the column mask and the motifs).  Returns a
+    GUIDE_HIT array: region, file, record, record_index, start, strand as in LOCATION, end = start + guide_size,
+    mismatches, mismatch_columns (the 1-based columns that differ, 5'->3' on the guide), pam5_match / pam3_match = 1 where
+    the motif lies beside the window as read on the guide's strand (an empty motif matches), sequence = the window on the
+    guide's strand.  With need_pam a window counts only where both motifs match.  A hit of a text that several regions
+    share is a row for each of them.  Rows in (region, file in command-line order, record_index, start, '+' before '-')
+    order.  ValueError for figures the pass does not take (guide_hits_refusal)."""
+    why = guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam)
+    if why is not None:
+        raise ValueError(why)
+    if len(texts) != len(text_regions):
+        raise ValueError(f"guide_hits: {len(texts)} texts, the regions of {len(text_regions)}")
+    files = list(ingroup_files) + list(outgroup_files)
+    G = guide_size
+    if len(texts) == 0:
+        return np.empty(0, dtype=GUIDE_HIT)
+    t_bytes = _text_matrix(texts, G, "guide_hits")
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, 0, G, 0, G, omit_soft, device,
+                                                   lambda eng: eng.guide_hits_table(t_bytes, mismatches, pam5, pam3, need_pam)):
+        hits = eng.guide_hits(0)
+        if len(hits) == 0:
+            continue
+        rows = eng.guide_hit_windows(G)
+        seps, ids = names()
+        shared = np.empty(len(hits), dtype=GUIDE_HIT)
+        _fill_shared(shared, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        shared["end"] = shared["start"] + G
+        _fill_guide_hit(shared, hits)
+        shared["sequence"] = _rows_text(rows, G, rna)
+        # a hit of text t is a row for every region of t
+        rep, region = _fan_out(hits["guide"].astype(np.int64), text_regions)
+        part = shared[rep]
+        part["region"] = region
+        order = np.lexsort((part["strand"] == "-", part["start"], part["record_index"], part["region"]))
+        parts.append((fi, part[order], part["region"][order]))
+    return _sorted_parts(parts, GUIDE_HIT)
+
+
+def write_guide_hits(path, rows):
+    """the TSV of the guide hits: GUIDE_HIT_HEADER, then a line per row"""
+    _write_tsv(path, GUIDE_HIT_HEADER, rows, GUIDE_HIT.names)
+
+
+GUIDE_BULGE_HIT_HEADER = GUIDE_HIT_HEADER + "\tbulge\tbulge_size\tbulge_column"
+GUIDE_BULGE_HIT = np.dtype(GUIDE_HIT.descr + [("bulge", "O"), ("bulge_size", "<u4"), ("bulge_column", "O")])
+
+
+def guide_bulge_hits(texts, text_regions, ingroup_files, outgroup_files, guide_size, mismatches=2, bulges=1, pam5="", pam3="",
+                     need_pam=False, omit_soft=False, device=0):
+    """Every window of every input genome that lies within `mismatches` substitutions of a picked guide's protospacer once
+    one bulge of 1 .. `bulges` bases is allowed for, on both strands (--guide-hit-bulges): a DNA bulge (the
+    genome holds bases the guide has no partner for: the window has guide_size + b bases) or an RNA bulge (guide letters
+    have no partner: guide_size - b bases).  One contiguous bulge, never at a guide end; a window's row carries the least
+    number of mismatches over the places of the bulge and, of those that reach it, the one nearest the guide's 5' end.
+    The arguments and the rows' order are guide_hits'; the unbulged hits are guide_hits' own and no part of the result.
+    (kr_guide_bulges_*: the near pass's scan over the guides' halves, a per-pair step that extends each seed.)  Returns a
+    GUIDE_BULGE_HIT array: GUIDE_HIT's fields -- end = start + guide_size +- b, mismatch_columns of the aligned columns
+    only, sequence = the window on the guide's strand -- and bulge ("DNA" / "RNA"), bulge_size, bulge_column (the
+    1-based guide column after which the bulge lies).  Rows in (region, file in command-line order, record_index, start,
+    '+' before '-', end) order.  ValueError for figures the pass does not take (guide_hits_refusal)."""
+    why = guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam, bulges=bulges)
+    if why is None and bulges < 1:
+        why = f"guide_bulge_hits: bulges is 1 or 2 (got {bulges})"
+    if why is not None:
+        raise ValueError(why)
+    if len(texts) != len(text_regions):
+        raise ValueError(f"guide_bulge_hits: {len(texts)} texts, the regions of {len(text_regions)}")
+    files = list(ingroup_files) + list(outgroup_files)
+    G, W = guide_size, guide_size + bulges
+    if len(texts) == 0:
+        return np.empty(0, dtype=GUIDE_BULGE_HIT)
+    t_bytes = _text_matrix(texts, G, "guide_bulge_hits")
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, 0, G, 0, G, omit_soft, device,
+                                                   lambda eng: eng.guide_bulges_table(t_bytes, mismatches, bulges, pam5, pam3, need_pam)):
+        hits = eng.guide_bulges(0)
+        if len(hits) == 0:
+            continue
+        rows = eng.guide_bulge_windows(W)
+        seps, ids = names()
+        shared = np.empty(len(hits), dtype=GUIDE_BULGE_HIT)
+        _fill_shared(shared, path, seps, ids, hits["pos"].astype(np.int64), hits["strand"])
+        length = hits["length"].astype(np.int64)
+        shared["end"] = shared["start"] + length
+        _fill_guide_hit(shared, hits)
+        padded = _rows_text(np.where(rows == 0, np.uint8(ord(" ")), rows), W, rna)
+        shared["sequence"] = [t[:n] for t, n in zip(padded, length.tolist())]
+        shared["bulge"] = np.where(hits["bulge"] > 0, "DNA", "RNA").astype(object)
+        shared["bulge_size"] = np.abs(hits["bulge"].astype(np.int64))
+        shared["bulge_column"] = [str(c) for c in hits["bulge_column"].tolist()]
+        # a hit of text t is a row for every region of t
+        rep, region = _fan_out(hits["guide"].astype(np.int64), text_regions)
+        part = shared[rep]
+        part["region"] = region
+        # (a region's rows at one start and strand differ in their end: G + 1, G - 1, G + 2, G - 2)
+        order = np.lexsort((part["end"], part["strand"] == "-", part["start"], part["record_index"], part["region"]))
+        parts.append((fi, part[order], part["region"][order]))
+    return _sorted_parts(parts, GUIDE_BULGE_HIT)
+
+
+def write_guide_bulge_hits(path, rows, bulged, files):
+    """the TSV of the guide hits under --guide-hit-bulges: GUIDE_BULGE_HIT_HEADER, then guide_hits' rows (with -, 0, - in the
+    three bulge columns) and guide_bulge_hits' rows, merged by (region, file in the order of `files`, record_index, start,
+    '+' before '-', end)"""
+    both = np.empty(len(rows) + len(bulged), dtype=GUIDE_BULGE_HIT)
+    head = both[:len(rows)]
+    for name in GUIDE_HIT.names:
+        head[name] = rows[name]
+    head["bulge"] = "-"
+    head["bulge_size"] = 0
+    head["bulge_column"] = "-"
+    both[len(rows):] = bulged
+    index = {}
+    for i, f_ in enumerate(files):
+        index.setdefault(f_, i)
+    fidx = np.array([index[f_] for f_ in both["file"]], dtype=np.int64)
+    both = both[np.lexsort((both["end"], both["strand"] == "-", both["start"], both["record_index"], fidx, both["region"]))]
+    _write_tsv(path, GUIDE_BULGE_HIT_HEADER, both)
+
+
+# ----------------------------------------------------------------------------
+# the guide hits inside the designed primers' products (--out_assay_hits)
+# ----------------------------------------------------------------------------
+ASSAY_HIT_HEADER = ("region\tfile\trecord\trecord_index\tproduct_start\tproduct_end\tproduct_strand\tlength\tleft_mismatches\t"
+                    "right_mismatches\tleft_end_mismatches\tright_end_mismatches\tguide_start\tguide_end\tguide_strand\t"
+                    "guide_mismatches\tmismatch_columns\tpam5_match\tpam3_match\torientation\tsequence")
+# (start, end, strand: the product's -- the names _fill_shared writes)
+ASSAY_HIT = np.dtype([("region", "<u4"), ("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"), ("end", "<i8"),
+                      ("strand", "U1"), ("length", "<u4"), ("left_mismatches", "<u4"), ("right_mismatches", "<u4"),
+                      ("left_end_mismatches", "<u4"), ("right_end_mismatches", "<u4"), ("guide_start", "<i8"), ("guide_end", "<i8"),
+                      ("guide_strand", "U1"), ("guide_mismatches", "<u4"), ("mismatch_columns", "O"), ("pam5_match", "<u4"),
+                      ("pam3_match", "<u4"), ("orientation", "O"), ("sequence", "O")])
+
+
+def assay_links(pairs_regions, text_regions):
+    """The links of the assay join: pairs_regions[p] = the regions of primer pair p (primer_pairs), text_regions[t] = the
+    regions of guide text t (guide_texts), both in one numbering.  A link is a (p, t) that some region has both of; a
+    region with a pair and no guide, or a guide and no pair, makes none.  -> (the links as uint32 [n, 2], strictly
+    ascending, the regions of link i as a list of ascending lists)"""
+    pair_of = {int(r): p for p, rs in enumerate(pairs_regions) for r in rs}
+    by_link = {}
+    for t, rs in enumerate(text_regions):
+        for r in rs:
+            if int(r) in pair_of:
+                by_link.setdefault((pair_of[int(r)], t), []).append(int(r))
+    keys = sorted(by_link)
+    return np.array(keys, dtype=np.uint32).reshape(-1, 2), [sorted(by_link[k]) for k in keys]
+
+
+def assay_orientation(s_d, s_p, s_h):
+    """'design' when a hit on strand s_h of a product on strand s_p lies on the strand of the product that the design put
+    the guide on (s_d = the region's guide strand in the --out_guides record), 'reverse' otherwise"""
+    return "design" if (int(s_h) ^ int(s_p)) == int(s_d) else "reverse"
+
+
+def assay_hits_refusal(design_primers, out_guides, amp_size, primer_mismatches, max_product, guide_size, guide_mismatches, pam5, pam3,
+                       need_pam):
+    """why --out_assay_hits does not run with these options and figures (one line), or None: it needs --design-primers and
+    --out_guides, and takes what primer_products_refusal and guide_hits_refusal take"""
+    if not design_primers:
+        return "--out_assay_hits needs --design-primers (the primer pairs whose products it looks into)"
+    if not out_guides:
+        return "--out_assay_hits needs --out_guides (the guides it looks for inside the products)"
+    why = primer_products_refusal(amp_size, primer_mismatches, max_product)
+    if why is None:
+        why = guide_hits_refusal(guide_size, guide_mismatches, pam5, pam3, need_pam)
+    return why
+
+
+def assay_hits(left, right, pairs, pairs_regions, texts, text_regions, region_strand, ingroup_files, outgroup_files, guide_size,
+               primer_mismatches=1, max_product=1000, guide_mismatches=2, pam5="", pam3="", need_pam=False, omit_soft=False,
+               device=0):
+    """Where the assay of a region gives a signal: every product of the region's primer pair, in every input
+    genome, that carries a window within `guide_mismatches` substitutions of the region's protospacer between its two
+    primer sites.  left, right, pairs, pairs_regions = primer_pairs(...); texts, text_regions = guide_texts(...) with the
+    regions numbered alike; region_strand[r] = the guide strand of region r in the --out_guides record.  One pass over the
+    inputs on one device: the primer table, the guide-hit table and the links stand in ONE locate context, every file is
+    uploaded once, scanned by both passes (kr_primers_scan, kr_guide_hits_scan) and their lists are joined by position on
+    the device (kr_assay_join); only the assay hits and the windows' text come back.  A product is exactly a product of
+    primer_products, a hit exactly a hit of guide_hits (need_pam's selection included; bulged hits take no part).  Returns
+    an ASSAY_HIT array: start / end / strand / length and the four mismatch figures are the product's, guide_* and
+    mismatch_columns, pam5_match, pam3_match, sequence the hit's, orientation = assay_orientation.  An assay hit of a link
+    that several regions share is a row for each.  Rows in (region, file in command-line order, record_index, start, end,
+    '+' before '-' for the product, guide_start, '+' before '-' for the guide) order.  ValueError for figures the passes
+    do not take."""
+    why = primer_products_refusal(None, primer_mismatches, max_product)
+    if why is None:
+        why = guide_hits_refusal(guide_size, guide_mismatches, pam5, pam3, need_pam)
+    if why is None and len(texts) != len(text_regions):
+        why = f"assay_hits: {len(texts)} texts, the regions of {len(text_regions)}"
+    if why is None and len(pairs) != len(pairs_regions):
+        why = f"assay_hits: {len(pairs)} pairs, the regions of {len(pairs_regions)}"
+    if why is not None:
+        raise ValueError(why)
+    G = guide_size
+    t_bytes = _text_matrix(texts, G, "assay_hits")
+    pairs = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    _check_max_product(max_product, left, right, pairs)
+    links, link_regions = assay_links(pairs_regions, text_regions)
+    if len(links) == 0:
+        return np.empty(0, dtype=ASSAY_HIT)
+    files = list(ingroup_files) + list(outgroup_files)
+    link_key = (links[:, 0].astype(np.int64) << 32) | links[:, 1]
+    region_strand = np.asarray(region_strand, dtype=np.int64)
+
+    def table(eng):
+        eng.primers_table(list(left) + list(right), len(left), pairs, primer_mismatches, max_product)
+        eng.guide_hits_table(t_bytes, guide_mismatches, pam5, pam3, need_pam)
+        eng.assay_table(links)
+
+    parts = []
+    for eng, fi, path, rna, names in _scan_genomes(files, 0, G, 0, G, omit_soft, device, table):
+        eng.primers_scan(0)
+        eng.guide_hits_scan(0)
+        if eng.assay_join(0) == 0:
+            continue
+        hits = eng.assay_hits()
+        text = _rows_text(eng.guide_hit_windows(G)[hits["hit"].astype(np.int64)], G, rna)
+        seps, ids = names()
+        # an assay hit of link i is a row for every region of i
+        li = np.searchsorted(link_key, (hits["pair"].astype(np.int64) << 32) | hits["guide"])
+        rep, region = _fan_out(li, link_regions)
+        h = hits[rep]
+        part = np.empty(len(h), dtype=ASSAY_HIT)
+        _fill_shared(part, path, seps, ids, h["pos"].astype(np.int64), h["strand"])
+        part["region"] = region
+        _fill_product(part, h)
+        # (the window lies inside the product: on its record)
+        part["guide_start"] = part["start"] + (h["hit_pos"].astype(np.int64) - h["pos"].astype(np.int64))
+        part["guide_end"] = part["guide_start"] + G
+        part["guide_strand"] = np.where(h["hit_strand"] == 0, "+", "-")
+        _fill_guide_hit(part, h, "guide_mismatches", "hit_mismatches", "hit_pam")
+        design = (h["hit_strand"].astype(np.int64) ^ h["strand"]) == region_strand[part["region"].astype(np.int64)]
+        part["orientation"] = np.where(design, "design", "reverse").astype(object)
+        part["sequence"] = text[rep]
+        order = np.lexsort((part["guide_strand"] == "-", part["guide_start"], part["strand"] == "-", part["end"], part["start"],
+                            part["record_index"], part["region"]))
+        parts.append((fi, part[order], part["region"][order]))
+    return _sorted_parts(parts, ASSAY_HIT)
+
+
+def write_assay_hits(path, rows):
+    """the TSV of --out_assay_hits: ASSAY_HIT_HEADER, then a line per row"""
+    _write_tsv(path, ASSAY_HIT_HEADER, rows, ASSAY_HIT.names)

@@ -6,7 +6,7 @@ import re
 import numpy as np
 import pytest
 
-from krisp_amd import _native
+from krisp_amd import _native, reports
 from krisp_amd import krisp_fasta as KF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -121,7 +121,7 @@ def _stand_in(monkeypatch, G, B, raw, seen):
                 table(eng)
             yield eng, fi, path, path == "b.fa", lambda: (np.array([20], dtype=np.int64), ["r0", "r1"])
 
-    monkeypatch.setattr(KF, "_scan_genomes", scan)
+    monkeypatch.setattr(reports, "_scan_genomes", scan)
 
 
 def test_a_bulged_hit_of_a_shared_text_is_a_row_for_each_region_in_the_file_order(monkeypatch):

@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import pytest
 
-from krisp_amd import _native
+from krisp_amd import _native, reports
 from krisp_amd import krisp_fasta as KF
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -258,7 +258,7 @@ def test_a_hit_of_a_shared_text_is_a_row_for_each_region_in_the_file_order(monke
                 table(eng)
             yield eng, fi, path, path == "b.fa", lambda: (np.array([20], dtype=np.int64), ["r0", "r1"])
 
-    monkeypatch.setattr(KF, "_scan_genomes", scan)
+    monkeypatch.setattr(reports, "_scan_genomes", scan)
     rows = KF.guide_hits(texts, text_regions, ["a.fa"], ["b.fa"], G, mismatches=2, pam5="TTTV", need_pam=True)
     assert seen["table"] == (b"".join(texts), 2, "TTTV", "", True)
     got = [(int(r["region"]), r["file"], r["record"], int(r["record_index"]), int(r["start"]), int(r["end"]), r["strand"],

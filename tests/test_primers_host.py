@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-from krisp_amd import _native, amplicon, primers
+from krisp_amd import _native, amplicon, primers, reports
 from krisp_amd import krisp_fasta as KF
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -257,7 +257,7 @@ def test_the_rows_of_a_shared_pair_are_expanded_per_region(monkeypatch):
         for fi, path in enumerate(files):
             yield eng, fi, path, False, lambda: (np.array([99], dtype=np.int64), ["chr1", "chr2"])
 
-    monkeypatch.setattr(KF, "_scan_genomes", scan)
+    monkeypatch.setattr(reports, "_scan_genomes", scan)
     rows = KF.primer_products(groups, rec, None, ["a.fa", "b.fa"], [], 24, 20, 48, mismatches=2, max_product=400)
     assert seen == [([LEFT[2:14].encode(), RIGHT[2:17].encode()], 1, [[0, 0]], 2, 400)]
     assert rows.dtype == KF.PRODUCT

@@ -30,6 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from krisp_amd import krisp_fasta as KF  # noqa: E402
+from krisp_amd.reports import _scan_genomes  # noqa: E402
 from design_profile import write_genomes  # noqa: E402
 
 G, MP, MG, MAX_PRODUCT = 20, 1, 2, 1000
@@ -74,7 +75,7 @@ def kernel_part(paths):
         eng.guide_hits_table(t, MG, GUIDE["pam5"], GUIDE["pam3"], False)
         eng.assay_table(links)
 
-    for eng, fi, path, _rna, _names in KF._scan_genomes(paths, 0, G, 0, G, False, 0, tables):
+    for eng, fi, path, _rna, _names in _scan_genomes(paths, 0, G, 0, G, False, 0, tables):
         tp, n_products = _least(lambda: eng.primers_scan(0))
         th, n_hits = _least(lambda: eng.guide_hits_scan(0))
         tj, n_assay = _least(lambda: eng.assay_join(0))

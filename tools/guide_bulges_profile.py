@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from krisp_amd import krisp_fasta as KF  # noqa: E402
+from krisp_amd.reports import _scan_genomes  # noqa: E402
 from design_profile import write_genomes  # noqa: E402
 
 OPTS = dict(guide_size=28, pam5="TTTV", pam3="", gc=(30, 70), min_mismatches=0)
@@ -62,7 +63,7 @@ def kernel_part(paths, bulges):
         eng.guide_hits_table(t, M, OPTS["pam5"], OPTS["pam3"], False)
         eng.guide_bulges_table(t, M, bulges, OPTS["pam5"], OPTS["pam3"], False)
 
-    for eng, fi, path, rna, names in KF._scan_genomes(paths, 0, G, 0, G, False, 0, tables):
+    for eng, fi, path, rna, names in _scan_genomes(paths, 0, G, 0, G, False, 0, tables):
         s, n = _least(lambda: eng._check(eng.lib.kr_guide_hits_scan(eng.ctx, 0), "kr_guide_hits_scan"))
         res["guide_hits_scan_s"] += s
         res["guide_hits"] += int(n)

@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 
 from krisp_amd import codec, synth  # noqa: E402
 from krisp_amd import krisp_fasta as KF  # noqa: E402
+from krisp_amd.reports import _group_flanks, _scan_genomes  # noqa: E402
 
 DESIGN = ["--primer_size", "18", "24", "--amp_size", "70", "100"]
 
@@ -88,7 +89,7 @@ def scan_part(paths):
     rows, _, _, _ = KF.design_templates(groups, ingroup)
     left, right, pairs, regions = KF.primer_pairs(rows, records)
     Le, De, Re = codec.effective_geometry(L, k - L - R, R)
-    flanks = KF._group_flanks(groups, Le, Re)
+    flanks = _group_flanks(groups, Le, Re)
     fl, li = np.unique(flanks[:, :Le], axis=0, return_inverse=True)
     fr, ri = np.unique(flanks[:, Le:], axis=0, return_inverse=True)
     fpairs = np.stack([li.ravel(), ri.ravel()], axis=1).astype(np.uint32)
@@ -100,7 +101,7 @@ def scan_part(paths):
         eng.primers_table(left + right, len(left), pairs, M, mp)
         eng.products_table(fl, fr, fpairs, M, mp)
 
-    for eng, fi, path, _rna, _names in KF._scan_genomes(paths, Le, De, Re, k, False, 0, tables):
+    for eng, fi, path, _rna, _names in _scan_genomes(paths, Le, De, Re, k, False, 0, tables):
         tp, hp = _timed(lambda: eng.primer_products(0))
         nsp = len(eng.primer_sites())
         tf, hf = _timed(lambda: eng.products(0))
