@@ -487,6 +487,15 @@ int64_t kr_guides_run(kr_ctx*, const uint8_t* rows, const uint64_t* row_off, con
                       int L, int D);
 /* the records of the latest run, one per region in the order given (KR_ERR_STATE before a run) */
 int64_t kr_guides_fetch(kr_ctx*, kr_guide_record* out, size_t cap);
+/* the shortlist of krisp_fasta --guide-candidates: as kr_guides_run -- the same arguments, checks and batches --
+ * for the `top` best candidates of every region in the order of the definition, 1 <= top <= 8 (KR_ERR_PARAM otherwise), on
+ * the device in k_guides_top.  Returns the number of filled slots.  kr_guides_fetch_top gives nregions * top records,
+ * region-major: slot j of a region is its candidate of rank j + 1, and equals kr_guides_run's record for j = 0; a slot
+ * beyond the region's candidates is zero but `candidates`, which in every slot is the region's full count.  A state of its
+ * own: kr_guides_fetch is not satisfied by a top run, nor kr_guides_fetch_top by kr_guides_run (KR_ERR_STATE). */
+int64_t kr_guides_run_top(kr_ctx*, const uint8_t* rows, const uint64_t* row_off, const uint32_t* bounds, uint64_t nregions, int K,
+                          int L, int D, int top);
+int64_t kr_guides_fetch_top(kr_ctx*, kr_guide_record* out, size_t cap);
 
 /* ---- the picked guides searched in every genome (krisp_fasta --out_guide_hits) -----------------------------------------
  * No seam in the reference.  The specificity pass of the guides: for every genome, every window (the locate pass's window
@@ -523,6 +532,12 @@ int64_t kr_guide_hits_fetch(kr_ctx*, kr_guide_hit* out, size_t cap);
  * reverse complement for strand 1 -- the window as the guide's strand reads it.  Returns the number of rows; rows == NULL:
  * size query */
 int64_t kr_guide_hits_windows(kr_ctx*, uint8_t* rows, size_t cap_bytes);
+/* the hits of the latest kr_guide_hits_scan (after need_pam's selection) counted on the device, for a caller that wants the
+ * counts and not the hits: out[4 * guide + mismatches] = the number of such hits, 4 * nguides counters (a scan holds fewer
+ * than 2^32 hits).  Returns 4 * nguides.  The list is only read: the fetch, the windows and kr_assay_join give the same
+ * bytes after it as before it.  No guides or no hits: zeros without a launch.  KR_ERR_STATE before a scan or after a new
+ * table; KR_ERR_CAPACITY for cap < 4 * nguides. */
+int64_t kr_guide_hits_tally(kr_ctx*, uint32_t* out, size_t cap);
 
 /* ---- guide hits with a bulge: in the locate context of kr_guide_hits_*, with a state of its own (a table and
  * a scan of either pass do not disturb the other's).  A bulged hit of size b is a window of G + b bases (a DNA bulge: b

@@ -139,10 +139,13 @@ SYMBOLS = [
     ("kr_guides_table", _c.c_int, [_P, _P]),
     ("kr_guides_run", _c.c_int64, [_P, _P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
     ("kr_guides_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_guides_run_top", _c.c_int64, [_P, _P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    ("kr_guides_fetch_top", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_hits_table", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_char_p, _c.c_char_p, _c.c_int]),
     ("kr_guide_hits_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_guide_hits_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_hits_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_guide_hits_tally", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_bulges_table", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_char_p, _c.c_char_p, _c.c_int]),
     ("kr_guide_bulges_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_guide_bulges_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
@@ -426,6 +429,7 @@ class Engine:
         if not self.ctx:
             raise KrispHipError("kr_create failed: " + self.lib.kr_last_error(None).decode())
         self.params = None
+        self._guide_hit_texts = 0
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -776,8 +780,10 @@ class Engine:
         """texts: uint8 [n, G] protospacers in A, C, G, T, in a locate context with L+D+R = G; pam5 / pam3: the motifs in
         IUPAC letters, read 5'->3' on the guide's strand -> slots of the seed table (kr_guide_hits_table)"""
         t = self._guide_texts(texts, "guide_hits_table")
-        return self._check(self.lib.kr_guide_hits_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches, _motif_bytes(pam5),
-                                                        _motif_bytes(pam3), 1 if need_pam else 0), "kr_guide_hits_table")
+        slots = self._check(self.lib.kr_guide_hits_table(self.ctx, _ptr(t) if t.size else None, len(t), mismatches, _motif_bytes(pam5),
+                                                         _motif_bytes(pam3), 1 if need_pam else 0), "kr_guide_hits_table")
+        self._guide_hit_texts = len(t)                # (guide_hits_tally's rows; a refused table leaves the earlier one)
+        return slots
 
     def guide_hits(self, gid):
         """GUIDE_HIT_RAW array of uploaded genome gid against the guides' table, in position order (kr_guide_hits_scan)"""
@@ -787,6 +793,13 @@ class Engine:
         """the latest guide_hits()'s windows as the guide's strand reads them, cut on the device: uint8 [nhits, G]
         (kr_guide_hits_windows)"""
         return self._sized_fetch("kr_guide_hits_windows", G)
+
+    def guide_hits_tally(self):
+        """the hits of the latest guide_hits() / guide_hits_scan() counted on the device: uint32 [nguides, 4], column m = the
+        guide's hits with m mismatches (kr_guide_hits_tally)"""
+        out = np.zeros((max(self._guide_hit_texts, 1), 4), dtype=np.uint32)
+        n = self._check(self.lib.kr_guide_hits_tally(self.ctx, _ptr(out), out.size), "kr_guide_hits_tally")
+        return out[:n // 4]
 
     def guide_bulges_table(self, texts, mismatches, bulges, pam5="", pam3="", need_pam=False):
         """as guide_hits_table, for the bulged search with bulges of 1 .. `bulges` bases (1 or 2): the seed table of the
@@ -912,22 +925,38 @@ class Engine:
             p.pam3[j] = m
         self._check(self.lib.kr_guides_table(self.ctx, ctypes.byref(p)), "kr_guides_table")
 
-    def guides(self, rows, row_off, bounds, L, D):
-        """rows: uint8 [n, K] (upper case, T for U), row_off: [regions + 1] counted in rows -- a region's first row is its
-        template, the others its outgroup rows --, bounds: [regions, 2] columns [lo, hi) -> GUIDE_RECORD array, one per
-        region (kr_guides_run, kr_guides_fetch)"""
+    def _guide_regions(self, rows, row_off, bounds, who):
+        """the arguments of guides() and guides_top() as the library reads them -> (rows, row_off, bounds, regions)"""
         rows = np.ascontiguousarray(rows, dtype=np.uint8)
         if rows.ndim != 2:
-            raise ValueError("guides: rows is a matrix, a row of K letters each")
+            raise ValueError(f"{who}: rows is a matrix, a row of K letters each")
         off = np.ascontiguousarray(row_off, dtype=np.uint64).ravel()
         bnd = np.ascontiguousarray(bounds, dtype=np.uint32).reshape(-1, 2)
         n = len(off) - 1
         if n < 0 or len(bnd) != n or (n and int(off[-1]) > len(rows)):
-            raise ValueError(f"guides: {len(off)} row offsets up to {int(off[-1]) if len(off) else 0}, {len(bnd)} bounds, {len(rows)} rows")
+            raise ValueError(f"{who}: {len(off)} row offsets up to {int(off[-1]) if len(off) else 0}, {len(bnd)} bounds, {len(rows)} rows")
+        return rows, off, bnd, n
+
+    def guides(self, rows, row_off, bounds, L, D):
+        """rows: uint8 [n, K] (upper case, T for U), row_off: [regions + 1] counted in rows -- a region's first row is its
+        template, the others its outgroup rows --, bounds: [regions, 2] columns [lo, hi) -> GUIDE_RECORD array, one per
+        region (kr_guides_run, kr_guides_fetch)"""
+        rows, off, bnd, n = self._guide_regions(rows, row_off, bounds, "guides")
         self._check(self.lib.kr_guides_run(self.ctx, _ptr(rows) if rows.size else None, _ptr(off), _ptr(bnd) if n else None, n,
                                            rows.shape[1], L, D), "kr_guides_run")
         out = np.empty(max(n, 1), dtype=GUIDE_RECORD)
         self._check(self.lib.kr_guides_fetch(self.ctx, _ptr(out), n), "kr_guides_fetch")
+        return out[:n]
+
+    def guides_top(self, rows, row_off, bounds, L, D, top):
+        """as guides(), for the `top` (1 .. 8) best candidates of every region -> GUIDE_RECORD [regions, top]: column j is the
+        candidate of rank j + 1, all zero but `candidates` where the region has fewer (kr_guides_run_top,
+        kr_guides_fetch_top)"""
+        rows, off, bnd, n = self._guide_regions(rows, row_off, bounds, "guides_top")
+        self._check(self.lib.kr_guides_run_top(self.ctx, _ptr(rows) if rows.size else None, _ptr(off), _ptr(bnd) if n else None, n,
+                                               rows.shape[1], L, D, top), "kr_guides_run_top")
+        out = np.empty((max(n, 1), top), dtype=GUIDE_RECORD)
+        self._check(self.lib.kr_guides_fetch_top(self.ctx, _ptr(out), n * top), "kr_guides_fetch_top")
         return out[:n]
 
     # ---- timing

@@ -292,7 +292,8 @@ struct kr_ctx {
         int gid = -1;                   // the genome of the latest kr_guide_hits_scan
         SeedTable seed;
         DevBuf pairs, hits, kept, rows; // pairs: the scan's list; kept: what need_pam leaves (it changes places with hits)
-        void bufs(Bufs& v) { seed.bufs(v); v.insert(v.end(), {&pairs, &hits, &kept, &rows}); }
+        DevBuf tally;                   // kr_guide_hits_tally's counters
+        void bufs(Bufs& v) { seed.bufs(v); v.insert(v.end(), {&pairs, &hits, &kept, &rows, &tally}); }
         void reset() { seed.slots = nguides = 0; nhits = -1; }
     } ghit;
     // the bulged guide-hit pass (kr_guide_bulges_*: h_guide_bulges.inc), in the same context: a state of its own beside ghit.
@@ -354,8 +355,10 @@ struct kr_ctx {
         bool on = false;
         kr_guide_params params{};
         int64_t nrec = -1;
-        DevBuf rows, off, bnd, rec;
+        DevBuf rows, off, bnd, rec;             // (a batch's: kr_guides_run and kr_guides_run_top take turns on them)
         std::vector<kr_guide_record> out;       // the records of the latest run, all batches
+        int64_t top_nrec = -1;                  // kr_guides_run_top's own: regions * top records, region-major
+        std::vector<kr_guide_record> top_out;
     } guides;
 };
 

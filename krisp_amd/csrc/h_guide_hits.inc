@@ -4,7 +4,7 @@
 // table's build, the two-pass driver and the fetches are h_scan.inc's.  The pass keeps a state of its own (kr_ctx::ghit):
 // a near-match table of the same context and this one do not disturb each other.  Beside the table it holds three lists
 // for the context's life, sized by the largest scan so far: the scan's pairs (16 bytes each), the hits (24) and, once
-// need_pam was on, the kept hits (24).
+// need_pam was on, the kept hits (24); and, once kr_guide_hits_tally was asked, 16 bytes of counters a guide.
 
 #define GHIT_MIN_SIZE 12            // protospacer lengths the pass takes (the guide pass's: kr_guides_table)
 #define GHIT_MAX_SIZE 40
@@ -166,4 +166,30 @@ int64_t kr_guide_hits_windows(kr_ctx* c, uint8_t* rows, size_t cap_bytes) {
     if ((rc = scan_ctx(c))) return rc;
     auto& gh = c->ghit;
     return scan_windows(c, gh.nhits, gh.gid, "kr_guide_hits_scan first", (u32)c->loc.k, gh.rows, rows, cap_bytes, scan_cut_k<kr_guide_hit>(c, gh));
+}
+
+// the hits of the latest scan counted per guide and distance (k_ghit_tally): out[4 guide + m], 4 nguides counters
+int64_t kr_guide_hits_tally(kr_ctx* c, uint32_t* out, size_t cap) {
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
+    auto& gh = c->ghit;
+    if (gh.nhits < 0) return fail(c, KR_ERR_STATE, "kr_guide_hits_scan first");
+    const u64 n = 4 * gh.nguides;                                  // (< 2^26: the table holds fewer than 2^24 guides)
+    if (n > cap) return fail(c, KR_ERR_CAPACITY, "kr_guide_hits_tally: tally buffer too small: %llu > %zu", (unsigned long long)n, cap);
+    if (!n) return 0;
+    if (!out) return fail(c, KR_ERR_PARAM, "kr_guide_hits_tally: null argument");
+    if (!gh.nhits) {
+        memset(out, 0, n * sizeof(u32));
+        return (int64_t)n;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, gh.tally, n * sizeof(u32)))) return rc;
+    HIPCHK(c, hipMemsetAsync(gh.tally.p, 0, n * sizeof(u32), c->stream));
+    const u64 nhits = (u64)gh.nhits;
+    hipLaunchKernelGGL(k_ghit_tally, dim3(scan_stride_grid(c, (nhits + 255) / 256)), dim3(256), 0, c->stream, (const kr_guide_hit*)gh.hits.p,
+                       nhits, (u32)gh.nguides, (u32*)gh.tally.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, gh.tally.p, n * sizeof(u32), hipMemcpyDeviceToHost));
+    return (int64_t)n;
 }

@@ -14,7 +14,10 @@
 // lanes, over the library's bound; hits are rare, so a second touch of each costs nothing.)
 //
 // With need_pam, k_ghit_keep keeps the hits whose motif bits are 3, in their order (count, k_loc_offsets, emit: the
-// scaffold's two passes over blocks of LOC_T hits).  No atomics anywhere: the same bytes on every run.
+// scaffold's two passes over blocks of LOC_T hits).  No atomics in the scan or the selection: the same bytes on every run.
+//
+// k_ghit_tally (--guide-candidates, DESIGN §22) counts the list per (guide, mismatches) for callers that want the counts and
+// not the hits: integer atomic adds, so its sums too are the same on every run.
 #include "ghit_step.inc"
 
 struct GhitMotifs {
@@ -61,4 +64,28 @@ __global__ __launch_bounds__(LOC_T) void k_ghit_keep(const kr_guide_hit* __restr
     const bool keep = i < nhits && hits[i].pam == 3;
     kr_guide_hit* o = out + scan_epilogue<EMIT>((u32)keep, scan, tl, cnt, off, nullptr);
     if (EMIT && keep) *o = hits[i];
+}
+
+// tally[4 guide + mismatches] += the hits of that guide at that distance; the list is only read.  A wavefront takes 64
+// neighbouring hits; a run of equal (guide, mismatches) among them -- a repeat sends most of a genome's hits to one guide --
+// is one add of its length by its first lane.  A hit that names no guide of the table or a distance above 3 (there is none
+// unless the scan is broken) is not counted: no add outside the 4 nguides counters
+__global__ __launch_bounds__(256) void k_ghit_tally(const kr_guide_hit* __restrict__ hits, u64 nhits, u32 nguides, u32* __restrict__ tally) {
+    const u32 lane = threadIdx.x & 63u;
+    // (the loop's bounds are the wavefront's: every lane of it takes every turn, the shuffle and the ballot are whole)
+    for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < nhits; base += (u64)gridDim.x * 256) {
+        const u64 i = base + lane;
+        u32 key = ~0u;
+        if (i < nhits) {
+            const kr_guide_hit h = hits[i];
+            if (h.guide < nguides && h.mismatches < 4u) key = 4u * h.guide + h.mismatches;
+        }
+        const u32 prev = (u32)__shfl_up((int)key, 1, 64);
+        const bool head = lane == 0 || prev != key;
+        const u64 heads = __ballot(head);
+        if (head && key != ~0u) {
+            const u64 later = lane == 63 ? 0ull : heads >> (lane + 1);      // the heads behind this one
+            atomicAdd(tally + key, later ? (u32)__ffsll((long long)later) : 64u - lane);
+        }
+    }
 }

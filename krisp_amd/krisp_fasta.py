@@ -35,9 +35,10 @@ from .reports import (                                                        # 
     PRODUCT_END, PRODUCT_HEADER, PRODUCT_MAX_MISMATCHES, PRODUCT_MIN_PRIMER, _GUIDE_COMPLEMENT, _check_max_product, _engine,
     _fan_out, _fill_guide_hit, _fill_product, _fill_shared, _group_flanks, _guide_rc, _mask_columns, _record_coords, _rows_text,
     _scan_genomes, _sorted_parts, _text_matrix, _write_tsv, assay_hits, assay_hits_refusal, assay_links, assay_orientation,
-    design_guides, design_primers, design_templates, guide_bulge_hits, guide_hits, guide_hits_refusal, guide_rows, guide_texts,
-    guides_refusal, locate_regions, motif_masks, near_matches, near_refusal, near_targets, predict_products, primer_pairs,
-    primer_products, primer_products_refusal, products_refusal, write_assay_hits, write_guide_bulge_hits, write_guide_hits,
+    design_guide_shortlist, design_guides, design_primers, design_templates, guide_bulge_hits, guide_candidates_refusal, guide_hits,
+    guide_hits_refusal, guide_rows, guide_tallies, guide_texts, guides_refusal, locate_regions, motif_masks, near_matches,
+    near_refusal, near_targets, pick_guides, predict_products, primer_pairs, primer_products, primer_products_refusal,
+    products_refusal, shortlist_texts, write_assay_hits, write_guide_bulge_hits, write_guide_candidates, write_guide_hits,
     write_guides, write_locations, write_near, write_products)
 
 def prettyTime(t):
@@ -1633,6 +1634,16 @@ def build_parser():
     p.add_argument("--guide-min-mismatches", type=int, default=None, metavar="INT",
                    help="columns in which the protospacer differs from EVERY outgroup sequence of its region at least:\n"
                         "0 .. --guide-size (default: 1)")
+    p.add_argument("--guide-candidates", type=int, default=None, metavar="INT",
+                   help="--out_guides picks a region's guide among its INT best candidates (1 .. 8, in the order above) by their\n"
+                        "off-targets: every candidate's protospacer is searched in every --outgroup genome, on both strands,\n"
+                        "within --guide-hit-mismatches substitutions (--guide-hits-need-pam applies), and the candidate with the\n"
+                        "fewest exact hits wins, then the fewest with 1 mismatch, and so on; ties go to the better candidate.  Every\n"
+                        "row gains the columns rank, shortlisted and outgroup_hits (the hits with 0, 1, ... mismatches).  Needs an\n"
+                        "--outgroup file; one more pass over the outgroup files.  (default: the best candidate, no search)")
+    p.add_argument("--out_guide_candidates", type=str, metavar="PATH",
+                   help="With --guide-candidates: also write every searched candidate of every region, as --out_guides writes the\n"
+                        "picked one, with the column picked (0/1), by region and rank")
     p.add_argument("--out_guide_hits", type=str, metavar="PATH",
                    help="Also search every genome for the guides --out_guides picked, and write every window within\n"
                         "--guide-hit-mismatches substitutions of a protospacer, on both strands, as a tab-separated file: region,\n"
@@ -1735,6 +1746,8 @@ _NEEDS = {
     "guide_hits": (("--guide-hit-mismatches", _GUIDE_HIT_OUTPUTS), ("--guide-hits-need-pam", _GUIDE_HIT_OUTPUTS),
                    ("--guide-hit-bulges", ("--out_guide_hits",))),
 }
+# ... or with this option, which the refusal does not name: --guide-candidates searches with the guide hits' two figures
+_ALSO_WITH = {"--guide-hit-mismatches": "--guide-candidates", "--guide-hits-need-pam": "--guide-candidates"}
 _PRIMER_OPTIONS = ("tm", "gc", "amp_size", "primer_size", "max_sec_tm", "gc_clamp", "max_end_gc")
 
 
@@ -1754,7 +1767,7 @@ def _check_options(args, parser):
 
     def needs(step):
         for opt, outputs in _NEEDS[step]:
-            if given(opt) and not any(given(out) for out in outputs):
+            if given(opt) and not any(given(out) for out in outputs) and not (opt in _ALSO_WITH and given(_ALSO_WITH[opt])):
                 _refuse(f"{opt} needs " + " or ".join(outputs))
 
     def fill(*names):
@@ -1815,6 +1828,11 @@ def _check_options(args, parser):
         check(assay_hits_refusal(args.design_primers, args.out_guides is not None, args.amp_size, args.primer_mismatches,
                                  args.max_product, args.guide_size, args.guide_hit_mismatches, args.pam5, args.pam3,
                                  args.guide_hits_need_pam))
+    check(guide_candidates_refusal(args.out_guides is not None, args.guide_candidates, args.outgroup,
+                                   args.out_guide_candidates is not None))
+    if args.guide_candidates is not None and args.out_guide_hits is None:
+        fill("guide_hit_mismatches")
+        check(guide_hits_refusal(args.guide_size, args.guide_hit_mismatches, args.pam5, args.pam3, args.guide_hits_need_pam))
     if args.primer3:
         from . import primers
         if not primers.available():
@@ -1908,10 +1926,25 @@ def _run_reports(args, groups, ingroup, device, records, templates):
         regions = np.cumsum(found) - 1
     else:
         templates = design_templates(groups, ingroup)
-    guides = design_guides(groups, ingroup, args.guide_size, args.pam5, args.pam3, tuple(args.guide_gc),
-                           args.guide_min_mismatches, bounds=bounds, device=device, templates=templates)
-    write_guides(args.out_guides, templates[0], guides, args.guide_size, len(args.pam5), len(args.pam3), regions=regions)
+    options = (args.guide_size, args.pam5, args.pam3, tuple(args.guide_gc), args.guide_min_mismatches)
+    lengths = dict(pam5_len=len(args.pam5), pam3_len=len(args.pam3), regions=regions)
     motifs = dict(pam5=args.pam5, pam3=args.pam3, need_pam=args.guide_hits_need_pam)
+    if args.guide_candidates is None:
+        guides = design_guides(groups, ingroup, *options, bounds=bounds, device=device, templates=templates)
+        write_guides(args.out_guides, templates[0], guides, args.guide_size, **lengths)
+    else:
+        M = args.guide_hit_mismatches
+        shortlist = design_guide_shortlist(groups, ingroup, *options, bounds=bounds, device=device, templates=templates,
+                                           top=args.guide_candidates)
+        texts, index = shortlist_texts(templates[0], shortlist, args.guide_size)
+        say(f"Searching the outgroup genomes for {len(texts):,} candidate guides with up to {M} mismatches ... ")
+        tallies = guide_tallies(texts, args.outgroup, args.guide_size, mismatches=M, **motifs, **where)
+        guides, ranks, picked = pick_guides(shortlist, index, tallies, M)
+        write_guides(args.out_guides, templates[0], guides, args.guide_size, **lengths, ranks=ranks,
+                     shortlisted=(index >= 0).sum(axis=1), outgroup_hits=picked[:, :M + 1])
+        if args.out_guide_candidates is not None:
+            write_guide_candidates(args.out_guide_candidates, templates[0], shortlist, index, tallies, ranks, args.guide_size, M,
+                                   **lengths)
     if args.out_guide_hits is not None:
         say(f"Searching every genome for the guides with up to {args.guide_hit_mismatches} mismatches ... ")
         texts, text_regions = guide_texts(templates[0], guides, args.guide_size, regions=regions)

@@ -1,8 +1,8 @@
 """The report passes of `krisp_fasta`: what runs after the diagnostic regions are found, on one device, one genome at a
 time -- where the regions lie (--out_locations), their near matches (--out_near), the products of their flanks
 (--out_products), a primer pair per region and its products (--design-primers, --out_primer_products), a guide per
-region and its hits (--out_guides, --out_guide_hits, --guide-hit-bulges) and the guide hits inside the primers' products
-(--out_assay_hits) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
+region, picked among its best candidates by their outgroup hits where asked (--out_guides, --guide-candidates), and its
+hits (--out_guide_hits, --guide-hit-bulges) and the guide hits inside the primers' products (--out_assay_hits) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
 command line and its callers reach the passes there."""
 import os
 
@@ -592,9 +592,15 @@ def design_guides(groups, ingroup_labels, guide_size=28, pam5="", pam3="", gc=(3
     `min_mismatches` columns; of those the one whose least number of differences to an outgroup row is greatest, then
     whose sum over the outgroup rows is greatest, then the best centred on the diagnostic stretch, '+' before '-', the
     leftmost.  bounds: [groups, 2] columns [lo, hi) that window and motifs must lie in (default: the whole template).
-    Every figure is an integer: no seed weights, no folding of the guide, no gapped matches, no off-target search.
+    Every figure is an integer: no seed weights, no folding of the guide, no gapped matches, no off-target search
+    (--guide-candidates weighs the best of these candidates by one: design_guide_shortlist, pick_guides).
     Returns a _native.GUIDE_RECORD array, one row per group (found = 0: no guide).  ValueError for figures the pass does
     not take (guides_refusal)."""
+    return _guide_pass(groups, ingroup_labels, guide_size, pam5, pam3, gc, min_mismatches, bounds, device, templates, None)
+
+
+def _guide_pass(groups, ingroup_labels, guide_size, pam5, pam3, gc, min_mismatches, bounds, device, templates, top):
+    """design_guides (top = None: a record per group) and design_guide_shortlist (`top` records per group) on the device"""
     from . import _native
     why = guides_refusal(None, guide_size, pam5, pam3, tuple(gc), min_mismatches)
     if why is not None:
@@ -602,7 +608,7 @@ def design_guides(groups, ingroup_labels, guide_size=28, pam5="", pam3="", gc=(3
     rows, off, L, D, R = guide_rows(groups, ingroup_labels, templates)
     n = len(off) - 1
     if n == 0:
-        return np.empty(0, dtype=_native.GUIDE_RECORD)
+        return np.empty(0 if top is None else (0, top), dtype=_native.GUIDE_RECORD)
     k = L + D + R
     if guide_size > k:
         raise ValueError(f"--guide-size must not exceed the amplicon length {k} (got {guide_size})")
@@ -610,34 +616,167 @@ def design_guides(groups, ingroup_labels, guide_size=28, pam5="", pam3="", gc=(3
         bounds = np.tile(np.array([0, k], dtype=np.uint32), (n, 1))
     with _engine(device) as eng:
         eng.guides_table(guide_size, motif_masks(pam5), motif_masks(pam3), tuple(gc), min_mismatches)
-        return eng.guides(rows, off, bounds, L, D)
+        return eng.guides(rows, off, bounds, L, D) if top is None else eng.guides_top(rows, off, bounds, L, D, top)
 
 
 def _guide_rc(text):
     return text[::-1].translate(_GUIDE_COMPLEMENT)
 
 
-def write_guides(path, templates, records, guide_size, pam5_len=0, pam3_len=0, regions=None):
+def _guide_line(template, r, guide_size, pam5_len, pam3_len, region):
+    """the eleven columns of GUIDE_HEADER for the record r (found = 1) of a region with this template row"""
+    from . import thermo
+    g, a, b = guide_size, pam5_len, pam3_len
+    t = bytes(template).decode("ascii")
+    p = int(r["start"])
+    if int(r["strand"]) == 0:
+        strand, proto, m5, m3 = "+", t[p:p + g], t[p - a:p], t[p + g:p + g + b]
+    else:
+        strand, proto, m5, m3 = "-", _guide_rc(t[p:p + g]), _guide_rc(t[p + g:p + g + a]), _guide_rc(t[p - b:p])
+    return (f"{region}\t{strand}\t{p}\t{p + g}\t{m5}\t{m3}\t{proto}\t{thermo.gc_percent(int(r['gc']), g)}\t"
+            f"{int(r['min_mismatches'])}\t{int(r['sum_mismatches'])}\t{int(r['candidates'])}")
+
+
+def _tally_text(tally):
+    return ",".join(str(int(x)) for x in tally)
+
+
+def write_guides(path, templates, records, guide_size, pam5_len=0, pam3_len=0, regions=None, ranks=None, shortlisted=None,
+                 outgroup_hits=None):
     """the TSV of --out_guides: GUIDE_HEADER, then a line per region with a guide.  templates: the regions' template rows
     (design_templates), records: theirs (design_guides, or any array with GUIDE_RECORD's fields), regions: the number each
     region is listed under (default: its index).  start / end = the window's template columns, 0-based and half-open;
-    pam5, pam3 and protospacer as read 5'->3' on the guide's strand"""
-    from . import thermo
-    g, a, b = guide_size, pam5_len, pam3_len
+    pam5, pam3 and protospacer as read 5'->3' on the guide's strand.  With --guide-candidates the three columns of
+    GUIDE_PICK_HEADER behind them, all three or none: ranks (pick_guides', 0-based; written 1-based), shortlisted (the
+    region's searched candidates) and outgroup_hits ([regions, M + 1] counts, written t0,...,tM)"""
+    picked = ranks is not None
+    if picked != (shortlisted is not None) or picked != (outgroup_hits is not None):
+        raise ValueError("write_guides: ranks, shortlisted and outgroup_hits come together")
     with open(path, "w") as f:
-        f.write(GUIDE_HEADER + "\n")
+        f.write(GUIDE_HEADER + (GUIDE_PICK_HEADER if picked else "") + "\n")
         for i, (row, r) in enumerate(zip(templates, records)):
             if not int(r["found"]):
                 continue
-            t = bytes(row).decode("ascii")
-            p = int(r["start"])
-            if int(r["strand"]) == 0:
-                strand, proto, m5, m3 = "+", t[p:p + g], t[p - a:p], t[p + g:p + g + b]
-            else:
-                strand, proto, m5, m3 = "-", _guide_rc(t[p:p + g]), _guide_rc(t[p + g:p + g + a]), _guide_rc(t[p - b:p])
+            line = _guide_line(row, r, guide_size, pam5_len, pam3_len, i if regions is None else int(regions[i]))
+            if picked:
+                line += f"\t{int(ranks[i]) + 1}\t{int(shortlisted[i])}\t{_tally_text(outgroup_hits[i])}"
+            f.write(line + "\n")
+
+
+# ----------------------------------------------------------------------------
+# the guide picked among a region's best candidates by its outgroup off-targets (--guide-candidates, DESIGN §22)
+# ----------------------------------------------------------------------------
+GUIDE_MAX_CANDIDATES = 8
+GUIDE_PICK_HEADER = "\trank\tshortlisted\toutgroup_hits"
+GUIDE_CANDIDATE_HEADER = GUIDE_HEADER + GUIDE_PICK_HEADER + "\tpicked"
+
+
+def guide_candidates_refusal(out_guides, candidates, outgroup_files, out_guide_candidates):
+    """why --guide-candidates / --out_guide_candidates are not taken (one line), or None.  out_guides, out_guide_candidates:
+    whether the outputs are asked for; candidates: the option's value or None"""
+    if candidates is None:
+        return "--out_guide_candidates needs --guide-candidates" if out_guide_candidates else None
+    if not out_guides:
+        return "--guide-candidates needs --out_guides (the guides it picks)"
+    if candidates < 1 or candidates > GUIDE_MAX_CANDIDATES:
+        return f"--guide-candidates must lie between 1 and {GUIDE_MAX_CANDIDATES} (got {candidates})"
+    if len(outgroup_files) == 0:
+        return "--guide-candidates needs an --outgroup file (the genomes its candidates are searched in)"
+    return None
+
+
+def design_guide_shortlist(groups, ingroup_labels, guide_size=28, pam5="", pam3="", gc=(30, 70), min_mismatches=1, bounds=None,
+                           device=0, templates=None, top=GUIDE_MAX_CANDIDATES):
+    """design_guides' candidates of every region in design_guides' order, the first `top` (1 .. 8) of them, on the device
+    (kr_guides_run_top).  Returns a _native.GUIDE_RECORD array [groups, top]: column j = the candidate of rank
+    j + 1, column 0 = design_guides' record; found = 0 where the region has fewer (`candidates` is the region's count in
+    every column).  ValueError for figures the pass does not take"""
+    if top < 1 or top > GUIDE_MAX_CANDIDATES:
+        raise ValueError(f"--guide-candidates must lie between 1 and {GUIDE_MAX_CANDIDATES} (got {top})")
+    return _guide_pass(groups, ingroup_labels, guide_size, pam5, pam3, gc, min_mismatches, bounds, device, templates, top)
+
+
+_COMPLEMENT_BYTES = np.arange(256, dtype=np.uint8)
+_COMPLEMENT_BYTES[[ord(x) for x in "ACGT"]] = [ord(x) for x in "TGCA"]
+
+
+def shortlist_texts(templates, shortlist, guide_size):
+    """The table of the shortlist's search: every filled slot's protospacer as read 5'->3' on its strand (as guide_texts:
+    template[start, start + guide_size), its reverse complement for strand 1), equal texts listed once, ordered by their
+    bytes.  -> (the distinct texts as bytes, int64 [regions, top]: the text of every slot, -1 for an empty one)"""
+    g = guide_size
+    index = np.full(shortlist.shape, -1, dtype=np.int64)
+    ri, si = np.nonzero(shortlist["found"])
+    if len(ri) == 0:
+        return [], index
+    t = np.ascontiguousarray(templates, dtype=np.uint8).reshape(len(shortlist), -1)
+    start = shortlist["start"][ri, si].astype(np.int64)
+    minus = shortlist["strand"][ri, si] != 0
+    # column c of a text: template column start + c on '+', the complement of column start + g - 1 - c on '-'
+    cols = np.where(minus[:, None], start[:, None] + (g - 1 - np.arange(g))[None, :], start[:, None] + np.arange(g)[None, :])
+    text = t[ri[:, None], cols]
+    text = np.where(minus[:, None], _COMPLEMENT_BYTES[text], text)
+    uniq, inverse = np.unique(text, axis=0, return_inverse=True)
+    index[ri, si] = np.asarray(inverse).ravel()
+    return [bytes(u) for u in uniq], index
+
+
+def guide_tallies(texts, outgroup_files, guide_size, mismatches=2, pam5="", pam3="", need_pam=False, omit_soft=False, device=0):
+    """How often every text (shortlist_texts) hits the outgroup genomes: the guide-hit search of guide_hits over
+    the outgroup files only, both strands, and per file the device's count of the hits by text and distance
+    (kr_guide_hits_tally) -- no hit and no window comes to the host.  Returns uint64 [texts, 4]: column m = the windows with
+    exactly m mismatches, summed over the files; the columns above `mismatches` are 0.  ValueError for figures the search
+    does not take (guide_hits_refusal)"""
+    why = guide_hits_refusal(guide_size, mismatches, pam5, pam3, need_pam)
+    if why is not None:
+        raise ValueError(why)
+    G = guide_size
+    total = np.zeros((len(texts), 4), dtype=np.uint64)
+    if len(texts) == 0:
+        return total
+    t_bytes = _text_matrix(texts, G, "guide_tallies")
+    for eng, _, _, _, _ in _scan_genomes(list(outgroup_files), 0, G, 0, G, omit_soft, device,
+                                         lambda eng: eng.guide_hits_table(t_bytes, mismatches, pam5, pam3, need_pam)):
+        if eng.guide_hits_scan(0):
+            total += eng.guide_hits_tally()
+    return total
+
+
+def pick_guides(shortlist, index, tallies, mismatches):
+    """The pick of --guide-candidates: per region the shortlisted candidate whose tally (t0, ..., tM), M = `mismatches`, is
+    lexicographically smallest, the lower rank where tallies tie.  shortlist: GUIDE_RECORD [regions, top]
+    (design_guide_shortlist), index: [regions, top] rows of `tallies` (shortlist_texts; -1: an empty slot), tallies:
+    uint64 [texts, 4] (guide_tallies; the columns above M are not looked at).  -> (the picked records, GUIDE_RECORD
+    [regions] -- a region without a candidate keeps its record of rank 1, found = 0 --, their 0-based ranks, their tallies
+    as uint64 [regions, 4] with zeros above M)"""
+    n, top = shortlist.shape
+    M = int(mismatches)
+    alive = index >= 0
+    t = np.zeros((n, top, 4), dtype=np.uint64)
+    t[alive, :M + 1] = np.asarray(tallies, dtype=np.uint64)[index[alive], :M + 1]
+    worst = np.uint64(np.iinfo(np.uint64).max)
+    for m in range(M + 1):
+        col = np.where(alive, t[:, :, m], worst)
+        alive &= col == col.min(axis=1, keepdims=True)
+    ranks = np.argmax(alive, axis=1)               # (the first slot still alive; 0 where the region has none)
+    rows = np.arange(n)
+    return shortlist[rows, ranks], ranks.astype(np.int64), t[rows, ranks]
+
+
+def write_guide_candidates(path, templates, shortlist, index, tallies, ranks, guide_size, mismatches, pam5_len=0, pam3_len=0,
+                           regions=None):
+    """the TSV of --out_guide_candidates: GUIDE_CANDIDATE_HEADER, then a line per shortlisted candidate -- write_guides'
+    columns with the candidate's own rank and tally, and picked = 1 for the region's pick (ranks: pick_guides') --, by
+    region, then rank"""
+    M = int(mismatches)
+    shortlisted = (index >= 0).sum(axis=1)
+    with open(path, "w") as f:
+        f.write(GUIDE_CANDIDATE_HEADER + "\n")
+        for i, (row, slots) in enumerate(zip(templates, shortlist)):
             region = i if regions is None else int(regions[i])
-            f.write(f"{region}\t{strand}\t{p}\t{p + g}\t{m5}\t{m3}\t{proto}\t{thermo.gc_percent(int(r['gc']), g)}\t"
-                    f"{int(r['min_mismatches'])}\t{int(r['sum_mismatches'])}\t{int(r['candidates'])}\n")
+            for j in range(int(shortlisted[i])):
+                f.write(_guide_line(row, slots[j], guide_size, pam5_len, pam3_len, region) +
+                        f"\t{j + 1}\t{int(shortlisted[i])}\t{_tally_text(tallies[index[i, j], :M + 1])}\t{int(ranks[i] == j)}\n")
 
 
 # ----------------------------------------------------------------------------
