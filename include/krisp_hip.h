@@ -733,6 +733,10 @@ enum { KR_OPT_SLICE_BASES = 1,       /* -1 automatic; 0..4: sort every genome in
        KR_OPT_JOIN2 = 13,            /* 1 (default; KR_JOIN2 in the environment): an intersection of two genomes, one of each side, with one
                                         diagnostic column and the filter on screens its keys in LDS and joins only the live ones
                                         (k_join2); 0: the n-way kernel as for every other call.  KR_JOIN2_GRID in the environment caps its grid (tests) */
+       KR_OPT_COARSE_ONE_STRAND = 14, /* 1 (default; KR_COARSE_ONE_STRAND in the environment): where one diagnostic column, `left` filling the
+                                        key's high word, L >= 5 and R < L allow it, kr_genome_partition writes the forward record of every
+                                        window only and kr_intersect asks each key both ways (the same candidates, records and counts);
+                                        0: both strands are partitioned */
        KR_OPT_WIDE_ORDERED = 6 };    /* wide path: 0 (default) flanks of >= 20 bases are numbered through minimizer buckets (look-ups
                                         of neighbouring windows share memory sectors): the same groups and hits, but `cand` no longer
                                         ascends with (left, right); 1: order-preserving ranks, groups in the reference's order */
@@ -799,6 +803,9 @@ int     kr_debug_place(kr_ctx*, double* out8);
  * [3] partitions that wrote into a pooled buffer, [4] searches run, [5] / [6] the fastest / slowest probe milliseconds among the
  * buffers held, [7] the option's value */
 int     kr_debug_coarse_pool(kr_ctx*, double* out8);
+/* KR_OPT_COARSE_ONE_STRAND's counters: out8[0] partitions that wrote one strand, [1] intersections that probed one-strand genomes,
+ * [2] / [3] the forward / reverse rounds of all of them, [4] / [5] of the latest, [6] the option's value, [7] 0 */
+int     kr_debug_coarse_strand(kr_ctx*, int64_t* out8);
 /* what the multi-GPU exchange has cost this context so far: out[0] host synchronisations, [1] point-to-point calls,
  * [2] collectives, [3] microseconds inside kr_cands_reduce / kr_cands_bcast, [4] kr_cands_reduce calls, [5] entries of the
  * agreed message size */

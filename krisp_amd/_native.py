@@ -53,6 +53,7 @@ OPT_LAZY_ORDER = 10
 OPT_COARSE_REST = 11
 OPT_COARSE_POOL = 12
 OPT_JOIN2 = 13
+OPT_COARSE_ONE_STRAND = 14
 ERR_KEY, ERR_HOST = -5, -6
 STRANDS_BOTH, STRANDS_FORWARD, STRANDS_CANONICAL = 0, 1, 2
 STAGES = ["pack", "hist8", "reduce8", "scatter1", "hist2", "scan2", "scatter2", "chunks", "localsort",
@@ -184,6 +185,7 @@ SYMBOLS = [
     ("kr_debug_comm", _c.c_int, [_P, _P]),
     ("kr_debug_place", _c.c_int, [_P, _P]),
     ("kr_debug_coarse_pool", _c.c_int, [_P, _P]),
+    ("kr_debug_coarse_strand", _c.c_int, [_P, _P]),
     ("kr_debug_comm_probe", _c.c_int, [_P, _c.c_size_t, _c.c_int, _P]),
     ("kr_debug_cands_selfexchange", _c.c_int64, [_P, _c.c_int]),
     ("kr_debug_info", _c.c_int, [_P, _P]),
@@ -1042,6 +1044,14 @@ class Engine:
         self._check(self.lib.kr_debug_place(self.ctx, _ptr(o)), "kr_debug_place")
         return dict(candidates=int(o[0]), taken=int(o[1]), fastest_ms=[round(float(x), 4) for x in o[2:6]],
                     median_ms=round(float(o[6]), 4), slowest_ms=round(float(o[7]), 4))
+
+    def debug_coarse_strand(self):
+        """KR_OPT_COARSE_ONE_STRAND's counters (kr_debug_coarse_strand): partitions that wrote one strand, intersections that
+        probed such genomes, their forward / reverse rounds in all and of the latest call, the option's value"""
+        o = np.zeros(8, dtype=np.int64)
+        self._check(self.lib.kr_debug_coarse_strand(self.ctx, _ptr(o)), "kr_debug_coarse_strand")
+        return dict(partitions=int(o[0]), calls=int(o[1]), rounds_forward=int(o[2]), rounds_reverse=int(o[3]),
+                    last_forward=int(o[4]), last_reverse=int(o[5]), on=int(o[6]))
 
     def debug_coarse_pool(self):
         """the pool of placed pass-1 targets of coarse genomes (kr_debug_coarse_pool)"""

@@ -31,6 +31,8 @@ struct Genome {
     bool coarse = false;     // kr_genome_partition: the sort stopped behind pass 1 -- sl[0].keys holds the keys in 256 buckets by their top byte,
                              // sl[0].off[0 .. 256] the buckets' bases, sl[0].off[2^b] the key count; `sorted` is false: whoever needs the fine
                              // buckets calls ensure_fine() first.  kr_intersect takes such a genome by k_coarse_probe (h_intersect.inc)
+    bool one_strand = false; // ... the forward record of every window only, in buckets by cs_digit (co_strand.inc): a key stands for two
+                             // records (sl[0].off[2^b] counts both), the probe asks it both ways
     DevBuf ckeys;            // ... out of this array when the genome holds one: a pass-1 target of the context's pool of PLACED
                              // buffers (coarse_pool_*); without one pass 1 writes sl[0].keys, which no placement search chose
     double ckeys_ms = 0;     // ... its probe time
@@ -151,6 +153,9 @@ struct kr_ctx {
     int coarse_rest = 1;        // KR_OPT_COARSE_REST / KR_COARSE_REST env: 1 = kr_genome_partition stops behind pass 1 where the context is
                                 // eligible; 0 = it is kr_genome_sort
     int64_t coarse_done = 0, coarse_promoted = 0;   // genomes kr_intersect took in the coarse state; coarse genomes sorted fine after all
+    int coarse_one = 1;         // KR_OPT_COARSE_ONE_STRAND / KR_COARSE_ONE_STRAND env: 1 = a coarse partition writes one strand where one_strand_form() holds
+    int64_t one_partitions = 0, one_calls = 0, one_rounds[2] = {0, 0}, one_last[2] = {0, 0};   // ... its counters (kr_debug_coarse_strand)
+    DevBuf co_ent;              // ... the candidates' entries by class, behind them the class counts, bounds and cursors (k_strand_*)
     int coarse_pool = 1;        // KR_OPT_COARSE_POOL / KR_COARSE_POOL env: 1 = coarse genomes that are partitioned again and again write
                                 // their pass 1 into placed buffers (coarse_pool_grow); 0 = always into their own key arrays
     struct PoolBuf { DevBuf buf; double ms; hipEvent_t ev; bool wait; };
@@ -538,7 +543,7 @@ static void reset_slices(kr_ctx* c, Genome& G) {
 }
 // what every new upload and every new sort makes of a genome's state
 static void genome_unsorted(Genome& G) {
-    G.sorted = G.finalized = G.ordered = G.coarse = G.hits_valid = false;
+    G.sorted = G.finalized = G.ordered = G.coarse = G.one_strand = G.hits_valid = false;
     G.count = -1;
 }
 
@@ -695,6 +700,8 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         c->coarse_rest = e17 ? atoi(e17) != 0 : 1;
         const char* e21 = getenv("KR_COARSE_POOL");
         c->coarse_pool = e21 ? atoi(e21) != 0 : 1;
+        const char* e26 = getenv("KR_COARSE_ONE_STRAND");
+        c->coarse_one = e26 ? atoi(e26) != 0 : 1;
         const char* e22 = getenv("KR_PLACE_MIN_BYTES");
         if (e22) c->place_min_bytes = (size_t)std::max(0ll, atoll(e22));
         const char* e18 = getenv("KR_COARSE_TCAP");
@@ -766,7 +773,7 @@ void kr_destroy(kr_ctx* c) {
                      &c->chunkpos, &c->flags, &c->blockcnt, &c->blockpos, &c->other, &c->records, &c->nrec, &c->fbdesc, &c->fbsegs,
                      &c->coltab, &c->collo, &c->colcnt, &c->colpos, &c->coltsum, &c->coltpos, &c->colfirst, &c->colfm, &c->isovf,
                      &c->bgz_in, &c->bgz_tab, &c->bgz_stat, &c->tx_scan, &c->tx_text, &c->tx_tile, &c->tx_tilepos, &c->tx_lines, &c->tx_ls, &c->tx_ll, &c->tx_op, &c->tx_outpos, &c->tx_state,
-                     &c->tx_tsum, &c->tx_tpos, &c->candP, &c->touchdesc, &c->touchovf, &c->co_state, &c->co_tab};
+                     &c->tx_tsum, &c->tx_tpos, &c->candP, &c->touchdesc, &c->touchovf, &c->co_state, &c->co_tab, &c->co_ent};
     for (DevBuf* b : all) release(c, *b);
     {
         kr_ctx::Bufs sb;                // the wide path's and the one-genome scans': every pass hands over its own
@@ -935,6 +942,10 @@ int kr_set_option(kr_ctx* c, int option, int64_t value) {
     case KR_OPT_COARSE_POOL:
         if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_COARSE_POOL: 0 or 1");
         c->coarse_pool = (int)value;
+        return KR_OK;
+    case KR_OPT_COARSE_ONE_STRAND:
+        if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_COARSE_ONE_STRAND: 0 or 1");
+        c->coarse_one = (int)value;
         return KR_OK;
     case KR_OPT_JOIN2:
         if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_JOIN2: 0 or 1");
@@ -1303,14 +1314,23 @@ static void launch_pack(kr_ctx* c, Genome& G, Lane& ln, hipStream_t st) {
 // generator reads dictionaries and caches from global memory inside the tile (data-dependent
 // loads): it keeps the first form of the kernel; packed windows take the pipelined one -- BIG
 // for the pass 0 of sliced genomes, whose output can exceed what a buffer descriptor spans.
+static bool p1_fast_on() {
+    static const bool on = [] { const char* e = getenv("KR_P1_FAST"); return e ? atoi(e) != 0 : true; }();
+    return on;
+}
+static bool p1_fast_form(const Geom& g) {
+    return p1_fast_on() && g.wmode == 0 && g.strands == 0 && g.rot == 0 && g.npc == 0 && (u32)((g.mR | g.mD) >> 32) == 0u;
+}
+// `one`: the forward record of every window only, by co_strand.inc's digit (a coarse genome, SortPlan.one)
 static void launch_scatter1(const Geom& g, hipStream_t st, const u64* codes, const u32* bad, u64 nwords,
-                            const u32* base1, const u64* base64, const u32* rowoff, u64* dst, u64 dst_keys) {
+                            const u32* base1, const u64* base64, const u32* rowoff, u64* dst, u64 dst_keys, bool one = false) {
     const bool big = base64 != nullptr;
     // both strands, no rotation, the fields that move inside the low word: the generator that shifts the word string once
     // per thread (p1_fast_keys; KR_P1_FAST=0: the general one, A/B and tests)
-    static const bool fast_on = [] { const char* e = getenv("KR_P1_FAST"); return e ? atoi(e) != 0 : true; }();
-    const bool fast = fast_on && g.wmode == 0 && g.strands == 0 && g.rot == 0 && g.npc == 0 && (u32)((g.mR | g.mD) >> 32) == 0u;
-    if (g.wmode && g.wmode != 1 && g.wcmode == 4) {
+    const bool fast = p1_fast_form(g);
+    if (one) {
+        hipLaunchKernelGGL((k_scatter1p<0, 0, 1, 1>), dim3(NWG), dim3(P1_T), 0, st, codes, bad, nwords, base1, base64, rowoff, dst, dst_keys, g);
+    } else if (g.wmode && g.wmode != 1 && g.wcmode == 4) {
         hipLaunchKernelGGL(k_scatter1l, dim3(NWG), dim3(P1_T), 0, st, base1, base64, rowoff, dst, g);
     } else if (g.wmode) {
         const auto kw = g.wmode == 1 ? k_scatter1w<1> : g.wcmode == 2 ? k_scatter1w<3> : k_scatter1w<2>;
@@ -1329,8 +1349,8 @@ static void launch_scatter2(hipStream_t st, const u64* src, u64* dst, const uint
     hipLaunchKernelGGL(k_scatter2<2 * P2_T>, dim3(ntmax), dim3(2 * P2_T), 0, st, src, dst, tiledesc, tilehist, cursor, b, shl, region_n);
 }
 
-static void launch_hist8(kr_ctx* c, Genome& G, Lane& ln, hipStream_t st, const Geom& g) {
-    const auto kh = g.wmode == 1 ? k_hist8w<1> : g.wmode ? (g.wcmode == 2 ? k_hist8w<3> : k_hist8w<2>) : g.strands ? k_hist8<2> : k_hist8<0>;
+static void launch_hist8(kr_ctx* c, Genome& G, Lane& ln, hipStream_t st, const Geom& g, bool one = false) {
+    const auto kh = one ? k_hist8<3> : g.wmode == 1 ? k_hist8w<1> : g.wmode ? (g.wcmode == 2 ? k_hist8w<3> : k_hist8w<2>) : g.strands ? k_hist8<2> : k_hist8<0>;
     hipLaunchKernelGGL(kh, dim3(NWG), dim3(P1_T), 0, st, (const u64*)ln.codes.p, (const u32*)ln.bad.p, G.nwords,
                        (u32*)ln.partial8.p, g);
 }
@@ -1546,6 +1566,7 @@ struct SortPlan {
     bool reuse_count;   // count_slices(G) has just run on this lane (single lane): the codes, the bad bits and the workgroup
                         // histograms of the absolute top byte (already prefix-summed by k_reduce8a) are still in the lane's scratch
     bool coarse;        // kr_genome_partition on an eligible context: the sort stops behind pass 1
+    bool one;           // ... and pass 1 writes the forward record of every window only (one_strand_form)
     bool lazy;          // ... or at the fine buckets: no LDS sort
     bool sliced, route2, fine16;
     bool cached_keys;   // the wide path's composite keys are read back from the genome's cache
@@ -1555,10 +1576,18 @@ struct SortPlan {
     int nsl, helper;    // lanes the genome's slices take turns on: the genome's own, and nsl - 1 from lane `helper` on
 };
 
+// A coarse genome's forward strand answers for both (co_strand.inc, k_coarse.inc) where the context is coarse_eligible and:
+// one diagnostic column; pass 1's FAST key path (`left` fills the key's high word); L >= 5 -- the digit's four positions
+// lie in `left` --; R < L -- so does window position R.  KR_OPT_COARSE_ONE_STRAND = 0: never.
+static bool one_strand_form(const kr_ctx* c) {
+    return c->coarse_one && c->g.D == 1 && p1_fast_form(c->g) && c->g.L >= 5 && c->g.R < c->g.L && c->g.sbits == 0;
+}
+
 static SortPlan sort_plan(const kr_ctx* c, const Genome& G, const Lane& ln, bool reuse_count, bool coarse) {
     SortPlan p{};
     p.reuse_count = reuse_count;
     p.coarse = coarse;
+    p.one = coarse && !reuse_count && one_strand_form(c);
     p.cached_keys = reuse_count && c->g.wmode == 2 && c->g.wcache;
     p.cached_mode = c->g.wlcnt ? 4 : 2;
     p.sliced = c->nslices > 1;
@@ -1749,7 +1778,7 @@ static void pass1_counted(kr_ctx* c, Genome& G, const SortPlan& p, Lane& ln, Lan
         hipLaunchKernelGGL(k_hist8k, dim3(NWG), dim3(P1_T), 0, ss, src, (u64)S.nmax, g.sbits, (u32*)ln.partial8.p);
     } else if (!p.reuse_count) {
         StageScope sc(c, KR_ST_HIST8, ss);
-        launch_hist8(c, G, ln, ss, g);
+        launch_hist8(c, G, ln, ss, g, p.one);
     }
     {
         StageScope sc(c, KR_ST_REDUCE8, ss);
@@ -1766,14 +1795,14 @@ static void pass1_counted(kr_ctx* c, Genome& G, const SortPlan& p, Lane& ln, Lan
                            (const u32*)ls.base1.p, (const u32*)ln.partial8.p, pass1_dst, (u32)S.nmax);
     else
         launch_scatter1(g, ss, (const u64*)ln.codes.p, (const u32*)ln.bad.p, G.nwords, (const u32*)ls.base1.p,
-                        (const u64*)nullptr, (const u32*)ln.partial8.p, pass1_dst, S.nmax);
+                        (const u64*)nullptr, (const u32*)ln.partial8.p, pass1_dst, S.nmax, p.one);
 }
 
 // The coarse exit: the buckets' bases leave the lane's scratch; the words finalize() reads: no oversized bucket, the key count.
-static void coarse_exit(kr_ctx* c, Lane& ls, Slice& S) {
+static void coarse_exit(kr_ctx* c, Lane& ls, Slice& S, bool one) {
     StageScope sc(c, KR_ST_REDUCE8, ls.stream);
     hipLaunchKernelGGL(k_coarse_keep, dim3(1), dim3(320), 0, ls.stream, (const u32*)ls.base1.p, (u32*)S.off.p, 1u << c->g.b,
-                       (u32*)S.ovf.p);
+                       (u32*)S.ovf.p, one ? 2u : 1u);
 }
 
 // Pass 2 of a slice, from the lane's pass-1 array into the slice's keys: by fine offsets counted from the codes
@@ -1881,7 +1910,7 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
         if (p.route2) pass1_route2(c, p, ln, ls, S, s, src, pass1_dst);
         else pass1_counted(c, G, p, ln, ls, S, s, src, pass1_dst);
         if (coarse) {
-            coarse_exit(c, ls, S);
+            coarse_exit(c, ls, S, p.one);
             continue;
         }
         if ((rc = pass2(c, G, p, ln, ls, S))) return rc;
@@ -1890,6 +1919,8 @@ static int genome_sort(kr_ctx* c, int id, bool reuse_count, bool coarse) {
     G.ordered = !p.lazy && !coarse;
     G.sorted = !coarse;   // enqueued; oversized buckets (if any) are resolved by finalize()
     G.coarse = coarse;
+    G.one_strand = p.one;
+    if (p.one) c->one_partitions++;
     return KR_OK;
 }
 

@@ -85,6 +85,12 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
         }
     }
     if (cg.empty()) return KR_COARSE_PASS;
+    // all coarse genomes of the call hold one strand (co_strand.inc): each key is asked both ways; none does: today's probe;
+    // a mix (the option changed between their partitions): they are sorted fine
+    size_t n_one = 0;
+    for (Genome* G : cg) n_one += G->one_strand;
+    if (n_one != 0 && n_one != cg.size()) return KR_COARSE_PASS;
+    const bool one = n_one != 0;
     const bool ok = apply_filter && fmode(c, apply_filter) == 1 && c->g.D == 1 && n <= CO_MAXG && has_in && has_out &&
                     c->nslices == 1 && !c->wide.on && !c->custom_layout;
     if (!ok) return KR_COARSE_PASS;
@@ -104,6 +110,9 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     if ((rc = ensure(c, c->co_state, (size_t)nC * 4))) return rc;
     if ((rc = ensure(c, c->co_tab, (size_t)(2 * 260 + 256 * CO_ROW) * 4))) return rc;
     if ((rc = cands_compact_room(c, nC))) return rc;
+    // one-strand form: two entries per candidate, then the class counts, bounds (+ 1) and cursors
+    const size_t ent_bytes = (size_t)2 * nC * sizeof(CoEnt);
+    if (one && (rc = ensure(c, c->co_ent, ent_bytes + (size_t)(3 * CS_CLS + 8) * 4))) return rc;
     for (Genome* G : cg) {
         if (G->hitcap < hitcap || !G->hits.p) {
             if ((rc = ensure(c, G->hits, (size_t)hitcap * 8 + 16))) return rc;
@@ -113,8 +122,11 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     }
     if (c->co_occ == 0) {
         int per = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_coarse_probe, CO_T, 0);
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_coarse_probe<0>, CO_T, 0);
         c->co_occ = (e == hipSuccess && per >= 1) ? per : 1;
+        // (one grid for both forms: the one-strand form holds the same LDS and is compiled for the same occupancy)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_coarse_probe<1>, CO_T, 0) == hipSuccess && per >= 1)
+            c->co_occ = std::min(c->co_occ, per);
     }
     const u32 grid = c->co_grid ? c->co_grid : (u32)(c->co_occ * c->ncu);
     if ((rc = join_lanes(c))) return rc;                // (the partitions ran on the sort lanes)
@@ -139,9 +151,24 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     {
         // one launch each for all coarse genomes of the call (k_coarse_tables also clears their hit counts)
         StageScope sc(c, KR_ST_INTERSECT, st);
-        hipLaunchKernelGGL(k_coarse_tables, dim3(1), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC, ca, c->co_tcap, cb, ust, rows);
-        hipLaunchKernelGGL(k_coarse_probe, dim3(grid), dim3(CO_T), 0, st, ca, (const u32*)cb, (const u32*)ust, (const u32*)rows,
-                           (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel);
+        if (one) {
+            const CoStrand S = cs_make(g.L, g.R);
+            CoEnt* ents = (CoEnt*)c->co_ent.p;
+            u32 *cnt = (u32*)((char*)c->co_ent.p + ent_bytes), *cls = cnt + CS_CLS, *cursor = cls + CS_CLS + 4;
+            const u32 cgrid = std::min<u32>((nC + CS_T - 1) / CS_T, (u32)c->ncu);
+            HIPCHK(c, hipMemsetAsync(cnt, 0, CS_CLS * 4, st));
+            hipLaunchKernelGGL(k_strand_count, dim3(cgrid), dim3(CS_T), 0, st, (const kr_cand*)c->candB.p, nC, S, cnt);
+            hipLaunchKernelGGL(k_strand_tables, dim3(1), dim3(CS_CLS), 0, st, (const u32*)cnt, ca, c->co_tcap, cls, cursor, ust, rows,
+                               c->mbox + 56);
+            hipLaunchKernelGGL(k_strand_fill, dim3(cgrid), dim3(CS_T), 0, st, (const kr_cand*)c->candB.p, nC, S, cursor, ents);
+            hipLaunchKernelGGL(k_coarse_probe<1>, dim3(grid), dim3(CO_T), 0, st, ca, (const u32*)cls, (const u32*)ust, (const u32*)rows,
+                               (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel, (const CoEnt*)ents, S);
+        } else {
+            hipLaunchKernelGGL(k_coarse_tables, dim3(1), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC, ca, c->co_tcap, cb, ust, rows);
+            hipLaunchKernelGGL(k_coarse_probe<0>, dim3(grid), dim3(CO_T), 0, st, ca, (const u32*)cb, (const u32*)ust, (const u32*)rows,
+                               (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel, (const CoEnt*)nullptr,
+                               CoStrand{});
+        }
     }
     for (Genome* G : cg)
         if (G->ckeys.p) G->ckeys_busy = st;             // (the probe is the last reader of a pooled buffer)
@@ -155,6 +182,13 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     for (Genome* G : cg) G->ckeys_busy = nullptr;       // (the host has waited: nothing is at the pooled buffers)
+    if (one) {
+        c->one_calls++;
+        for (int q = 0; q < 2; q++) {
+            c->one_last[q] = ((volatile u32*)c->mbox)[56 + q];
+            c->one_rounds[q] += c->one_last[q];
+        }
+    }
     for (size_t j = 0; j < cg.size(); j++)
         if (((volatile u32*)c->mbox)[32 + j] > hitcap) {
             // a hit list that overflowed (a genome that repeats the candidates' prefixes many times over): nothing is

@@ -289,6 +289,21 @@ int kr_debug_coarse_pool(kr_ctx* c, double* out8) {
     return KR_OK;
 }
 
+// KR_OPT_COARSE_ONE_STRAND (h_core.inc: one_strand_form; k_coarse.inc): out[0] partitions that wrote one strand, [1] intersections
+// that probed one-strand genomes, [2] / [3] the forward / reverse rounds of all of them, [4] / [5] of the latest, [6] the option
+int kr_debug_coarse_strand(kr_ctx* c, int64_t* o) {
+    if (!c || !o) return KR_ERR_PARAM;
+    o[0] = c->one_partitions;
+    o[1] = c->one_calls;
+    o[2] = c->one_rounds[0];
+    o[3] = c->one_rounds[1];
+    o[4] = c->one_last[0];
+    o[5] = c->one_last[1];
+    o[6] = c->coarse_one;
+    o[7] = 0;
+    return KR_OK;
+}
+
 int kr_debug_isect(kr_ctx* c, int64_t* o) {
     if (!c || !o) return KR_ERR_PARAM;
     o[0] = c->isect_ovf_items;

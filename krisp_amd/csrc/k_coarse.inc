@@ -75,20 +75,146 @@ __global__ __launch_bounds__(256) void k_coarse_tables(const kr_cand* __restrict
     if (t == 0) ust[256] = total;
 }
 
+// ---- one-strand form (co_strand.inc): pass 1 wrote the forward record of every window, in 256 buckets by cs_digit.  The
+// candidates a key of digit d can meet are two classes -- class 2 d: those whose prefix read forward shows d, class 2 d + 1:
+// those whose reverse complement does -- and a round of the probe is one reading of up to tcap candidates of one class:
+// its entries (pattern, candidate) against key & mask (pmask / mask_rc).  The three kernels below take k_coarse_tables'
+// place: count the classes, scan them (+ rows, units, cleared hit counts), fill the entry array.
+#define CS_CLS 512
+#define CS_T 1024               // threads of k_strand_count / k_strand_fill: one workgroup per CU at most -- every workgroup ends with
+                                // CS_CLS global atomics on the same CS_CLS words, and those run one after the other
+struct CoEnt { u64 pat; u32 ci, pad; };
+
+// h[c] += 1 for every active lane, where the lanes of a wave hold equal c in RUNS (the list ascends by prefix, so
+// neighbours share their forward class: 64 single adds to one LDS word would run one after the other): the first lane of
+// a run adds its length.  -> what the lane's own add would have returned.  Call with all 64 lanes.
+__device__ __forceinline__ u32 co_run_add(u32* h, u32 c, bool active) {
+    const u32 lane = threadIdx.x & 63u;
+    if (!active) c = 0xFFFFFFFFu;
+    const u32 prev = (u32)__shfl_up((int)c, 1);
+    const bool head = lane == 0 || prev != c;
+    const u64 hb = __builtin_amdgcn_ballot_w64(head);
+    const u32 leader = 63u - (u32)__clzll((long long)(hb & ((2ull << lane) - 1ull)));      // (bit 0 is set: lane 0 is a head)
+    const u64 above = (hb >> lane) >> 1;
+    const u32 len = above ? (u32)__builtin_ctzll(above) + 1u : 64u - lane;
+    u32 r0 = 0;
+    if (head && active) r0 = atomicAdd(&h[c], len);
+    return (u32)__shfl((int)r0, (int)leader) + (lane - leader);
+}
+
+// cnt[CS_CLS] (zeroed by the host) += the candidates of every class
+__global__ __launch_bounds__(CS_T) void k_strand_count(const kr_cand* __restrict__ cands, u32 n, CoStrand S, u32* __restrict__ cnt) {
+    __shared__ u32 h[CS_CLS];
+    if (threadIdx.x < CS_CLS) h[threadIdx.x] = 0;
+    __syncthreads();
+    for (u32 i0 = blockIdx.x * CS_T; i0 < n; i0 += gridDim.x * CS_T) {
+        const u32 i = i0 + threadIdx.x;
+        const bool on = i < n;
+        const u64 P = cands[on ? i : n - 1].prefix;
+        (void)co_run_add(h, 2 * cs_class_fwd(S, P), on);
+        if (on) atomicAdd(&h[2 * cs_class_rev(S, P) + 1], 1u);
+    }
+    __syncthreads();
+    for (u32 t = threadIdx.x; t < CS_CLS; t += CS_T)
+        if (h[t]) atomicAdd(&cnt[t], h[t]);
+}
+
+// cls[t] = entries in front of class t (cls[CS_CLS] = 2 n), cursor[] = the same, for k_strand_fill; rows[d] = the buckets of
+// digit d in every genome; ust[d] = units in front of digit d: co_byte_units over (forward rounds + reverse rounds) * tcap
+// candidates -- a decoded round below the forward rounds is a forward round.  Also clears the genomes' hit counts.
+__device__ __forceinline__ u32 co_rounds(u32 nc, u32 tcap) { return nc / tcap + (nc % tcap ? 1u : 0u); }
+__global__ __launch_bounds__(CS_CLS) void k_strand_tables(const u32* __restrict__ cnt, CoarseArgs A, u32 tcap, u32* __restrict__ cls,
+                                                          u32* __restrict__ cursor, u32* __restrict__ ust, u32* rows,
+                                                          u32* __restrict__ host_rounds) {
+    __shared__ u32 waves[17];
+    const u32 t = threadIdx.x;
+    u32 total;
+    const u32 ex = block_excl_scan(cnt[t], waves, total);
+    cls[t] = ex;
+    cursor[t] = ex;
+    if (t == 0) cls[CS_CLS] = total;
+    if (t < 4 * A.n) A.hits[t >> 2][t & 3u] = 0;
+    u32 units = 0, rf = 0, rr = 0;
+    if (t < 256) {
+        u32* row = rows + t * CO_ROW;
+        for (u32 j = 0; j < A.n; j++) {
+            row[2 * j] = A.off[j][t];
+            row[2 * j + 1] = A.off[j][t + 1];
+        }
+        rf = co_rounds(cnt[2 * t], tcap);
+        rr = co_rounds(cnt[2 * t + 1], tcap);
+        units = co_byte_units((rf + rr) * tcap, tcap, row, A.n);
+        if (co_row_chunks(row, A.n) == 0) rf = rr = 0;       // (a digit without keys: no round is run)
+    }
+    const u32 ux = block_excl_scan(units, waves, total);
+    if (t < 256) ust[t] = ux;
+    if (t == 0) ust[256] = total;
+    // the forward and the reverse rounds of the call, for the host's counters (kr_debug_coarse_strand)
+    (void)block_excl_scan(rf, waves, total);
+    if (t == 0) host_rounds[0] = total;
+    (void)block_excl_scan(rr, waves, total);
+    if (t == 0) host_rounds[1] = total;
+}
+
+// the entries into their classes: a workgroup counts its candidates' classes in LDS, takes its room in each class with one
+// atomic, and places its entries (their order inside a class is free: a round's table is a set)
+__global__ __launch_bounds__(CS_T) void k_strand_fill(const kr_cand* __restrict__ cands, u32 n, CoStrand S, u32* __restrict__ cursor,
+                                                     CoEnt* __restrict__ ents) {
+    __shared__ u32 h[CS_CLS], base[CS_CLS];
+    if (threadIdx.x < CS_CLS) h[threadIdx.x] = 0;
+    __syncthreads();
+    for (u32 i0 = blockIdx.x * CS_T; i0 < n; i0 += gridDim.x * CS_T) {
+        const u32 i = i0 + threadIdx.x;
+        const bool on = i < n;
+        const u64 P = cands[on ? i : n - 1].prefix;
+        (void)co_run_add(h, 2 * cs_class_fwd(S, P), on);
+        if (on) atomicAdd(&h[2 * cs_class_rev(S, P) + 1], 1u);
+    }
+    __syncthreads();
+    for (u32 t = threadIdx.x; t < CS_CLS; t += CS_T) {
+        base[t] = h[t] ? atomicAdd(&cursor[t], h[t]) : 0u;
+        h[t] = 0;
+    }
+    __syncthreads();
+    for (u32 i0 = blockIdx.x * CS_T; i0 < n; i0 += gridDim.x * CS_T) {
+        const u32 i = i0 + threadIdx.x;
+        const bool on = i < n;
+        const u64 P = cands[on ? i : n - 1].prefix;
+        const u32 cf = 2 * cs_class_fwd(S, P), cr = 2 * cs_class_rev(S, P) + 1;
+        const u32 rank = co_run_add(h, cf, on);
+        if (!on) continue;
+        CoEnt e;
+        e.ci = i;
+        e.pad = 0;
+        e.pat = P;
+        ents[base[cf] + rank] = e;
+        e.pat = cs_pattern_rev(S, P);
+        ents[base[cr] + atomicAdd(&h[cr], 1u)] = e;
+    }
+}
+
 // One key against the table of the round (linear probing from the hash's top bits; a slot's tag gates the look at the
 // candidate's full prefix): a key under a candidate's prefix joins the unit's hits in LDS (the excess of a unit with more
 // than CO_HB of them goes straight to the list) and ORs presence + diagnostic base into the candidate's state word
+// OS (one-strand form): slot -> entry c0 + idx of the round's slice, whose pattern is compared and whose candidate takes the
+// bits; in a reverse round (`rev`) the hit is the window's REVERSE record: its key goes to the list, its base to the state
+template <int OS>
 __device__ __forceinline__ void co_lookup(u64 key, u64 pmask, int LR, const u32* slots, u32 c0, const kr_cand* __restrict__ cands,
                                           u32* __restrict__ state, u32 orbits, u32 side_shift, u64* s_hit, u32* s_nhit,
-                                          u32* __restrict__ hits, u64* __restrict__ hitkeys, u32 hitcap) {
+                                          u32* __restrict__ hits, u64* __restrict__ hitkeys, u32 hitcap,
+                                          const CoEnt* __restrict__ ents, bool rev, const CoStrand& S) {
     const u64 pre = key & pmask;
     const u32 h = co_hash(pre);
     const u32 tag = h & 0x7FFFFu;
     u32 s = h >> (32 - CO_SLOT_LOG);
     for (u32 w = slots[s]; w != CO_EMPTY; w = slots[s]) {
         if ((w & 0x7FFFFu) == tag) {
-            const u32 ci = c0 + (w >> 19);
-            if (cands[ci].prefix == pre) {
+            u32 ci = c0 + (w >> 19);
+            if ((OS ? ents[ci].pat : cands[ci].prefix) == pre) {
+                if (OS) {
+                    ci = ents[ci].ci;
+                    if (rev) key = cs_rev_key(S, key);
+                }
                 const u32 at0 = atomicAdd(s_nhit, 1u);
                 if (at0 < CO_HB) s_hit[at0] = key;
                 else {
@@ -133,9 +259,14 @@ __device__ __forceinline__ void co_load(u32x4 (&v)[CO_UNROLL], const u64* __rest
 // lanes below it.  Phase 2 (per UNIT: its barriers and its dependent global reads would drain the prefetch) looks the
 // queued keys up, a thread per key, densely; a unit that overran the queue is read again and looked up in place.  A unit's hits gather
 // in LDS and take their room in the genome's list with ONE atomic per unit.
+//
+// OS: the one-strand form -- cb = the class bounds (k_strand_tables), a round = one reading of one class: its slice of the
+// entry array and its mask (both wave-uniform) stand where cands + c0 and pmask stand in the two-strand form.
+template <int OS>
 __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u32* __restrict__ cb, const u32* __restrict__ ust,
                                                        const u32* __restrict__ rows, const kr_cand* __restrict__ cands,
-                                                       u32* __restrict__ state, u32 tcap, u64 pmask, int LR) {
+                                                       u32* __restrict__ state, u32 tcap, u64 pmask0, int LR,
+                                                       const CoEnt* __restrict__ ents, CoStrand S) {
     __shared__ u32 slots[CO_SLOTS];
     __shared__ u32 bitmap[1u << (CO_BM_LOG - 5)];
     __shared__ u32 s_ust[257];
@@ -159,6 +290,8 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
     u64* __restrict__ hitkeys = nullptr;
     u32 hitcap = 0, orbits = 0, side_shift = 0;
     bool cold = true;                                    // no load of the iteration at hand has been issued
+    u64 pmask = pmask0;                                  // the mask of the round at hand (OS: pmask or mask_rc)
+    bool rev = false;                                    // OS: the round at hand is a reverse round
 
     // unit `un` of top byte t becomes the unit at hand; its round's table is built unless it stands
     auto adopt = [&](const CoUnit& un) {
@@ -179,11 +312,22 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
             for (u32 i = threadIdx.x; i < CO_SLOTS; i += CO_T) slots[i] = CO_EMPTY;
             for (u32 i = threadIdx.x; i < (1u << (CO_BM_LOG - 5)); i += CO_T) bitmap[i] = 0;
             __syncthreads();
-            const u32 cb0 = cb[t], cb1 = cb[t + 1];
-            c0 = cb0 + r * tcap;
+            u32 cb0 = cb[OS ? 2 * t : t], cb1 = cb[OS ? 2 * t + 1 : t + 1], rr = r;
+            if (OS) {
+                const u32 rf = CO_RFL(co_rounds(cb1 - cb0, tcap));
+                rev = r >= rf;
+                if (rev) {
+                    rr = r - rf;
+                    cb0 = cb1;
+                    cb1 = cb[2 * t + 2];
+                }
+                const u64 m = rev ? S.mask_rc : pmask0;
+                pmask = ((u64)CO_RFL((u32)(m >> 32)) << 32) | CO_RFL((u32)m);
+            }
+            c0 = cb0 + rr * tcap;
             const u32 c1 = cb1 - c0 > tcap ? c0 + tcap : cb1;
             for (u32 i = c0 + threadIdx.x; i < c1; i += CO_T) {
-                const u32 h = co_hash(cands[i].prefix);
+                const u32 h = co_hash(OS ? ents[i].pat : cands[i].prefix);
                 const u32 word = ((i - c0) << 19) | (h & 0x7FFFFu);
                 u32 s = h >> (32 - CO_SLOT_LOG);
                 while (atomicCAS(&slots[s], CO_EMPTY, word) != CO_EMPTY) s = (s + 1) & (CO_SLOTS - 1);
@@ -263,7 +407,8 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
         if (s_qn <= CO_QCAP) {
             const u32 qn = s_qn;
             for (u32 i = threadIdx.x; i < qn; i += CO_T)
-                co_lookup(s_q[i], pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap);
+                co_lookup<OS>(s_q[i], pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap,
+                              ents, rev, S);
         } else {
             // more keys passed the prefilter than the queue holds, and some were dropped (nothing of the unit has been
             // looked up yet): the queue is discarded and the unit's keys are read again and looked up in place -- exact
@@ -276,7 +421,8 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
                     const u64 key = e ? ((u64)w.w << 32 | w.z) : ((u64)w.y << 32 | w.x);
                     const u32 h = co_hash(key & pmask);
                     if (p + e >= k0 && p + e < k1 && ((bitmap[h >> (37 - CO_BM_LOG)] >> ((h >> (32 - CO_BM_LOG)) & 31u)) & 1u))
-                        co_lookup(key, pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap);
+                        co_lookup<OS>(key, pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap,
+                                      ents, rev, S);
                 }
             }
         }
@@ -387,9 +533,10 @@ __global__ __launch_bounds__(256) void k_coarse_rowsort(u32 npairs, u32 n, const
 
 // kr_genome_partition: the top-byte buckets' bases out of the lane's scratch into the genome's own offsets array
 // (off[0 .. 256]), and the two words finalize() reads of a slice -- off[nb] = the key count, ovf[0] = no oversized bucket
-__global__ void k_coarse_keep(const u32* __restrict__ base1, u32* __restrict__ off, u32 nb, u32* __restrict__ ovf) {
+// (per_key: records a key of the array stands for -- 2 where pass 1 wrote one strand for both, co_strand.inc)
+__global__ void k_coarse_keep(const u32* __restrict__ base1, u32* __restrict__ off, u32 nb, u32* __restrict__ ovf, u32 per_key) {
     const u32 t = threadIdx.x;
     if (t <= 256) off[t] = base1[t];
-    else if (t == 257) off[nb] = base1[256];
+    else if (t == 257) off[nb] = per_key * base1[256];
     else if (t == 258) ovf[0] = 0;
 }

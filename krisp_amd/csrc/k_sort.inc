@@ -137,6 +137,19 @@ __device__ __forceinline__ void hist8_word(std::integer_sequence<int, J...>, con
     (hist8_window<J>(sf, sr, invalid, g, lhist), ...);
 }
 
+// one strand (WIDE = 3; co_strand.inc): the forward key alone, counted by the digit both of the window's records share --
+// the key's high word is the window's first 16 bases (`left` fills it: the FAST geometries)
+template <int J>
+__device__ __forceinline__ void hist8_window_fwd(const u32 (&sf)[5], u32 invalid, const CoStrand& S, u32* lhist) {
+    if ((invalid >> (31 - J)) & 1u) return;
+    atomicAdd(&lhist[cs_digit(S, (u64)bits128<2 * J>(sf) << 32)], 1u);
+}
+template <int... J>
+__device__ __forceinline__ void hist8_word_fwd(std::integer_sequence<int, J...>, const u32 (&sf)[5], u32 invalid,
+                                               const CoStrand& S, u32* lhist) {
+    (hist8_window_fwd<J>(sf, invalid, S, lhist), ...);
+}
+
 template <int WIDE>
 __global__ __launch_bounds__(P1_T) void k_hist8(const u64* __restrict__ codes, const u32* __restrict__ bad,
                                                u64 nwords, u32* __restrict__ partial8, Geom g) {
@@ -151,6 +164,12 @@ __global__ __launch_bounds__(P1_T) void k_hist8(const u64* __restrict__ codes, c
         u32 b0 = bad[w], b1 = bad[w + 1];
         if (b0 == 0xFFFFFFFFu) continue;
         u64 c0 = codes[w], c1 = codes[w + 1];
+        if (WIDE == 3) {
+            const CoStrand S = cs_make(g.L, g.R);
+            const u32 sf[5] = {(u32)(c0 >> 32), (u32)c0, (u32)(c1 >> 32), (u32)c1, 0u};
+            hist8_word_fwd(std::make_integer_sequence<int, 32>{}, sf, word_invalid(b0, b1, g.k), S, lhist);
+            continue;
+        }
         if (WIDE == 2) {
 #pragma unroll 4
             for (int j = 0; j < 32; j++) {

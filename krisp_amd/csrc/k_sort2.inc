@@ -289,8 +289,9 @@ __global__ __launch_bounds__(LS_THREADS, LS2_OCC) void k_localsort2(u64* keys, c
 // ----------------------------------------------------------------------------
 struct P1Regs { u32x4 c; u32x2 b; };
 
+template <int TPW = P1_TPW>
 __device__ __forceinline__ void p1_issue(P1Regs& r, bufrsrc cs, bufrsrc bs, u64 wt) {
-    const u32 w = (u32)wt + opaque_tid() / P1_TPW;
+    const u32 w = (u32)wt + opaque_tid() / TPW;
     r.c = __builtin_amdgcn_raw_buffer_load_b128(cs, w * 8, 0, 0);       // codes[w], codes[w + 1]
     r.b = __builtin_amdgcn_raw_buffer_load_b64(bs, w * 4, 0, 0);        // bad[w], bad[w + 1]
     __builtin_amdgcn_sched_barrier(0);
@@ -338,14 +339,39 @@ __device__ __forceinline__ void p1_fast_keys(u64 c0, u64 c1, u32 b0, u32 b1, con
     }
 }
 
-template <int WIDE, int BIG, int FAST = 0>
+// ONE (a coarse genome whose forward strand answers for both: co_strand.inc): the forward keys alone, 32 windows per pair
+// of threads, so a tile is twice the code words and still P1_STAGE keys
+#define P1_ONE_TPW (P1_TPW / 2)
+#define P1_ONE_PPT (2 * P1_PPT)
+__device__ __forceinline__ void p1_fast_keys_fwd(u64 c0, u64 c1, u32 b0, u32 b1, const Geom& g, u64 (&key)[P1_KPT], u32& vm) {
+    static_assert(P1_ONE_PPT <= 16 && P1_ONE_PPT == P1_KPT, "a thread's windows must start inside one dword of the shifted string");
+    const u32 q = opaque_tid() % P1_ONE_TPW;
+    const int cs = 2 * P1_ONE_PPT * (int)q;                  // bit offset of the thread's first window in c0:c1 (< 64)
+    const u64 f01 = cs ? (c0 << cs) | (c1 >> (64 - cs)) : c0;
+    const u32 f0 = (u32)(f01 >> 32), f1 = (u32)f01, f2 = (u32)((c1 << cs) >> 32);
+    const u64 B = (((u64)b0 << 32) | b1) << (P1_ONE_PPT * q);
+    const u32 bh = (u32)(B >> 32), bl = (u32)B;
+    const u32 mLh = (u32)(g.mL >> 32), mLl = (u32)g.mL, mRl = (u32)g.mR, mDl = (u32)g.mD;
+    const u32 sR = (u32)g.sR & 31u, sD = (u32)g.sD & 31u, vsh = 32u - (u32)g.k;
+#pragma unroll
+    for (int jj = 0; jj < P1_ONE_PPT; jj++) {
+        const u32 bm = __funnelshift_l(bl, bh, jj);
+        const u32 fh = __funnelshift_l(f1, f0, 2 * jj), fl = __funnelshift_l(f2, f1, 2 * jj);
+        key[jj] = ((u64)(fh & mLh) << 32) | ((fl & mLl) | ((fl << sR) & mRl) | ((fl >> sD) & mDl));
+        vm |= (bm >> vsh) == 0u ? 1u << jj : 0u;
+    }
+}
+
+template <int WIDE, int BIG, int FAST = 0, int ONE = 0>
 __device__ __forceinline__ void p1_tile(const P1Regs& R, u64 wt, u64 w1, const Geom& g, bufrsrc ds, u64* dst,
                                         u64 sink, u64* stage, u64* cur, u32* cnt, u32* cnt_next, u64* delta,
                                         u32* waves) {
     const u32 tid = opaque_tid();
     const int dsh = BIG ? 64 - P0_DIGIT_BITS(g) : 56;
-    const u64 w = wt + tid / P1_TPW;
+    const u64 w = wt + tid / (ONE ? P1_ONE_TPW : P1_TPW);
     const int j0 = (tid % P1_TPW) * P1_PPT;
+    const CoStrand S = cs_make(ONE ? g.L : 5, ONE ? g.R : 0);       // (ONE: the digit is co_strand.inc's; else unused)
+    auto digit = [&](u64 k) { return ONE ? cs_digit(S, k) : (u32)(k >> dsh); };
     u64 key[P1_KPT];
     u32 rp[P1_KPT / 2];         // a key's arrival number inside its digit: 16 bits, two per register
     u32 vm = 0;
@@ -355,7 +381,9 @@ __device__ __forceinline__ void p1_tile(const P1Regs& R, u64 wt, u64 w1, const G
         const u32 b0 = R.b.x, b1 = R.b.y;
         if (b0 != 0xFFFFFFFFu) {
             const u64 c0 = pair_lo(R.c), c1 = pair_hi(R.c);
-            if (FAST) {
+            if (ONE) {
+                p1_fast_keys_fwd(c0, c1, b0, b1, g, key, vm);
+            } else if (FAST) {
                 p1_fast_keys(c0, c1, b0, b1, g, key, vm);
             } else if (WIDE == 2) {
 #pragma unroll
@@ -383,7 +411,7 @@ __device__ __forceinline__ void p1_tile(const P1Regs& R, u64 wt, u64 w1, const G
     }
 #pragma unroll
     for (int q = 0; q < P1_KPT; q++)
-        if ((vm >> q) & 1) rp[q >> 1] |= atomicAdd(&cnt[(u32)(key[q] >> dsh)], 1u) << (16 * (q & 1));
+        if ((vm >> q) & 1) rp[q >> 1] |= atomicAdd(&cnt[digit(key[q])], 1u) << (16 * (q & 1));
     __syncthreads();
     const u32 c = tid < 256 ? cnt[tid] : 0;
     u32 total;
@@ -397,19 +425,19 @@ __device__ __forceinline__ void p1_tile(const P1Regs& R, u64 wt, u64 w1, const G
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < P1_KPT; q++)
-        if ((vm >> q) & 1) stage[cnt[(u32)(key[q] >> dsh)] + ((rp[q >> 1] >> (16 * (q & 1))) & 0xFFFFu)] = key[q];
+        if ((vm >> q) & 1) stage[cnt[digit(key[q])] + ((rp[q >> 1] >> (16 * (q & 1))) & 0xFFFFu)] = key[q];
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < P1_KPT; q++) {
         const u32 p = q * P1_T + tid;
         const u64 k2 = stage[p];
-        const u64 o = p + delta[(u32)(k2 >> dsh)];
+        const u64 o = p + delta[digit(k2)];
         if (BIG) dst[p < total ? o : sink] = k2;
         else buf_store_u64<KR_P1_ST_AUX>(k2, ds, p < total ? (u32)o * 8 : BUF_OOB);
     }
 }
 
-template <int WIDE, int BIG, int FAST = 0>
+template <int WIDE, int BIG, int FAST = 0, int ONE = 0>
 __global__ __launch_bounds__(P1_T, P1_OCC) void k_scatter1p(const u64* __restrict__ codes, const u32* __restrict__ bad,
                                                             u64 nwords, const u32* __restrict__ base1,
                                                             const u64* __restrict__ base64,
@@ -444,19 +472,21 @@ __global__ __launch_bounds__(P1_T, P1_OCC) void k_scatter1p(const u64* __restric
     const bufrsrc bs = make_rsrc(bad, (u32)(nwords + PAD_WORDS) * 4);
     const bufrsrc ds = make_rsrc(dst, BIG ? 0u : (u32)dst_keys * 8);
     const u64 sink = dst_keys + 1;            // (the arrays have two keys of slack)
+    constexpr int TPW = ONE ? P1_ONE_TPW : P1_TPW;
+    constexpr u64 WORDS = P1_T / TPW;         // code words of a tile
     P1Regs A, B;
-    p1_issue(A, cs, bs, w0);
+    p1_issue<TPW>(A, cs, bs, w0);
     {   // equalise the memory-operation history of the loop's two entries (see k_localsort2)
         const bufrsrc none = make_rsrc(dst, 0);
 #pragma unroll
         for (int q = 0; q < P1_KPT; q++) buf_store_u64(0, none, 64u * q);     // (distinct, non-adjacent offsets: else they are merged or widened)
     }
     __syncthreads();
-    for (u64 wt = w0; wt < w1; wt += 2 * P1_WORDS) {
-        p1_issue(B, cs, bs, wt + P1_WORDS);
-        p1_tile<WIDE, BIG, FAST>(A, wt, w1, g, ds, dst, sink, stage, cur, cnt[0], cnt[1], delta, waves);
-        p1_issue(A, cs, bs, wt + 2 * P1_WORDS);
-        p1_tile<WIDE, BIG, FAST>(B, wt + P1_WORDS, w1, g, ds, dst, sink, stage, cur, cnt[1], cnt[0], delta, waves);
+    for (u64 wt = w0; wt < w1; wt += 2 * WORDS) {
+        p1_issue<TPW>(B, cs, bs, wt + WORDS);
+        p1_tile<WIDE, BIG, FAST, ONE>(A, wt, w1, g, ds, dst, sink, stage, cur, cnt[0], cnt[1], delta, waves);
+        p1_issue<TPW>(A, cs, bs, wt + 2 * WORDS);
+        p1_tile<WIDE, BIG, FAST, ONE>(B, wt + WORDS, w1, g, ds, dst, sink, stage, cur, cnt[1], cnt[0], delta, waves);
     }
 }
 

@@ -34,6 +34,7 @@
 
 // One translation unit, cut into parts by subject (kernels k_*, host code h_*):
 #include "k_keys.inc"        // typedefs, key geometry, tunables, key generators
+#include "co_strand.inc"     // one strand of a coarse genome answers for both: digit, classes, patterns (shared with a host check)
 #include "k_sort.inc"        // pack, histograms, pass 0 / 1 / 2, chunk table, LDS sort, merge fallback
 #include "k_sort2.inc"       // pass 1 / pass 2 / LDS sort as persistent, software-pipelined kernels (buffer loads, counted waits)
 #include "k_intersect.inc"   // n-way intersection, candidate compaction, collection, list merge
