@@ -453,6 +453,28 @@ int kr_design_hairpins(kr_ctx*, const kr_hairpin_params* params);
  * KR_ERR_STATE when that run had the check off.  kr_design_record does not change with the check. */
 int64_t kr_design_fetch_hairpins(kr_ctx*, int32_t* out, size_t cap);
 
+/* ---- N mutually compatible assays of the designed pairs (krisp_fasta --panel) -------------------------------------------
+ * Replaces no seam of the reference, which selects nothing.  Of ncand candidates in the caller's order -- a template of W
+ * bytes and a primer pair each, the pair as four uint16: left_start, left_len, right_start, right_len, as kr_design_record
+ * names them -- the first `size` that are different loci (no window of 16 bases A C G T shared with an earlier member's
+ * template, on either strand) and do not clash (every duplex figure of a candidate's primer, in the left role, with a
+ * member's primer at most max_sec): DESIGN §23 has the definition.  It runs on the device in csrc/k_panel.inc, a launch per
+ * round and one synchronise, with the model and max_sec of the latest kr_design_table (KR_ERR_STATE before one).  All
+ * candidates are resident at once: KR_ERR_CAPACITY when templates and state (W + 18 bytes a candidate) do not fit.
+ * KR_ERR_PARAM for W outside 1 .. 2047, a primer outside 10 .. 60 bases or outside its template, size outside 1 .. 64, a
+ * null pointer with ncand > 0.  Returns the number of members, 0 .. size; ncand = 0: 0 without a launch. */
+int64_t kr_panel_run(kr_ctx*, const uint8_t* templates, const uint16_t* pairs, uint64_t ncand, int W, int size);
+/* a member, in order of acceptance: its position among the candidates, the greatest figures of its primers against the
+ * primers of the members before it in mK (0 and 0 for the first), and how many candidates it dropped as the same locus
+ * ([0]) and for a clash ([1]) */
+typedef struct { uint32_t position; int32_t cross_any, cross_end; uint32_t dropped[2]; } kr_panel_member;
+/* the members of the latest run (KR_ERR_STATE before one) */
+int64_t kr_panel_fetch(kr_ctx*, kr_panel_member* out, size_t cap);
+/* two bytes per candidate of the latest run: fate (1 member, 2 dropped as the same locus, 3 dropped for a clash, 0 still
+ * alive when the panel was full) and by (the 1-based member that dropped it, a member's own number, 0 for fate 0); cap
+ * counts bytes.  Returns the number of bytes written (KR_ERR_STATE before a run) */
+int64_t kr_panel_fates(kr_ctx*, uint8_t* out, size_t cap);
+
 /* ---- a CRISPR guide per region (krisp_fasta --out_guides) ---------------------------------------------------------------
  * Replaces no seam of the reference, which picks no guide.  For every region the protospacer window of guide_size columns
  * of the region's template that lies next to the enzyme's PAM / PFS, passes the GC and poly-X filters and differs most

@@ -31,6 +31,8 @@ DESIGN_RECORD = np.dtype([("found", "<u4"), ("product_size", "<u4"), ("pair_pena
                           ("right_self_end", "<i4"), ("pair_any", "<i4"), ("pair_end", "<i4")])             # kr_design_record
 # ... and, behind it, the pair's two figures of kr_design_fetch_hairpins: what Engine.design returns with the check on
 DESIGN_RECORD_HP = np.dtype(DESIGN_RECORD.descr + [("left_hairpin", "<i4"), ("right_hairpin", "<i4")])
+PANEL_MEMBER = np.dtype([("position", "<u4"), ("cross_any", "<i4"), ("cross_end", "<i4"), ("dropped", "<u4", (2,))])  # kr_panel_member
+PANEL_FATE = np.dtype([("fate", "u1"), ("by", "u1")])                         # kr_panel_fates: two bytes a candidate
 GUIDE_RECORD = np.dtype([("found", "<u4"), ("strand", "<u4"), ("start", "<u4"), ("min_mismatches", "<u4"),
                          ("sum_mismatches", "<u4"), ("gc", "<u4"), ("candidates", "<u4"), ("pad", "<u4")])    # kr_guide_record
 GUIDE_HIT_RAW = np.dtype([("guide", "<u4"), ("strand", "u1"), ("mismatches", "u1"), ("pam", "u1"), ("pad", "u1"), ("pos", "<u8"),
@@ -137,6 +139,9 @@ SYMBOLS = [
     ("kr_design_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_design_hairpins", _c.c_int, [_P, _P]),
     ("kr_design_fetch_hairpins", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_panel_run", _c.c_int64, [_P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int]),
+    ("kr_panel_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_panel_fates", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guides_table", _c.c_int, [_P, _P]),
     ("kr_guides_run", _c.c_int64, [_P, _P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
     ("kr_guides_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
@@ -915,6 +920,26 @@ class Engine:
             both[name] = out[name][:len(t)]
         both["left_hairpin"], both["right_hairpin"] = hp[:len(t), 0], hp[:len(t), 1]
         return both
+
+    def panel(self, templates, pairs, size):
+        """templates: uint8 [candidates, W], pairs: uint16 [candidates, 4] (left_start, left_len, right_start, right_len), in
+        the order the selection goes by; after design_table (the model and max_sec) -> (PANEL_MEMBER array of at most
+        `size` members in order of acceptance, PANEL_FATE array, one per candidate) (kr_panel_run, kr_panel_fetch,
+        kr_panel_fates)"""
+        t = np.ascontiguousarray(templates, dtype=np.uint8)
+        if t.ndim != 2:
+            raise ValueError("panel: templates is a matrix, a row of W letters each")
+        q = np.ascontiguousarray(pairs, dtype=np.uint16).reshape(-1, 4)
+        if len(q) != len(t):
+            raise ValueError(f"panel: {len(t)} templates, {len(q)} pairs")
+        n = len(t)
+        members = self._check(self.lib.kr_panel_run(self.ctx, _ptr(t) if n else None, _ptr(q) if n else None, n, t.shape[1], size),
+                              "kr_panel_run")
+        out = np.zeros(max(members, 1), dtype=PANEL_MEMBER)
+        self._check(self.lib.kr_panel_fetch(self.ctx, _ptr(out), members), "kr_panel_fetch")
+        fates = np.zeros(max(n, 1), dtype=PANEL_FATE)
+        self._check(self.lib.kr_panel_fates(self.ctx, _ptr(fates), 2 * n), "kr_panel_fates")
+        return out[:members], fates[:n]
 
     def guides_table(self, guide_size, pam5=(), pam3=(), gc=(30, 70), min_mismatches=1):
         """the options of guides(): pam5 / pam3 = the motifs as sequences of 4-bit IUPAC masks, read 5'->3' on the guide's

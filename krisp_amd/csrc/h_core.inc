@@ -355,6 +355,14 @@ struct kr_ctx {
         std::vector<kr_design_record> out;      // the records of the latest run, all batches
         std::vector<int32_t> hp_out;            // ... and, with the hairpin check, its two figures a region
     } design;
+    // the panel pass (kr_panel_*: h_panel.inc): all candidates resident, the model and max_sec are design's
+    struct Panel {
+        int64_t nmem = -1;                      // members of the latest run
+        u64 ncand = 0;
+        DevBuf tmpl, pairs, state, cross, pick;
+        std::vector<kr_panel_member> members;   // the latest run's, in order of acceptance
+        std::vector<uint8_t> fates;             // ... and (fate, by) per candidate
+    } panel;
     // the guide pass (kr_guides_*: h_guides.inc): no genome, no geometry of another pass
     struct Guides {
         bool on = false;
@@ -786,6 +794,9 @@ void kr_destroy(kr_ctx* c) {
         auto& gu = c->guides;
         DevBuf* gb[] = {&gu.rows, &gu.off, &gu.bnd, &gu.rec};
         for (DevBuf* b : gb) release(c, *b);
+        auto& pn = c->panel;
+        DevBuf* pb[] = {&pn.tmpl, &pn.pairs, &pn.state, &pn.cross, &pn.pick};
+        for (DevBuf* b : pb) release(c, *b);
     }
     if (c->mbox) (void)hipHostFree(c->mbox);
     for (auto e : c->pool) (void)hipEventDestroy(e);

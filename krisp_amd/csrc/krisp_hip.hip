@@ -55,6 +55,8 @@
 #include "k_primers.inc"     // the primer-product pass: sites of primer texts of mixed lengths, joined into PCR products
 #include "k_assay.inc"       // the assay join: the guide hits inside the primer products' interiors, a thread per product
 #include "k_design.inc"      // the primer design pass: a wavefront per region, integer thermodynamics, the best pair
+#include "panel_step.inc"    // what the panel pass does per window, table slot and primer base, in plain C++ (shared with a host check)
+#include "k_panel.inc"       // the panel pass: a launch per round, the member's windows in an LDS table, a wavefront per candidate
 #include "k_coarse.inc"      // a genome that stopped behind pass 1 against a short candidate list: LDS table per top byte, hit list
 #include "k_guides.inc"      // the guide pass: a wavefront per region, the window next to a PAM that differs most from the outgroup rows
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
@@ -70,6 +72,7 @@
 #include "h_primers.inc"     // kr_primers_*: in-silico PCR of designed primer pairs against a genome
 #include "h_assay.inc"       // kr_assay_*: the link table, the join of the two lists on the device, its rows
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options
+#include "h_panel.inc"       // kr_panel_*: N mutually compatible assays of the designed pairs, selected on the device
 #include "h_guides.inc"      // kr_guides_*: a CRISPR guide per region from its template, its outgroup rows and the guide options
 #include "h_pgzip.inc"       // one gzip member inflated on several threads (host only)
 #include "h_ingest.inc"      // file -> inflate -> parse -> pinned upload buffer (host side)

@@ -39,7 +39,8 @@ from .reports import (                                                        # 
     guide_hits_refusal, guide_rows, guide_tallies, guide_texts, guides_refusal, locate_regions, motif_masks, near_matches,
     near_refusal, near_targets, pick_guides, predict_products, primer_pairs, primer_products, primer_products_refusal,
     products_refusal, shortlist_texts, write_assay_hits, write_guide_bulge_hits, write_guide_candidates, write_guide_hits,
-    write_guides, write_locations, write_near, write_products)
+    write_guides, write_locations, write_near, write_products,
+    PANEL_HEADER, PANEL_MAX_SIZE, panel_candidates, panel_refusal, select_panel, write_panel)
 
 def prettyTime(t):
     """shared.py:8-31."""
@@ -1673,6 +1674,19 @@ def build_parser():
                         "designed locus of an ingroup genome is a row without mismatches; the rows to look at are the others.\n"
                         "Both searches and their join run on the device over one read of every input.  Bulged hits\n"
                         "(--guide-hit-bulges) take no part: the unbulged hits alone are joined.  (default: no join)")
+    p.add_argument("--panel", type=int, default=None, metavar="INT",
+                   help="With --design-primers and --out_panel: pick INT (1 .. 64) of the designed assays that can share a tube.\n"
+                        "The regions with a pair (with --out_guides: and a guide) go by ascending pair_penalty (with\n"
+                        "--out_guides: the greater min_mismatches first), then region; the first is a member, and after every\n"
+                        "member a later candidate is dropped when it is the same locus (its template shares 16 bases with the\n"
+                        "member's, on either strand) or clashes (a duplex figure of one of its primers with one of the member's\n"
+                        "lies above --max_sec_tm); the next member is the first still alive.  The selection runs on the device;\n"
+                        "no pass over the inputs.  (default: no panel)")
+    p.add_argument("--out_panel", type=str, metavar="PATH",
+                   help="The file of --panel, tab-separated, a row per member in order of acceptance: member, region (the pair's\n"
+                        "data row in the CSV), pair_penalty, product_size, left_sequence, right_sequence, cross_any, cross_end (the\n"
+                        "greatest duplex figures of its primers with the primers of the members before it), dropped_same_locus,\n"
+                        "dropped_clash (the candidates this member dropped, by cause)")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -1837,6 +1851,7 @@ def _check_options(args, parser):
         from . import primers
         if not primers.available():
             _refuse("--primer3 needs the primer3-py package, which is not installed here (the k-mer path itself does not use it)")
+    check(panel_refusal(args.design_primers, args.panel, args.out_panel is not None, bool(args.primer3)))
     return args
 
 
@@ -1880,7 +1895,7 @@ def _render(args, groups, ingroup, device):
         if args.verbose:
             print("Designing a primer pair for every region ... ", file=sys.stderr)
         # (the templates are built once: the guide pass takes them too)
-        templates = design_templates(groups, ingroup) if args.out_guides is not None else None
+        templates = design_templates(groups, ingroup) if args.out_guides is not None or args.panel is not None else None
         records = design_primers(groups, ingroup, device=device, hairpins=args.hairpins, templates=templates, **design)
         csv_text, align_text = primers.render_designed(groups, ingroup, records, dot=args.dot_alignment)
     else:
@@ -1914,8 +1929,21 @@ def _run_reports(args, groups, ingroup, device, records, templates):
         write_products(args.out_primer_products,
                        primer_products(groups, records, ingroup, *files, *geometry, mismatches=args.primer_mismatches,
                                        max_product=args.max_product, **where))
-    if args.out_guides is None:
-        return
+    guides = None
+    if args.out_guides is not None:
+        guides = _run_guide_reports(args, groups, ingroup, device, records, templates, say)
+    if args.panel is not None:
+        say(f"Picking a panel of {args.panel} assays ... ")
+        order = panel_candidates(records, guides)
+        design = {name: getattr(args, name) for name in _PRIMER_OPTIONS}
+        members, _fates = select_panel(templates[0], records, order, args.panel, device=device, **design)
+        write_panel(args.out_panel, templates[0], records, order, members)
+
+
+def _run_guide_reports(args, groups, ingroup, device, records, templates, say):
+    """_run_reports' passes of --out_guides: the guides, their hits, the assay hits -> the guides' records"""
+    files = (args.files, args.outgroup)
+    where = dict(omit_soft=args.omit_soft, device=device)
     say("Picking a guide for every region ... ")
     bounds = regions = None
     if args.design_primers:
@@ -1969,6 +1997,7 @@ def _run_reports(args, groups, ingroup, device, records, templates):
                          assay_hits(left, right, pairs, pairs_regions, texts, text_regions, region_strand, *files, args.guide_size,
                                     primer_mismatches=args.primer_mismatches, max_product=args.max_product,
                                     guide_mismatches=args.guide_hit_mismatches, **motifs, **where))
+    return guides
 
 
 def main(argv=None):

@@ -2,7 +2,8 @@
 time -- where the regions lie (--out_locations), their near matches (--out_near), the products of their flanks
 (--out_products), a primer pair per region and its products (--design-primers, --out_primer_products), a guide per
 region, picked among its best candidates by their outgroup hits where asked (--out_guides, --guide-candidates), and its
-hits (--out_guide_hits, --guide-hit-bulges) and the guide hits inside the primers' products (--out_assay_hits) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
+hits (--out_guide_hits, --guide-hit-bulges), the guide hits inside the primers' products (--out_assay_hits) and N mutually
+compatible assays of the designed pairs (--panel) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
 command line and its callers reach the passes there."""
 import os
 
@@ -1093,3 +1094,89 @@ def assay_hits(left, right, pairs, pairs_regions, texts, text_regions, region_st
 def write_assay_hits(path, rows):
     """the TSV of --out_assay_hits: ASSAY_HIT_HEADER, then a line per row"""
     _write_tsv(path, ASSAY_HIT_HEADER, rows, ASSAY_HIT.names)
+
+
+# ----------------------------------------------------------------------------
+# N mutually compatible assays of the designed pairs (--panel, DESIGN §23)
+# ----------------------------------------------------------------------------
+PANEL_HEADER = ("member\tregion\tpair_penalty\tproduct_size\tleft_sequence\tright_sequence\tcross_any\tcross_end\t"
+                "dropped_same_locus\tdropped_clash")
+PANEL_MAX_SIZE = 64
+
+
+def panel_refusal(design_primers, panel, out_panel, primer3):
+    """why --panel / --out_panel are not taken (one line), or None.  panel: the option's value or None; design_primers,
+    out_panel, primer3: whether the options are given"""
+    if panel is None:
+        return "--out_panel needs --panel (the number of assays to pick)" if out_panel else None
+    if not design_primers:
+        return "--panel needs --design-primers (the primer pairs it picks among)"
+    if panel < 1 or panel > PANEL_MAX_SIZE:
+        return f"--panel must lie between 1 and {PANEL_MAX_SIZE} (got {panel})"
+    if not out_panel:
+        return "--panel needs --out_panel (the file the panel is written to)"
+    if primer3:
+        return "--panel cannot be combined with --primer3 (the pairs Primer3 designs are not compared)"
+    return None
+
+
+def panel_candidates(records, guides=None):
+    """The candidates of the panel pass in the order the selection goes by: the regions with a pair (records: design_primers')
+    by ascending pair_penalty, then region; with `guides` (a GUIDE_RECORD per region: design_guides' or pick_guides') only
+    those that have a guide too, the greater min_mismatches first, then pair_penalty, then region.  -> int64 region indexes"""
+    ok = records["found"] != 0
+    if guides is not None:
+        if len(guides) != len(records):
+            raise ValueError(f"panel_candidates: {len(guides)} guides for {len(records)} records")
+        ok = ok & (guides["found"] != 0)
+    idx = np.flatnonzero(ok).astype(np.int64)
+    keys = (idx, records["pair_penalty"][idx].astype(np.int64))
+    if guides is not None:
+        keys += (-guides["min_mismatches"][idx].astype(np.int64),)
+    return idx[np.lexsort(keys)]
+
+
+def select_panel(templates, records, order, size, device=0, tm=(53, 68), gc=(40, 70), amp_size=(70, 150), primer_size=(25, 35),
+                 max_sec_tm=40, gc_clamp=1, max_end_gc=4):
+    """The panel of --panel on the device (kr_panel_*): of the candidates `order` (panel_candidates: region
+    indexes into the template rows `templates` and design_primers' `records`) the first `size` (1 .. 64) that are different
+    loci -- no window of 16 bases shared between two templates, on either strand -- and whose primers' duplex figures with
+    the primers of every earlier member stay at `max_sec_tm` or below: member 1 is the first candidate; after every member
+    each later candidate still alive is dropped if it is the same locus, else if it clashes; the next member is the first
+    still alive.  The primer options are design_primers' (the model's integers and max_sec_tm are what the pass reads).
+    -> (_native.PANEL_MEMBER array, in order of acceptance: `position` indexes `order`; _native.PANEL_FATE array, one per
+    candidate of `order`).  ValueError for a size outside 1 .. 64 or figures the designer does not take"""
+    from . import _native, thermo
+    if size < 1 or size > PANEL_MAX_SIZE:
+        raise ValueError(f"--panel must lie between 1 and {PANEL_MAX_SIZE} (got {size})")
+    opts = dict(tm=tuple(tm), gc=tuple(gc), amp_size=tuple(amp_size), primer_size=tuple(primer_size), max_sec_tm=max_sec_tm,
+                gc_clamp=gc_clamp, max_end_gc=max_end_gc)
+    why = thermo.refusal(**opts)
+    if why is not None:
+        raise ValueError(why)
+    order = np.asarray(order, dtype=np.int64)
+    if len(order) == 0:
+        return np.empty(0, dtype=_native.PANEL_MEMBER), np.empty(0, dtype=_native.PANEL_FATE)
+    rows = np.ascontiguousarray(templates, dtype=np.uint8)[order]
+    pairs = np.stack([records[f][order] for f in ("left_start", "left_len", "right_start", "right_len")], axis=1).astype(np.uint16)
+    with _engine(device) as eng:
+        eng.design_table(thermo.params(**opts))
+        return eng.panel(rows, pairs, size)
+
+
+def write_panel(path, templates, records, order, members):
+    """the TSV of --out_panel: PANEL_HEADER, then a line per member in order of acceptance.  templates, records, order as
+    select_panel takes them, members: its.  region = the pair's data row in the CSV of --design-primers (the region's rank
+    among the regions with a pair); penalty and figures as the CSV prints its own, from the integers"""
+    from . import thermo
+    rank = np.cumsum(records["found"] != 0) - 1
+    with open(path, "w") as f:
+        f.write(PANEL_HEADER + "\n")
+        for j, m in enumerate(members):
+            i = int(order[int(m["position"])])
+            r = records[i]
+            t = bytes(templates[i]).decode("ascii")
+            ls, ln, rs, rn = (int(r[k]) for k in ("left_start", "left_len", "right_start", "right_len"))
+            f.write(f"{j + 1}\t{int(rank[i])}\t{thermo.milli(int(r['pair_penalty']))}\t{int(r['product_size'])}\t{t[ls:ls + ln]}\t"
+                    f"{_guide_rc(t[rs:rs + rn])}\t{thermo.celsius(int(m['cross_any']))}\t{thermo.celsius(int(m['cross_end']))}\t"
+                    f"{int(m['dropped'][0])}\t{int(m['dropped'][1])}\n")
