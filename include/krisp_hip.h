@@ -623,6 +623,43 @@ int64_t kr_assay_join(kr_ctx*, int id);
  * are ordered here.  Returns their number; out == NULL: the number only.  KR_ERR_STATE before a join */
 int64_t kr_assay_fetch(kr_ctx*, kr_assay_hit* out, size_t cap);
 
+/* ---- multiplex in-silico PCR of a panel's oligos (krisp_fasta --out_panel_products) -----------------------------------
+ * No seam in the reference.  With all the primers of a panel in one tube every oligo can open a product and every oligo
+ * can close one: DESIGN §24 holds the definition, tests/multiplex_reference.py restates it.  There are T distinct texts
+ * of 10 .. 60 letters, written 5'->3'.  Entry 2 t is text t as written: it OPENS a product, its 3' end lies in its last
+ * columns.  Entry 2 t + 1 is its reverse complement: it CLOSES a product, its 3' end lies in its first columns (the primer
+ * pass's numbering with nleft = T, nright = 0).  A site is the primer pass's site.  A product (a, b) is an opening site of
+ * entry 2 a at s1 and a closing site of entry 2 b + 1 at s2 on one record with s2 >= s1 + len(a) and
+ * s2 + len(b) - s1 <= max_product; a == b is the product of one primer with itself.  There is no strand: a designed pair
+ * (L, R) amplifies (L, R) on '+' and (R, L) on '-'.  It runs in the locate context (only the soft-mask mode plays a part)
+ * with a state of its own: a kr_primers_* table, its lists and the assay links beside it are not touched.  On the device
+ * the sites are csrc/k_primers.inc's scan, the join and the tally csrc/k_multiplex.inc.
+ *
+ * kr_multiplex_table: the texts as kr_primers_table takes them, ntexts + 1 ascending offsets.  KR_ERR_PARAM for ntexts
+ * outside 1 .. 128, a length outside 10 .. 60, mismatches outside 0 .. 3, max_product < 2 * the longest text (with that
+ * bound every ordered pair can form a product), a null table.  Returns the number of slots of the seed table;
+ * KR_ERR_CAPACITY for a table that does not fit.  kr_set_params_locate drops the table. */
+int64_t kr_multiplex_table(kr_ctx*, const uint8_t* text, const uint32_t* offsets, uint64_t ntexts, int mismatches,
+                           uint32_t max_product);
+/* one product, 24 bytes: pos = the first base of the opening site, length = to the last base of the closing site, fwd =
+ * the text that opens, rev = the text that closes, their sites' mismatches and those in the 5 columns at the 3' ends; the
+ * pad is zero */
+typedef struct { uint64_t pos; uint32_t length; uint16_t fwd, rev; uint8_t fwd_mm, rev_mm, fwd_end_mm, rev_end_mm, pad[4]; } kr_multiplex_hit;
+/* scans uploaded genome `id` as kr_primers_scan does: its separators, its sites, their records, then the join of every
+ * opening site with every closing site in reach.  Returns the number of products.  Counted, scanned, written: no atomics,
+ * the same bytes on every run.  KR_ERR_STATE "kr_multiplex_table first" without a table; KR_ERR_CAPACITY for 2^32 sites
+ * or products or more, or lists that do not fit. */
+int64_t kr_multiplex_scan(kr_ctx*, int id);
+/* the products of the latest scan in (pos, length, fwd, rev) order.  KR_ERR_STATE before a scan */
+int64_t kr_multiplex_fetch(kr_ctx*, kr_multiplex_hit* out, size_t cap);
+/* the sites of the latest scan, as the device lists them.  Returns their number; out == NULL: the number only */
+int64_t kr_multiplex_sites(kr_ctx*, kr_product_site* out, size_t cap);
+/* the products of the latest scan counted on the device, for a caller that wants the counts and not the rows:
+ * out[2 * (a * T + b) + clean] = the number of products (a, b), clean = 1 where both end-mismatch figures are 0; 2 T^2
+ * counters.  Returns 2 T^2.  The list is only read: a fetch gives the same bytes after it as before it.  No products:
+ * zeros without a launch.  KR_ERR_STATE before a scan or after a new table; KR_ERR_CAPACITY for cap < 2 T^2. */
+int64_t kr_multiplex_tally(kr_ctx*, uint32_t* out, size_t cap);
+
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics
  * (kstream/kstream.py:458-479 file lines, 510-537 FASTA iff the first line holds '>', 450 that line is

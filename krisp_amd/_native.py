@@ -24,6 +24,8 @@ PRODUCT_SITE = np.dtype([("pos", "<u8"), ("entry", "<u4"), ("mismatches", "u1"),
                          ("pad", "<u2")])                                      # kr_product_site
 PRODUCT_HIT = np.dtype([("pos", "<u8"), ("length", "<u4"), ("pair", "<u4"), ("strand", "u1"), ("left_mm", "u1"),
                         ("right_mm", "u1"), ("left_end_mm", "u1"), ("right_end_mm", "u1"), ("pad", "u1", (3,))])   # kr_product_hit
+MULTIPLEX_HIT = np.dtype([("pos", "<u8"), ("length", "<u4"), ("fwd", "<u2"), ("rev", "<u2"), ("fwd_mm", "u1"), ("rev_mm", "u1"),
+                          ("fwd_end_mm", "u1"), ("rev_end_mm", "u1"), ("pad", "u1", (4,))])                 # kr_multiplex_hit
 DESIGN_RECORD = np.dtype([("found", "<u4"), ("product_size", "<u4"), ("pair_penalty", "<u4"), ("left_start", "<u2"),
                           ("left_len", "<u2"), ("right_start", "<u2"), ("right_len", "<u2"), ("left_tm", "<i4"), ("right_tm", "<i4"),
                           ("left_gc", "<u2"), ("right_gc", "<u2"), ("left_penalty", "<u4"), ("right_penalty", "<u4"),
@@ -152,6 +154,11 @@ SYMBOLS = [
     ("kr_guide_hits_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_hits_windows", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_hits_tally", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_multiplex_table", _c.c_int64, [_P, _P, _P, _c.c_uint64, _c.c_int, _c.c_uint32]),
+    ("kr_multiplex_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_multiplex_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_multiplex_sites", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_multiplex_tally", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guide_bulges_table", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_char_p, _c.c_char_p, _c.c_int]),
     ("kr_guide_bulges_scan", _c.c_int64, [_P, _c.c_int]),
     ("kr_guide_bulges_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
@@ -437,6 +444,7 @@ class Engine:
             raise KrispHipError("kr_create failed: " + self.lib.kr_last_error(None).decode())
         self.params = None
         self._guide_hit_texts = 0
+        self._multiplex_texts = 0
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -890,6 +898,41 @@ class Engine:
         """ASSAY_HIT_RAW array of the latest assay_join() in (pos, length, strand, pair, hit_pos, hit_strand, guide) order
         (kr_assay_fetch)"""
         return self._sized_fetch("kr_assay_fetch", ASSAY_HIT_RAW)
+
+    def multiplex_table(self, texts, mismatches, max_product):
+        """texts: a list of 1 .. 128 bytes (upper case, T for U, 5'->3'), each of its own length 10 .. 60: the oligos of one
+        tube.  Text t opens a product as written and closes one as its reverse complement -> slots of the seed table
+        (kr_multiplex_table).  A state of its own beside primers_table's"""
+        texts = [bytes(t) for t in texts]
+        offsets = np.zeros(len(texts) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum([len(t) for t in texts], dtype=np.int64)
+        text = np.frombuffer(b"".join(texts) + b"\0", dtype=np.uint8)      # (never empty: a pointer to pass)
+        slots = self._check(self.lib.kr_multiplex_table(self.ctx, _ptr(text), _ptr(offsets), len(texts), mismatches, max_product),
+                            "kr_multiplex_table")
+        self._multiplex_texts = len(texts)            # (multiplex_tally's side; a refused table leaves no table)
+        return slots
+
+    def multiplex_scan(self, gid):
+        """scans uploaded genome gid against the oligos' table and leaves the products on the device -> their number
+        (kr_multiplex_scan)"""
+        return self._check(self.lib.kr_multiplex_scan(self.ctx, gid), "kr_multiplex_scan")
+
+    def multiplex_products(self, gid):
+        """MULTIPLEX_HIT array of uploaded genome gid in (pos, length, fwd, rev) order (kr_multiplex_scan)"""
+        return self._scan_fetch("kr_multiplex_scan", "kr_multiplex_fetch", gid, MULTIPLEX_HIT)
+
+    def multiplex_sites(self):
+        """the latest multiplex scan's primer sites as the device lists them: PRODUCT_SITE, position order
+        (kr_multiplex_sites)"""
+        return self._sized_fetch("kr_multiplex_sites", PRODUCT_SITE)
+
+    def multiplex_tally(self):
+        """the products of the latest multiplex scan counted on the device: uint32 [T, T, 2], [a, b, clean] = the products
+        that text a opens and text b closes, clean = 1 where neither 3' end holds a mismatch (kr_multiplex_tally)"""
+        T = max(self._multiplex_texts, 1)
+        out = np.zeros((T, T, 2), dtype=np.uint32)
+        self._check(self.lib.kr_multiplex_tally(self.ctx, _ptr(out), out.size), "kr_multiplex_tally")
+        return out
 
     def design_table(self, params):
         """params: thermo.Params, the model's integers and the primer options (kr_design_table)"""

@@ -345,6 +345,12 @@ struct kr_ctx {
         void bufs(Bufs& v) { v.insert(v.end(), {&links, &hits}); }
         void reset() { on = false; nlinks = 0; nhits = -1; }
     } assay;
+    // the multiplex pass (kr_multiplex_*: h_multiplex.inc), in the same context: the primer pass's state once more, a table
+    // of its own with nleft = the texts and nright = 0 and no pair list; hits holds kr_multiplex_hit
+    struct Mux : Prim {
+        DevBuf tally;                   // kr_multiplex_tally's counters
+        void bufs(Bufs& v) { Prim::bufs(v); v.push_back(&tally); }
+    } mux;
     // the primer design pass (kr_design_*: h_design.inc): no genome, no geometry of another pass
     struct Design {
         bool on = false;
@@ -786,7 +792,7 @@ void kr_destroy(kr_ctx* c) {
     {
         kr_ctx::Bufs sb;                // the wide path's and the one-genome scans': every pass hands over its own
         c->wide.bufs(sb);
-        c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb); c->assay.bufs(sb);
+        c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb); c->assay.bufs(sb); c->mux.bufs(sb);
         for (DevBuf* b : sb) release(c, *b);
         auto& ds = c->design;
         DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec, &ds.hprec};

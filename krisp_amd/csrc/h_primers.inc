@@ -9,12 +9,49 @@
 #define PRIM_MIN_LEN 10             // the lengths kr_design_table takes for a primer
 #define PRIM_MAX_LEN 60
 
-static void prim_geom(const kr_ctx* c, PrimGeom* pg) {
-    const auto& pm = c->prim;
+// (pm: the primer pass's state, or the multiplex pass's -- h_multiplex.inc)
+static void prim_geom(const kr_ctx* c, const kr_ctx::Prim& pm, PrimGeom* pg) {
     memset(pg, 0, sizeof *pg);
     pg->smin = pm.smin; pg->maxlen = pm.maxlen;
     pg->omit = (u32)c->loc.omit; pg->M = (u32)pm.M; pg->nleft2 = (u32)(2 * pm.nleft);
     seed_pieces(pg->smin, (u32)pm.M + 1, pg->off, pg->pw);
+}
+
+// the lengths of the nt texts of a table of `who`: 10 .. 60 letters each -> the shortest and the longest
+static int prim_lengths(kr_ctx* c, const char* who, const uint32_t* offsets, u64 nt, u32* smin_out, u32* maxlen_out) {
+    u32 smin = nt ? PRIM_MAX_LEN : PRIM_MIN_LEN, maxlen = PRIM_MIN_LEN;
+    for (u64 t = 0; t < nt; t++) {
+        const int64_t n = (int64_t)offsets[t + 1] - (int64_t)offsets[t];
+        if (n < PRIM_MIN_LEN || n > PRIM_MAX_LEN)
+            return fail(c, KR_ERR_PARAM, "%s: text %llu has %lld letters (%d .. %d are taken)", who, (unsigned long long)t, (long long)n,
+                        PRIM_MIN_LEN, PRIM_MAX_LEN);
+        smin = std::min(smin, (u32)n);
+        maxlen = std::max(maxlen, (u32)n);
+    }
+    *smin_out = smin; *maxlen_out = maxlen;
+    return KR_OK;
+}
+
+// the 2 nt entries of nt texts: their offsets (eoff), their text (arena: text t, then its reverse complement) and every
+// entry's keys under the NP pieces of the first smin columns of its text as it reads on the forward strand.  Throws
+// std::bad_alloc
+static void prim_entries(const uint8_t* text, const uint32_t* offsets, u64 nt, const PrimGeom& pg, u32 NP, std::vector<uint8_t>& arena,
+                         std::vector<u32>& eoff, SeedKeys& keyed) {
+    const u64 ne = 2 * nt;
+    eoff.resize(ne + 1);
+    u64 at = 0;
+    for (u64 t = 0; t < nt; t++) {
+        const u32 n = offsets[t + 1] - offsets[t];
+        eoff[2 * t] = (u32)at;                      // (< 2^24 texts of <= 60 letters twice: < 2^31)
+        eoff[2 * t + 1] = (u32)(at + n);
+        at += 2 * (u64)n;
+    }
+    eoff[ne] = (u32)at;
+    arena.resize(at + 16);
+    for (u64 t = 0; t < nt; t++)
+        seed_both_strands(arena.data() + eoff[2 * t], text + (offsets[t] - offsets[0]), offsets[t + 1] - offsets[t]);
+    keyed.reserve(ne * NP);
+    for (u64 e = 0; e < ne; e++) seed_keys(keyed, arena.data() + eoff[e], pg.off, NP, 0, (u32)e);
 }
 
 int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets, uint64_t nleft, uint64_t nright,
@@ -34,41 +71,19 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
         return fail(c, KR_ERR_CAPACITY, "kr_primers_table: %llu primer texts (the limit is %u)", (unsigned long long)nt, (1u << 24) - 1);
     if (npairs >= LOC_EMPTY) return fail(c, KR_ERR_CAPACITY, "kr_primers_table: %llu pairs (the limit is %u)",
                                          (unsigned long long)npairs, LOC_EMPTY - 1);
-    u32 smin = nt ? PRIM_MAX_LEN : PRIM_MIN_LEN, maxlen = PRIM_MIN_LEN;
-    for (u64 t = 0; t < nt; t++) {
-        const int64_t n = (int64_t)offsets[t + 1] - (int64_t)offsets[t];
-        if (n < PRIM_MIN_LEN || n > PRIM_MAX_LEN)
-            return fail(c, KR_ERR_PARAM, "kr_primers_table: text %llu has %lld letters (%d .. %d are taken)", (unsigned long long)t,
-                        (long long)n, PRIM_MIN_LEN, PRIM_MAX_LEN);
-        smin = std::min(smin, (u32)n);
-        maxlen = std::max(maxlen, (u32)n);
-    }
+    u32 smin, maxlen;
+    if ((rc = prim_lengths(c, "kr_primers_table", offsets, nt, &smin, &maxlen))) return rc;
     pm.M = M; pm.max_product = max_product; pm.nleft = nleft; pm.nright = nright; pm.plist.npairs = npairs;
     pm.smin = smin; pm.maxlen = maxlen;
     PrimGeom pg;
-    prim_geom(c, &pg);
+    prim_geom(c, pm, &pg);
     const u32 NP = (u32)M + 1;
-    const u64 ne = 2 * nt;
     std::vector<uint8_t> arena;
     std::vector<u32> eoff, pidx, plen;
     SeedKeys keyed;
     std::vector<u64> pkeys;
     try {
-        eoff.resize(ne + 1);
-        u64 at = 0;
-        for (u64 t = 0; t < nt; t++) {
-            const u32 n = offsets[t + 1] - offsets[t];
-            eoff[2 * t] = (u32)at;                  // (< 2^24 texts of <= 60 letters twice: < 2^31)
-            eoff[2 * t + 1] = (u32)(at + n);
-            at += 2 * (u64)n;
-        }
-        eoff[ne] = (u32)at;
-        arena.resize(at + 16);
-        for (u64 t = 0; t < nt; t++)
-            seed_both_strands(arena.data() + eoff[2 * t], text + (offsets[t] - offsets[0]), offsets[t + 1] - offsets[t]);
-        // every entry under the NP pieces of the first smin columns of its text as it reads on the forward strand
-        keyed.reserve(ne * NP);
-        for (u64 e = 0; e < ne; e++) seed_keys(keyed, arena.data() + eoff[e], pg.off, NP, 0, (u32)e);
+        prim_entries(text, offsets, nt, pg, NP, arena, eoff, keyed);
         plen.assign(npairs + 1, 0u);
         rc = pair_list_sort(c, "kr_primers_table", pairs, npairs, nleft, nright, pkeys, pidx, [&](u64 p, u32 li, u32 rj) {
             const u32 n1 = offsets[li + 1] - offsets[li], n2 = offsets[nleft + rj + 1] - offsets[nleft + rj];
@@ -94,13 +109,23 @@ int64_t kr_primers_table(kr_ctx* c, const uint8_t* text, const uint32_t* offsets
 }
 
 extern "C++" {    // (a template inside the translation unit's extern "C" block)
+// the sites of genome G against the table of st (the primer pass's or the multiplex pass's), by its number of pieces
 template <u32 NP>
-static int prim_sites_np(kr_ctx* c, const Genome& G, const PrimGeom& pg, u64 nw, u64 ntiles, u64* ns) {
-    return prod_sites_launch(c, G, c->prim, pg, nw, ntiles, "kr_primers_scan",
-                             "kr_primers_scan: 2^32 or more primer sites in one genome (fewer mismatches or pairs)",
-                             k_prim_scan<NP, false>, k_prim_scan<NP, true>, ns, (const u32*)c->prim.eoff.p);
+static int prim_sites_np(kr_ctx* c, const Genome& G, kr_ctx::Prim& st, const PrimGeom& pg, u64 nw, u64 ntiles, const char* who,
+                         const char* over, u64* ns) {
+    return prod_sites_launch(c, G, st, pg, nw, ntiles, who, over, k_prim_scan<NP, false>, k_prim_scan<NP, true>, ns, (const u32*)st.eoff.p);
 }
 }  // extern "C++"
+
+static int prim_sites(kr_ctx* c, const Genome& G, kr_ctx::Prim& st, const PrimGeom& pg, u64 nw, u64 ntiles, const char* who,
+                      const char* over, u64* ns) {
+    switch (pg.M + 1) {
+    case 1: return prim_sites_np<1>(c, G, st, pg, nw, ntiles, who, over, ns);
+    case 2: return prim_sites_np<2>(c, G, st, pg, nw, ntiles, who, over, ns);
+    case 3: return prim_sites_np<3>(c, G, st, pg, nw, ntiles, who, over, ns);
+    default: return prim_sites_np<4>(c, G, st, pg, nw, ntiles, who, over, ns);
+    }
+}
 
 int64_t kr_primers_scan(kr_ctx* c, int id) {
     const Genome* Gp;
@@ -110,14 +135,10 @@ int64_t kr_primers_scan(kr_ctx* c, int id) {
     c->prim.gid = id;
     c->assay.nhits = -1;                            // (a join of the earlier list is no join of this one)
     PrimGeom pg;
-    prim_geom(c, &pg);
+    prim_geom(c, c->prim, &pg);
     auto sites = [&](u64 nw, u64 ntiles, u64* ns) {
-        switch (pg.M + 1) {
-        case 1: return prim_sites_np<1>(c, G, pg, nw, ntiles, ns);
-        case 2: return prim_sites_np<2>(c, G, pg, nw, ntiles, ns);
-        case 3: return prim_sites_np<3>(c, G, pg, nw, ntiles, ns);
-        default: return prim_sites_np<4>(c, G, pg, nw, ntiles, ns);
-        }
+        return prim_sites(c, G, c->prim, pg, nw, ntiles, "kr_primers_scan",
+                          "kr_primers_scan: 2^32 or more primer sites in one genome (fewer mismatches or pairs)", ns);
     };
     // (window starts of the shortest text)
     return prod_scan(c, G, c->prim, pg, pg.smin, "kr_primers_scan", sites, k_prim_join<false>, k_prim_join<true>, (const u32*)c->prim.eoff.p);

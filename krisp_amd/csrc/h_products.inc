@@ -123,30 +123,38 @@ static int prod_join(kr_ctx* c, kr_ctx::Prod& st, const Geom& pg, u64 ns, const 
         [&](u32* bc, const u64* bo, u32* fl) { launch(emit, bc, bo, (kr_product_hit*)st.hits.p, fl); }, total_out);
 }
 
-// a product pass's scan behind scan_genome: the windows of `width` bases (the shortest text's), the separators, the sites
-// -- sites(nw, ntiles, &ns): the pass's choice of prod_sites_launch by its M --, their records, the join -> the products
+// a product pass's scan behind scan_genome, up to its join: the windows of `width` bases (the shortest text's), the
+// separators, the sites -- sites(nw, ntiles, &ns): the pass's choice of prod_sites_launch by its M -- and their records
+// (launched: the join follows on the stream) -> *ns sites.  The pass's counts stand at -1 until its caller sets them
+template <typename S>
+static int prod_scan_sites(kr_ctx* c, const Genome& G, kr_ctx::Prod& st, u64 width, const char* who, S&& sites, u64* ns) {
+    int rc;
+    st.nsites = st.nhits = -1;
+    *ns = 0;
+    u64 nw;
+    const u64 ntiles = scan_tiles(G.n_bases, width, &nw);
+    if (!ntiles || !(st.nleft + st.nright)) return KR_OK;
+    u64 nseps = 0;
+    // (the pass's own list: k_prod_rec reads it, and a kr_locate_seps of the caller writes loc.seps)
+    if ((rc = scan_seps(c, G, who, st.seps, [&](u64 total) { return ensure(c, st.seps, total * 8); }, &nseps))) return rc;
+    if (nseps >= (1ull << 32)) return fail(c, KR_ERR_CAPACITY, "%s: 2^32 or more records in one genome", who);
+    if ((rc = sites(nw, ntiles, ns))) return rc;
+    if (*ns) {
+        const u32 grid = scan_stride_grid(c, (*ns + 255) / 256);
+        hipLaunchKernelGGL(k_prod_rec, dim3(grid), dim3(256), 0, c->stream, (const kr_product_site*)st.sites.p, *ns,
+                           (const u64*)st.seps.p, nseps, (u32*)st.rec.p);
+    }
+    return KR_OK;
+}
+
+// ... and with the join of the two passes that have a pair list (the pass's join kernels) -> the products
 template <typename Geom, typename S, typename KC, typename KE, typename... E>
 static int64_t prod_scan(kr_ctx* c, const Genome& G, kr_ctx::Prod& st, const Geom& pg, u64 width, const char* who, S&& sites, KC join_count,
                          KE join_emit, E... eoff) {
     int rc;
-    st.nsites = st.nhits = -1;
-    u64 nw;
-    const u64 ntiles = scan_tiles(G.n_bases, width, &nw);
-    if (!ntiles || !(st.nleft + st.nright)) {
-        st.nsites = st.nhits = 0;
-        return 0;
-    }
-    u64 nseps = 0, ns = 0, np = 0;
-    // (the pass's own list: k_prod_rec reads it, and a kr_locate_seps of the caller writes loc.seps)
-    if ((rc = scan_seps(c, G, who, st.seps, [&](u64 total) { return ensure(c, st.seps, total * 8); }, &nseps))) return rc;
-    if (nseps >= (1ull << 32)) return fail(c, KR_ERR_CAPACITY, "%s: 2^32 or more records in one genome", who);
-    if ((rc = sites(nw, ntiles, &ns))) return rc;
-    if (ns) {
-        const u32 grid = scan_stride_grid(c, (ns + 255) / 256);
-        hipLaunchKernelGGL(k_prod_rec, dim3(grid), dim3(256), 0, c->stream, (const kr_product_site*)st.sites.p, ns,
-                           (const u64*)st.seps.p, nseps, (u32*)st.rec.p);
-        if ((rc = prod_join(c, st, pg, ns, who, join_count, join_emit, &np, eoff...))) return rc;
-    }
+    u64 ns = 0, np = 0;
+    if ((rc = prod_scan_sites(c, G, st, width, who, sites, &ns))) return rc;
+    if (ns && (rc = prod_join(c, st, pg, ns, who, join_count, join_emit, &np, eoff...))) return rc;
     st.nsites = (int64_t)ns;
     st.nhits = (int64_t)np;
     return (int64_t)np;

@@ -1,7 +1,7 @@
 // h_scan.inc -- part of krisp_hip.hip (one translation unit): the host side of what the six one-genome scans share
 // (k_scan.inc): the locate pass and the five seed passes -- near matches, guide hits, bulged guide hits, flank products,
-// primer products.  All six run in the locate context (kr_set_params_locate), one after the other on the context's
-// stream: the per-tile counts, their offsets and the overflow flag are one set of scratch (loc.tcount, loc.toff, loc.flag).
+// primer products (the multiplex pass, h_multiplex.inc, is the primer pass's scan with a join of its own).  All run in the
+// locate context (kr_set_params_locate), one after the other on the context's stream: the per-tile counts, their offsets and the overflow flag are one set of scratch (loc.tcount, loc.toff, loc.flag).
 //   all six: scan_ctx / scan_genome (the entry points' prologue), scan_tiles, scan_lds_bytes, scan_grid / scan_stride_grid
 //     (launch geometry), scan_two_pass (every list), scan_fetch; scan_seps (locate, products, primers); scan_windows (the
 //     hits' text: locate, near matches, guide hits, bulges -- the pass's cut launch passed in)

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(LOC_T) void k_ghit_keep(const kr_guide_hit* __restr
 
 // tally[4 guide + mismatches] += the hits of that guide at that distance; the list is only read.  A wavefront takes 64
 // neighbouring hits; a run of equal (guide, mismatches) among them -- a repeat sends most of a genome's hits to one guide --
-// is one add of its length by its first lane.  A hit that names no guide of the table or a distance above 3 (there is none
+// is one add of its length by its first lane (k_scan.inc: tally_runs).  A hit that names no guide of the table or a distance above 3 (there is none
 // unless the scan is broken) is not counted: no add outside the 4 nguides counters
 __global__ __launch_bounds__(256) void k_ghit_tally(const kr_guide_hit* __restrict__ hits, u64 nhits, u32 nguides, u32* __restrict__ tally) {
     const u32 lane = threadIdx.x & 63u;
@@ -80,12 +80,6 @@ __global__ __launch_bounds__(256) void k_ghit_tally(const kr_guide_hit* __restri
             const kr_guide_hit h = hits[i];
             if (h.guide < nguides && h.mismatches < 4u) key = 4u * h.guide + h.mismatches;
         }
-        const u32 prev = (u32)__shfl_up((int)key, 1, 64);
-        const bool head = lane == 0 || prev != key;
-        const u64 heads = __ballot(head);
-        if (head && key != ~0u) {
-            const u64 later = lane == 63 ? 0ull : heads >> (lane + 1);      // the heads behind this one
-            atomicAdd(tally + key, later ? (u32)__ffsll((long long)later) : 64u - lane);
-        }
+        tally_runs(key, lane, tally);
     }
 }

@@ -141,6 +141,19 @@ __device__ inline u64 scan_epilogue(T cnt, T* sh, u64 tl, u32* __restrict__ tcou
     }
 }
 
+// a wavefront's 64 neighbouring list elements counted by key (the tallies of the guide-hit and the multiplex pass): a run
+// of equal keys among them is one integer add of its length by its first lane; key ~0 = not counted.  Every lane of the
+// wavefront calls it (the shuffle and the ballot are whole)
+__device__ inline void tally_runs(u32 key, u32 lane, u32* __restrict__ tally) {
+    const u32 prev = (u32)__shfl_up((int)key, 1, 64);
+    const bool head = lane == 0 || prev != key;
+    const u64 heads = __ballot(head);
+    if (head && key != ~0u) {
+        const u64 later = lane == 63 ? 0ull : heads >> (lane + 1);          // the heads behind this one
+        atomicAdd(tally + key, later ? (u32)__ffsll((long long)later) : 64u - lane);
+    }
+}
+
 // exclusive offsets of per-tile counts (one workgroup of 1024 threads, a contiguous run of tiles each): off[n] = the total
 __global__ __launch_bounds__(1024) void k_loc_offsets(const u32* __restrict__ cnt, u64 n, u64* __restrict__ off) {
     __shared__ u64 sh[1024];

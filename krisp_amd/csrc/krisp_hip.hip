@@ -54,6 +54,7 @@
 #include "k_products.inc"    // the product pass: sites of the flanks within M substitutions, joined into PCR products
 #include "k_primers.inc"     // the primer-product pass: sites of primer texts of mixed lengths, joined into PCR products
 #include "k_assay.inc"       // the assay join: the guide hits inside the primer products' interiors, a thread per product
+#include "k_multiplex.inc"   // the multiplex pass: every opening site of a panel's oligos joined with every closing site, and its tally
 #include "k_design.inc"      // the primer design pass: a wavefront per region, integer thermodynamics, the best pair
 #include "panel_step.inc"    // what the panel pass does per window, table slot and primer base, in plain C++ (shared with a host check)
 #include "k_panel.inc"       // the panel pass: a launch per round, the member's windows in an LDS table, a wavefront per candidate
@@ -71,6 +72,7 @@
 #include "h_products.inc"    // kr_products_*: in-silico PCR of the regions' flanks against a genome; the scan, join, fetch and sites of both product passes
 #include "h_primers.inc"     // kr_primers_*: in-silico PCR of designed primer pairs against a genome
 #include "h_assay.inc"       // kr_assay_*: the link table, the join of the two lists on the device, its rows
+#include "h_multiplex.inc"   // kr_multiplex_*: in-silico PCR with all the oligos of a panel in one tube
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options
 #include "h_panel.inc"       // kr_panel_*: N mutually compatible assays of the designed pairs, selected on the device
 #include "h_guides.inc"      // kr_guides_*: a CRISPR guide per region from its template, its outgroup rows and the guide options

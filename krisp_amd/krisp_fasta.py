@@ -40,7 +40,9 @@ from .reports import (                                                        # 
     near_refusal, near_targets, pick_guides, predict_products, primer_pairs, primer_products, primer_products_refusal,
     products_refusal, shortlist_texts, write_assay_hits, write_guide_bulge_hits, write_guide_candidates, write_guide_hits,
     write_guides, write_locations, write_near, write_products,
-    PANEL_HEADER, PANEL_MAX_SIZE, panel_candidates, panel_refusal, select_panel, write_panel)
+    PANEL_HEADER, PANEL_MAX_SIZE, panel_candidates, panel_refusal, select_panel, write_panel,
+    PANEL_PRODUCT, PANEL_PRODUCT_HEADER, PANEL_SUMMARY, PANEL_SUMMARY_HEADER, panel_kind, panel_oligos, panel_products,
+    panel_products_refusal, panel_texts, write_panel_products, write_panel_summary)
 
 def prettyTime(t):
     """shared.py:8-31."""
@@ -1687,6 +1689,18 @@ def build_parser():
                         "data row in the CSV), pair_penalty, product_size, left_sequence, right_sequence, cross_any, cross_end (the\n"
                         "greatest duplex figures of its primers with the primers of the members before it), dropped_same_locus,\n"
                         "dropped_clash (the candidates this member dropped, by cause)")
+    p.add_argument("--out_panel_products", type=str, metavar="PATH",
+                   help="With --panel: multiplex in-silico PCR.  With all the panel's primers in one tube, every product they\n"
+                        "amplify in every genome, the outgroups included: any primer may open a product and any primer may close\n"
+                        "one (--primer-mismatches, --max-product and --omit-soft as --out_primer_products reads them).  A\n"
+                        "tab-separated file, a row per product: file, record, record_index, start, end, length, forward, reverse\n"
+                        "(the primers' names: 1L and 1R are member 1's), kind (pair: the two primers of one member; single: one\n"
+                        "primer with itself; cross: everything else), forward_mismatches, reverse_mismatches,\n"
+                        "forward_end_mismatches, reverse_end_mismatches.  One more pass over the inputs.  (default: no search)")
+    p.add_argument("--out_panel_summary", type=str, metavar="PATH",
+                   help="With --panel: the products of --out_panel_products counted on the device, a row per file and ordered\n"
+                        "primer pair with at least one: file, forward, reverse, kind, products, clean_end_products (those without\n"
+                        "a mismatch in the five 3' bases of either primer).  Alone it brings no product to the host.")
     p.add_argument("-w", "--workdir", type=str, metavar="PATH", help="Work directory to place temporary files")
     p.add_argument("-p", "--primer3", action=argparse.BooleanOptionalAction,
                    help="Design primers with Primer3 for every region found (needs the primer3-py package)")
@@ -1760,8 +1774,11 @@ _NEEDS = {
     "guide_hits": (("--guide-hit-mismatches", _GUIDE_HIT_OUTPUTS), ("--guide-hits-need-pam", _GUIDE_HIT_OUTPUTS),
                    ("--guide-hit-bulges", ("--out_guide_hits",))),
 }
-# ... or with this option, which the refusal does not name: --guide-candidates searches with the guide hits' two figures
-_ALSO_WITH = {"--guide-hit-mismatches": "--guide-candidates", "--guide-hits-need-pam": "--guide-candidates"}
+# ... or with one of these options, which the refusal does not name: --guide-candidates searches with the guide hits' two figures,
+# and the panel's products read the product passes' two figures
+_PANEL_PRODUCT_OUTPUTS = ("--out_panel_products", "--out_panel_summary")
+_ALSO_WITH = {"--guide-hit-mismatches": ("--guide-candidates",), "--guide-hits-need-pam": ("--guide-candidates",),
+              "--primer-mismatches": _PANEL_PRODUCT_OUTPUTS, "--max-product": _PANEL_PRODUCT_OUTPUTS}
 _PRIMER_OPTIONS = ("tm", "gc", "amp_size", "primer_size", "max_sec_tm", "gc_clamp", "max_end_gc")
 
 
@@ -1781,7 +1798,7 @@ def _check_options(args, parser):
 
     def needs(step):
         for opt, outputs in _NEEDS[step]:
-            if given(opt) and not any(given(out) for out in outputs) and not (opt in _ALSO_WITH and given(_ALSO_WITH[opt])):
+            if given(opt) and not any(given(out) for out in outputs) and not any(given(o) for o in _ALSO_WITH.get(opt, ())):
                 _refuse(f"{opt} needs " + " or ".join(outputs))
 
     def fill(*names):
@@ -1852,6 +1869,10 @@ def _check_options(args, parser):
         if not primers.available():
             _refuse("--primer3 needs the primer3-py package, which is not installed here (the k-mer path itself does not use it)")
     check(panel_refusal(args.design_primers, args.panel, args.out_panel is not None, bool(args.primer3)))
+    if any(given(out) for out in _PANEL_PRODUCT_OUTPUTS):
+        fill("primer_mismatches", "max_product")
+        check(panel_products_refusal(args.panel, args.out_panel_products is not None, args.out_panel_summary is not None,
+                                     args.amp_size, args.primer_size, args.primer_mismatches, args.max_product))
     return args
 
 
@@ -1938,6 +1959,15 @@ def _run_reports(args, groups, ingroup, device, records, templates):
         design = {name: getattr(args, name) for name in _PRIMER_OPTIONS}
         members, _fates = select_panel(templates[0], records, order, args.panel, device=device, **design)
         write_panel(args.out_panel, templates[0], records, order, members)
+        if args.out_panel_products is not None or args.out_panel_summary is not None:
+            say(f"Predicting what the panel's primers amplify together, with up to {args.primer_mismatches} mismatches each ... ")
+            rows, summary = panel_products(panel_oligos(templates[0], records, order, members), *files, *geometry,
+                                           mismatches=args.primer_mismatches, max_product=args.max_product,
+                                           rows=args.out_panel_products is not None, **where)
+            if args.out_panel_products is not None:
+                write_panel_products(args.out_panel_products, rows)
+            if args.out_panel_summary is not None:
+                write_panel_summary(args.out_panel_summary, summary)
 
 
 def _run_guide_reports(args, groups, ingroup, device, records, templates, say):

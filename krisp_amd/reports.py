@@ -3,7 +3,7 @@ time -- where the regions lie (--out_locations), their near matches (--out_near)
 (--out_products), a primer pair per region and its products (--design-primers, --out_primer_products), a guide per
 region, picked among its best candidates by their outgroup hits where asked (--out_guides, --guide-candidates), and its
 hits (--out_guide_hits, --guide-hit-bulges), the guide hits inside the primers' products (--out_assay_hits) and N mutually
-compatible assays of the designed pairs (--panel) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
+compatible assays of the designed pairs (--panel) and what their oligos amplify together (--out_panel_products) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
 command line and its callers reach the passes there."""
 import os
 
@@ -1180,3 +1180,161 @@ def write_panel(path, templates, records, order, members):
             f.write(f"{j + 1}\t{int(rank[i])}\t{thermo.milli(int(r['pair_penalty']))}\t{int(r['product_size'])}\t{t[ls:ls + ln]}\t"
                     f"{_guide_rc(t[rs:rs + rn])}\t{thermo.celsius(int(m['cross_any']))}\t{thermo.celsius(int(m['cross_end']))}\t"
                     f"{int(m['dropped'][0])}\t{int(m['dropped'][1])}\n")
+
+
+# ----------------------------------------------------------------------------
+# multiplex in-silico PCR of the panel's oligos in every genome (--out_panel_products, --out_panel_summary)
+# ----------------------------------------------------------------------------
+PANEL_PRODUCT_HEADER = ("file\trecord\trecord_index\tstart\tend\tlength\tforward\treverse\tkind\tforward_mismatches\t"
+                        "reverse_mismatches\tforward_end_mismatches\treverse_end_mismatches")
+PANEL_SUMMARY_HEADER = "file\tforward\treverse\tkind\tproducts\tclean_end_products"
+# (forward_index, reverse_index: the oligos' indexes, which order the rows; the files do not print them)
+PANEL_PRODUCT = np.dtype([("file", "O"), ("record", "O"), ("record_index", "<i8"), ("start", "<i8"), ("end", "<i8"), ("length", "<i8"),
+                          ("forward", "O"), ("reverse", "O"), ("kind", "O"), ("forward_mismatches", "u1"), ("reverse_mismatches", "u1"),
+                          ("forward_end_mismatches", "u1"), ("reverse_end_mismatches", "u1"), ("forward_index", "<i8"),
+                          ("reverse_index", "<i8")])
+PANEL_SUMMARY = np.dtype([("file", "O"), ("forward", "O"), ("reverse", "O"), ("kind", "O"), ("products", "<i8"),
+                          ("clean_end_products", "<i8"), ("forward_index", "<i8"), ("reverse_index", "<i8")])
+PANEL_MAX_OLIGO_TEXTS = 128         # kr_multiplex_table's limit: the distinct texts of 64 members at most
+PANEL_MIN_OLIGO, PANEL_MAX_OLIGO = 10, 60
+
+
+def panel_products_refusal(panel, out_products, out_summary, amp_size, primer_size, mismatches, max_product):
+    """why --out_panel_products / --out_panel_summary are not taken (one line), or None.  panel: --panel's value or None;
+    out_products, out_summary: whether the options are given; mismatches, max_product: the figures after the defaults"""
+    if not (out_products or out_summary):
+        return None
+    if panel is None:
+        return f"{'--out_panel_products' if out_products else '--out_panel_summary'} needs --panel (the oligos it searches for)"
+    if mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES:
+        return f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    if max_product < amp_size[1]:
+        return (f"--max-product must be at least the upper bound of --amp_size, {amp_size[1]} bases (got {max_product}): a "
+                "member's designed product itself would not be found")
+    if max_product < 2 * primer_size[1]:
+        return (f"--max-product must be at least twice the upper bound of --primer_size, {2 * primer_size[1]} bases (got "
+                f"{max_product}): two oligos of the panel would not fit one product")
+    if max_product >= 1 << 31:
+        return f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    return None
+
+
+def panel_oligos(templates, records, order, members):
+    """The oligos of a panel in index order, 2 (member - 1) + side with L = 0 and R = 1 -> a list of (name, text): the names
+    1L, 1R, 2L, ..., the texts 5'->3' exactly as write_panel prints left_sequence and right_sequence.  templates, records,
+    order, members: as write_panel takes them"""
+    out = []
+    for j, m in enumerate(members):
+        i = int(order[int(m["position"])])
+        r = records[i]
+        t = bytes(templates[i]).decode("ascii")
+        ls, ln, rs, rn = (int(r[k]) for k in ("left_start", "left_len", "right_start", "right_len"))
+        out.append((f"{j + 1}L", t[ls:ls + ln]))
+        out.append((f"{j + 1}R", _guide_rc(t[rs:rs + rn])))
+    return out
+
+
+def panel_kind(i, j):
+    """what the product of oligo i (forward) and oligo j (reverse) is: `single` the same oligo twice, `pair` the two oligos
+    of one member in either order, `cross` everything else -- an oligo with its twin in another member too"""
+    return "single" if i == j else "pair" if i // 2 == j // 2 else "cross"
+
+
+def panel_texts(oligos):
+    """the table of the multiplex pass: equal texts once, ordered by their bytes -> (texts, owners): owners[t] = the indexes
+    of the oligos whose text is texts[t], ascending"""
+    texts = sorted({text.encode("ascii") for _, text in oligos})
+    at = {t: n for n, t in enumerate(texts)}
+    owners = [[] for _ in texts]
+    for i, (_, text) in enumerate(oligos):
+        owners[at[text.encode("ascii")]].append(i)
+    return texts, owners
+
+
+def _panel_fan_out(fwd, rev, owners):
+    """a product of the texts (fwd, rev) is a row for every oligo of fwd with every oligo of rev -> (rep, forward oligo,
+    reverse oligo): output row j repeats product rep[j]"""
+    rep, fi = _fan_out(fwd, owners)
+    rep2, ri = _fan_out(rev[rep], owners)
+    return rep[rep2], fi[rep2].astype(np.int64), ri.astype(np.int64)
+
+
+def panel_products(oligos, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1, max_product=1000, omit_soft=False,
+                   device=0, rows=True):
+    """Multiplex in-silico PCR: with all the oligos of a panel (panel_oligos) in one tube, what do they amplify
+    in every input genome?  Every oligo can open a product and every oligo can close one: a site is primer_products' site, a
+    product is a site of the forward oligo as written and, downstream on the same record and not overlapping it, a site of
+    the reverse oligo's reverse complement, at most `max_product` bases from end to end.  One pass over the inputs on one
+    device (kr_multiplex_*).  -> (PANEL_PRODUCT array, PANEL_SUMMARY array): the rows by file in the order given,
+    record_index, start, end, forward oligo, reverse oligo; the summary -- a row per file and ordered oligo pair with a
+    product, from the device's tally -- by file, forward, reverse.  An oligo's text that several oligos share gives a row
+    for each of them.  rows=False: no product comes to the host, the first array is empty.  ValueError for figures the pass
+    does not take"""
+    why = None
+    if mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES:
+        why = f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    elif max_product >= 1 << 31:
+        why = f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    for name, text in oligos:
+        if why is None and not (PANEL_MIN_OLIGO <= len(text) <= PANEL_MAX_OLIGO and set(text) <= set("ACGT")):
+            why = f"panel_products: oligo {name} is not {PANEL_MIN_OLIGO} .. {PANEL_MAX_OLIGO} letters of A, C, G, T"
+        elif why is None and max_product < 2 * len(text):
+            why = f"--max-product must be at least twice the longest oligo, {2 * len(text)} bases (got {max_product})"
+    texts, owners = panel_texts(oligos)
+    if why is None and len(texts) > PANEL_MAX_OLIGO_TEXTS:
+        why = f"panel_products: {len(texts)} distinct oligos (the limit is {PANEL_MAX_OLIGO_TEXTS})"
+    if why is not None:
+        raise ValueError(why)
+    if not texts:
+        return np.empty(0, dtype=PANEL_PRODUCT), np.empty(0, dtype=PANEL_SUMMARY)
+    files = list(ingroup_files) + list(outgroup_files)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    names = np.array([name for name, _ in oligos], dtype=object)
+    kinds = np.array([[panel_kind(i, j) for j in range(len(oligos))] for i in range(len(oligos))], dtype=object)
+    parts, sums = [], []
+    for eng, fi, path, _rna, recs in _scan_genomes(files, Le, De, Re, k, omit_soft, device,
+                                                   lambda eng: eng.multiplex_table(texts, mismatches, max_product)):
+        hits = eng.multiplex_products(0) if rows else None
+        if (len(hits) if rows else eng.multiplex_scan(0)) == 0:
+            continue
+        tally = eng.multiplex_tally()
+        a, b = np.nonzero(tally.sum(axis=2))
+        rep, fo, ro = _panel_fan_out(a.astype(np.int64), b.astype(np.int64), owners)
+        part = np.empty(len(rep), dtype=PANEL_SUMMARY)
+        part["file"] = path
+        part["forward_index"], part["reverse_index"] = fo, ro
+        part["forward"], part["reverse"], part["kind"] = names[fo], names[ro], kinds[fo, ro]
+        part["products"] = tally[a, b].sum(axis=1)[rep]
+        part["clean_end_products"] = tally[a, b, 1][rep]
+        sums.append(part[np.lexsort((ro, fo))])
+        if not rows:
+            continue
+        seps, ids = recs()
+        rep, fo, ro = _panel_fan_out(hits["fwd"].astype(np.int64), hits["rev"].astype(np.int64), owners)
+        hits = hits[rep]
+        part = np.empty(len(hits), dtype=PANEL_PRODUCT)
+        ri, start = _record_coords(seps, hits["pos"].astype(np.int64))
+        part["file"] = path
+        part["record"] = np.asarray(ids, dtype=object)[ri]
+        part["record_index"], part["start"], part["length"] = ri, start, hits["length"]
+        part["end"] = part["start"] + part["length"]
+        part["forward_index"], part["reverse_index"] = fo, ro
+        part["forward"], part["reverse"], part["kind"] = names[fo], names[ro], kinds[fo, ro]
+        for side, src in (("forward", "fwd"), ("reverse", "rev")):
+            part[side + "_mismatches"] = hits[src + "_mm"]
+            part[side + "_end_mismatches"] = hits[src + "_end_mm"]
+        # (positions ascend with (record_index, start); a position's rows by end, then by the oligos)
+        parts.append(part[np.lexsort((ro, fo, hits["length"], hits["pos"]))])
+    return (np.concatenate(parts) if parts else np.empty(0, dtype=PANEL_PRODUCT),
+            np.concatenate(sums) if sums else np.empty(0, dtype=PANEL_SUMMARY))
+
+
+def write_panel_products(path, rows):
+    """the TSV of --out_panel_products: PANEL_PRODUCT_HEADER, then panel_products' rows"""
+    _write_tsv(path, PANEL_PRODUCT_HEADER, rows, PANEL_PRODUCT_HEADER.split("\t"))
+
+
+def write_panel_summary(path, summary):
+    """the TSV of --out_panel_summary: PANEL_SUMMARY_HEADER, then panel_products' summary"""
+    _write_tsv(path, PANEL_SUMMARY_HEADER, summary, PANEL_SUMMARY_HEADER.split("\t"))
