@@ -398,6 +398,13 @@ int64_t kr_primers_scan(kr_ctx*, int id);
 int64_t kr_primers_fetch(kr_ctx*, kr_product_hit* out, size_t cap);
 /* the sites of the latest scan, as the device lists them.  Returns their number; out == NULL: the number only */
 int64_t kr_primers_sites(kr_ctx*, kr_product_site* out, size_t cap);
+/* the products of the latest scan counted on the device (krisp_fasta --primer-candidates; csrc/k_primers.inc:
+ * k_prim_tally), eight uint32 per pair of the table: out[8 p + m] = pair p's products with left_mm + right_mm = m, m = 0 ..
+ * 6, out[8 p + 7] = those with left_end_mm = right_end_mm = 0.  The list on the device is only read: no product comes to
+ * the host.  Integer adds: the same bytes on every run.  cap counts uint32; returns 8 npairs.  Zeros without a launch where
+ * the table has no pair or the scan found no product; KR_ERR_STATE "kr_primers_scan first" before a scan of the standing
+ * table, KR_ERR_CAPACITY for a buffer below 8 npairs. */
+int64_t kr_primers_tally(kr_ctx*, uint32_t* out, size_t cap);
 
 /* ---- a primer pair per region (krisp_fasta --design-primers) -----------------------------------------------------------
  * Replaces no seam of the reference: it designs with the third-party Primer3.  This is a small designer of its own whose
@@ -452,6 +459,20 @@ int kr_design_hairpins(kr_ctx*, const kr_hairpin_params* params);
  * 0 and 0 for a region without a pair; cap counts int32.  Returns the number of int32 written, two per region.
  * KR_ERR_STATE when that run had the check off.  kr_design_record does not change with the check. */
 int64_t kr_design_fetch_hairpins(kr_ctx*, int32_t* out, size_t cap);
+/* The shortlist (krisp_fasta --primer-candidates): a region's passing pairs are kr_design_run's, under the
+ * hairpin check too; in ascending (pair_penalty, left_start, left_len, right_start, right_len) order -- a total order, the
+ * key holds the positions -- the first `top` of them are the region's shortlist, rank 1 the pair kr_design_run picks.  It
+ * runs in csrc/k_design.inc (k_design_top): k_design's branch-and-bound with the top-th least accepted key as the bound.
+ * kr_design_run_top: kr_design_run's arguments, checks and batches, 1 <= top <= 8 (KR_ERR_PARAM otherwise).  Returns the
+ * number of regions with a pair.  The records and the state are its own: a kr_design_run neither changes nor satisfies
+ * them, and the other way round; kr_design_table drops both. */
+int64_t kr_design_run_top(kr_ctx*, const uint8_t* templates, uint64_t nregions, int L, int D, int R, int top);
+/* the records of the latest kr_design_run_top, region-major: out[r top + j] = the pair of rank j + 1 of region r, with every
+ * figure of a kr_design_record; all zero where the region has fewer pairs.  Returns nregions * top */
+int64_t kr_design_fetch_top(kr_ctx*, kr_design_record* out, size_t cap);
+/* ... and their hairpin figures: out[2 (r top + j)] the left and out[2 (r top + j) + 1] the right primer's; KR_ERR_STATE
+ * when that run had the check off */
+int64_t kr_design_fetch_top_hairpins(kr_ctx*, int32_t* out, size_t cap);
 
 /* ---- N mutually compatible assays of the designed pairs (krisp_fasta --panel) -------------------------------------------
  * Replaces no seam of the reference, which selects nothing.  Of ncand candidates in the caller's order -- a template of W

@@ -141,6 +141,10 @@ SYMBOLS = [
     ("kr_design_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_design_hairpins", _c.c_int, [_P, _P]),
     ("kr_design_fetch_hairpins", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_design_run_top", _c.c_int64, [_P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    ("kr_design_fetch_top", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_design_fetch_top_hairpins", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_primers_tally", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_panel_run", _c.c_int64, [_P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int]),
     ("kr_panel_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_panel_fates", _c.c_int64, [_P, _P, _c.c_size_t]),
@@ -860,9 +864,11 @@ class Engine:
         offsets[1:] = np.cumsum([len(t) for t in texts], dtype=np.int64)
         text = np.frombuffer(b"".join(texts) + b"\0", dtype=np.uint8)      # (never empty: a pointer to pass)
         pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
-        return self._check(self.lib.kr_primers_table(self.ctx, _ptr(text), _ptr(offsets), nleft, len(texts) - nleft,
-                                                     _ptr(pr) if pr.size else None, len(pr), mismatches, max_product),
-                           "kr_primers_table")
+        slots = self._check(self.lib.kr_primers_table(self.ctx, _ptr(text), _ptr(offsets), nleft, len(texts) - nleft,
+                                                      _ptr(pr) if pr.size else None, len(pr), mismatches, max_product),
+                            "kr_primers_table")
+        self._primer_pairs = len(pr)                  # (primers_tally's rows; a refused table leaves no table)
+        return slots
 
     def primer_products(self, gid):
         """PRODUCT_HIT array of uploaded genome gid in (pos, length, strand, pair) order (kr_primers_scan)"""
@@ -877,6 +883,14 @@ class Engine:
         """scans uploaded genome gid against the primer table and leaves the products on the device -> their number
         (kr_primers_scan)"""
         return self._check(self.lib.kr_primers_scan(self.ctx, gid), "kr_primers_scan")
+
+    def primers_tally(self):
+        """the products of the latest primers_scan() / primer_products() counted on the device: uint32 [pairs, 8], column m
+        = the pair's products with left_mm + right_mm = m (0 .. 6), column 7 = those without a mismatch at either 3' end
+        (kr_primers_tally)"""
+        out = np.zeros((max(getattr(self, "_primer_pairs", 0), 1), 8), dtype=np.uint32)
+        n = self._check(self.lib.kr_primers_tally(self.ctx, _ptr(out), out.size), "kr_primers_tally")
+        return out[:n // 8]
 
     def guide_hits_scan(self, gid):
         """scans uploaded genome gid against the guides' table and leaves the hits on the device -> their number
@@ -962,6 +976,26 @@ class Engine:
         for name in DESIGN_RECORD.names:
             both[name] = out[name][:len(t)]
         both["left_hairpin"], both["right_hairpin"] = hp[:len(t), 0], hp[:len(t), 1]
+        return both
+
+    def design_top(self, templates, L, D, R, top):
+        """as design(), for the `top` (1 .. 8) passing pairs of least (penalty, left_start, left_len, right_start, right_len)
+        of every region -> DESIGN_RECORD [regions, top]: column j is the pair of rank j + 1, column 0 design()'s record, all
+        zero where the region has fewer (kr_design_run_top, kr_design_fetch_top); after design_hairpins(params)
+        DESIGN_RECORD_HP [regions, top] with every slot's two hairpin figures (kr_design_fetch_top_hairpins)"""
+        t = np.ascontiguousarray(templates, dtype=np.uint8).reshape(-1, L + D + R)
+        self._check(self.lib.kr_design_run_top(self.ctx, _ptr(t) if t.size else None, len(t), L, D, R, top), "kr_design_run_top")
+        n = len(t)
+        out = np.empty((max(n, 1), top), dtype=DESIGN_RECORD)
+        self._check(self.lib.kr_design_fetch_top(self.ctx, _ptr(out), n * top), "kr_design_fetch_top")
+        if not getattr(self, "_design_hairpins", False):
+            return out[:n]
+        hp = np.empty((max(n, 1), top, 2), dtype=np.int32)
+        self._check(self.lib.kr_design_fetch_top_hairpins(self.ctx, _ptr(hp), 2 * n * top), "kr_design_fetch_top_hairpins")
+        both = np.empty((n, top), dtype=DESIGN_RECORD_HP)
+        for name in DESIGN_RECORD.names:
+            both[name] = out[name][:n]
+        both["left_hairpin"], both["right_hairpin"] = hp[:n, :, 0], hp[:n, :, 1]
         return both
 
     def panel(self, templates, pairs, size):

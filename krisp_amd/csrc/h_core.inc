@@ -333,7 +333,8 @@ struct kr_ctx {
         u32 smin = 0, maxlen = 0;
         int gid = -1;                   // the genome of the latest kr_primers_scan
         DevBuf eoff, plen;              // plen: pair p's two text lengths (left | right << 16), what the assay join reads
-        void bufs(Bufs& v) { Prod::bufs(v); v.insert(v.end(), {&eoff, &plen}); }
+        DevBuf pair_tally;              // kr_primers_tally's counters
+        void bufs(Bufs& v) { Prod::bufs(v); v.insert(v.end(), {&eoff, &plen, &pair_tally}); }
     } prim;
     // the assay join (kr_assay_*: h_assay.inc), in the same context: the links (primer pair << 32 | guide, ascending) and the
     // assay hits of the latest join of prim's products with ghit's hits.  on: a link table stands (it may be empty)
@@ -357,9 +358,14 @@ struct kr_ctx {
         kr_design_params params{};
         int64_t nrec = -1;
         bool hp = false, hp_ran = false;        // kr_design_hairpins is on; the latest run had it on
-        DevBuf par, tmpl, rec, hprec;
+        DevBuf par, tmpl, rec, hprec;           // (tmpl, rec, hprec: a batch's; kr_design_run and kr_design_run_top take turns on them)
         std::vector<kr_design_record> out;      // the records of the latest run, all batches
         std::vector<int32_t> hp_out;            // ... and, with the hairpin check, its two figures a region
+        // kr_design_run_top's own list and state: regions * top records, region-major, and two figures a record
+        int64_t top_nrec = -1;
+        bool top_hp_ran = false;
+        std::vector<kr_design_record> top_out;
+        std::vector<int32_t> top_hp_out;
     } design;
     // the panel pass (kr_panel_*: h_panel.inc): all candidates resident, the model and max_sec are design's
     struct Panel {

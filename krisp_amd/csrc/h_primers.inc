@@ -4,7 +4,7 @@
 // the texts bring their own lengths): one genome resident at a time.  Beside the genome live the entries' text (2 bytes a
 // letter of a text) and their offsets (8 bytes a text), the table (16 bytes a slot, >= 2 slots a distinct piece), the entry
 // list (8 (M + 1) bytes a text), the bitmap, the pair list (12 bytes a pair), the separators (8 bytes each), the sites
-// (16 + 4 bytes each) and the products (24 bytes each).  The scan behind the prologue, the join, the fetch and the sites are
+// (16 + 4 bytes each), the products (24 bytes each) and kr_primers_tally's counters (32 bytes a pair).  The scan behind the prologue, the join, the fetch and the sites are
 // h_products.inc's (prod_scan, prod_fetch, prod_sites), with this pass's kernels and the entries' offsets.
 #define PRIM_MIN_LEN 10             // the lengths kr_design_table takes for a primer
 #define PRIM_MAX_LEN 60
@@ -147,3 +147,31 @@ int64_t kr_primers_scan(kr_ctx* c, int id) {
 int64_t kr_primers_fetch(kr_ctx* c, kr_product_hit* out, size_t cap) { return prod_fetch(c, true, "kr_primers_scan first", out, cap); }
 
 int64_t kr_primers_sites(kr_ctx* c, kr_product_site* out, size_t cap) { return prod_sites(c, true, "kr_primers_scan first", out, cap); }
+
+// the products of the latest scan counted per pair (k_prim_tally): out[8 p + m] = pair p's products with m mismatches in
+// their two sites together, out[8 p + 7] = those without a mismatch at either 3' end; 8 npairs counters
+int64_t kr_primers_tally(kr_ctx* c, uint32_t* out, size_t cap) {
+    int rc;
+    if ((rc = scan_ctx(c))) return rc;
+    auto& pm = c->prim;
+    if (pm.nhits < 0) return fail(c, KR_ERR_STATE, "kr_primers_scan first");
+    const u64 npairs = pm.plist.npairs, n = 8 * npairs;
+    if (npairs >= (1ull << 29)) return fail(c, KR_ERR_CAPACITY, "kr_primers_tally: %llu pairs (the counters' index has 32 bits)", (unsigned long long)npairs);
+    if (n > cap) return fail(c, KR_ERR_CAPACITY, "kr_primers_tally: tally buffer too small: %llu > %zu", (unsigned long long)n, cap);
+    if (!n) return 0;
+    if (!out) return fail(c, KR_ERR_PARAM, "kr_primers_tally: null argument");
+    if (!pm.nhits) {
+        memset(out, 0, n * sizeof(u32));
+        return (int64_t)n;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, pm.pair_tally, n * sizeof(u32)))) return rc;
+    HIPCHK(c, hipMemsetAsync(pm.pair_tally.p, 0, n * sizeof(u32), c->stream));
+    const u64 nhits = (u64)pm.nhits;
+    hipLaunchKernelGGL(k_prim_tally, dim3(scan_stride_grid(c, (nhits + 255) / 256)), dim3(256), 0, c->stream,
+                       (const kr_product_hit*)pm.hits.p, nhits, (u32)npairs, (u32*)pm.pair_tally.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, pm.pair_tally.p, n * sizeof(u32), hipMemcpyDeviceToHost));
+    return (int64_t)n;
+}

@@ -18,6 +18,8 @@
 // table (54 ints, loop lengths 3 .. 56) lies in LDS behind the model's, 1b runs des_hairpin on a survivor of 1a before its
 // self duplex, and 3 stores the winner's two figures into a second array of 8 bytes a region.  k_design<false> is the
 // kernel without any of it.
+// k_design_top (kr_design_run_top, DESIGN §25; behind k_design below) keeps the `top` least passing pairs of a region in
+// the place of the least: 2's bound is the top-th least key so far, 3 runs once per slot.
 #define DES_T 64
 #define DES_DEAD 0xffffffffu
 #define DES_TAB 48                  // ints of the table in LDS: nn_dh 16, nn_ds 16, term_dh 4, term_ds 4 (40, padded)
@@ -342,5 +344,243 @@ __global__ __launch_bounds__(DES_T) void k_design(const uint8_t* __restrict__ te
         int2 hp = make_int2(0, 0);
         if (found) hp = make_int2(des_hairpin(tab, loop, A, ls, ln, salt, lane), des_hairpin(tab, loop, B, ur, rn, salt, lane));
         if (lane == 0) hp_out[region] = hp;
+    }
+}
+
+__device__ __forceinline__ u64 des_shfl64(u64 v, int l) {
+    return ((u64)(u32)__shfl((int)(v >> 32), l, 64) << 32) | (u32)__shfl((int)(u32)v, l, 64);
+}
+
+// ---- the shortlist kernel of --primer-candidates (DESIGN §25).  k_design_top's steps are the inline pieces below: des_tables
+// (the tables, 1a and 1b, statement for statement k_design's) and des_record (3 for one key, which k_design_top runs per
+// slot).  k_design above does not call them: built from these pieces it computes the same records but compiles to other
+// registers (60 VGPRs and 95 / 90 SGPRs against 62 and 93 / 88), and the pass that every run of --design-primers takes keeps
+// the code it was measured with.  A change to a step of k_design belongs in both places; tests/test_gpu_design_shortlist.py
+// holds slot 0 of k_design_top to k_design's bytes.
+//
+// des_tables: the model's table, both sides' codes, prefixes and penalty tables of `region` in the LDS at `lds`, the
+// survivors of 1a and 1b marked -> S[0], S[1]; ends with a barrier
+template <bool HP>
+__device__ __forceinline__ void des_tables(unsigned char* const lds, const uint8_t* __restrict__ templates, u32 region, u32 lane,
+                                           const DesignGeom& g, const kr_design_params* __restrict__ P, DesSide (&S)[2]) {
+    int* const tab = (int*)lds;
+    const int* const loop = tab + DES_TAB;
+    uint8_t* codew[2];
+    int* phw[2];
+    int* psw[2];
+    u32* pcw[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        codew[q] = lds + g.o_code[q];
+        phw[q] = (int*)(lds + g.o_ph[q]);
+        psw[q] = (int*)(lds + g.o_ps[q]);
+        pcw[q] = (u32*)(lds + g.o_pc[q]);
+        S[q].code = codew[q]; S[q].ph = phw[q]; S[q].ps = psw[q]; S[q].pc = pcw[q];
+        S[q].pen = (u32*)(lds + g.o_pen[q]);
+        S[q].len = g.len[q]; S[q].nlen = g.nlen[q];
+    }
+    const int lo = P->size_lo, hi = P->size_hi, salt = P->salt_ds, conc = P->conc_ds, max_sec = P->max_sec;
+
+    // ---- the table, the codes of both sides
+    if (lane < 40) tab[lane] = ((const int*)P)[lane];
+    if (HP && lane < DES_MAX_LOOP - DES_MIN_LOOP + 1) tab[DES_TAB + lane] = ((const int*)(P + 1))[DES_MIN_LOOP + lane];
+    const uint8_t* T = templates + (u64)region * g.W;
+    for (u32 i = lane; i < g.L; i += DES_T) codew[0][i] = (uint8_t)des_code(T[i]);
+    for (u32 i = lane; i < g.R; i += DES_T) {
+        const u32 cd = des_code(T[g.W - 1 - i]);
+        codew[1][i] = (uint8_t)(cd < 4u ? 3u - cd : 4u);
+    }
+    __syncthreads();
+
+    // ---- prefix sums along each side, 64 positions a step: entry i + 1 holds the steps (i, i + 1) .. and the letters .. i
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const u32 n = g.len[q];
+        int ch = 0, cs = 0, cc = 0;
+        if (lane == 0) { phw[q][0] = 0; psw[q][0] = 0; pcw[q][0] = 0; }
+        for (u32 base = 0; base < n; base += DES_T) {
+            const u32 i = base + lane;
+            int h = 0, s = 0, cnt = 0;
+            if (i < n) {
+                const u32 a = codew[q][i];
+                if (i + 1 < n) {
+                    const u32 b = codew[q][i + 1];
+                    if (a < 4u && b < 4u) { h = tab[4 * a + b]; s = tab[16 + 4 * a + b]; }
+                }
+                bool five = i >= 4;
+                for (u32 k = 1; five && k < 5; k++) five = codew[q][i - k] == a;
+                cnt = (int)((a == 1u || a == 2u) ? 1u : 0u) | (int)((a >= 4u ? 1u : 0u) << 10) | (int)((five ? 1u : 0u) << 20);
+            }
+            h = des_wave_scan(h, lane) + ch;
+            s = des_wave_scan(s, lane) + cs;
+            cnt = des_wave_scan(cnt, lane) + cc;          // (three 10-bit counts, none above 1023: no carry between them)
+            if (i < n) { phw[q][i + 1] = h; psw[q][i + 1] = s; pcw[q][i + 1] = (u32)cnt; }
+            ch = __shfl(h, 63, 64); cs = __shfl(s, 63, 64); cc = __shfl(cnt, 63, 64);
+        }
+    }
+    __syncthreads();
+
+    // ---- 1a: a lane per candidate
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const DesSide& X = S[q];
+        const u32 total = X.nlen * X.len;
+        for (u32 e = lane; e < total; e += DES_T) {
+            const u32 n = (u32)lo + e / X.len, u = e % X.len;
+            u32 pen = DES_DEAD;
+            if (u + n <= X.len) {
+                const u32 pe = X.pc[u + n], pu = X.pc[u];
+                const int gc = (int)(pe & 1023u) - (int)(pu & 1023u);
+                const bool letters = ((pe >> 10) & 1023u) == ((pu >> 10) & 1023u);
+                const bool poly = (pe >> 20) != (X.pc[u + 4] >> 20);
+                const int clamp = (int)(pe & 1023u) - (int)(X.pc[u + n - (u32)P->gc_clamp] & 1023u);
+                const int endgc = (int)(pe & 1023u) - (int)(X.pc[u + n - 5] & 1023u);
+                if (letters && !poly && 100 * gc >= P->gc_lo * (int)n && 100 * gc <= P->gc_hi * (int)n && clamp == P->gc_clamp &&
+                    endgc <= P->max_end_gc) {
+                    const int tm = des_oligo_tm(tab, X, u, n, P);
+                    if (tm >= P->tm_lo && tm <= P->tm_hi) pen = (u32)(abs(tm - P->tm_opt) + 500 * abs(2 * (int)n - (lo + hi)));
+                }
+            }
+            X.pen[e] = pen;
+        }
+    }
+    __syncthreads();
+
+    // ---- 1b: the wave per survivor: (its hairpin figure,) self_any and self_end
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const DesSide& X = S[q];
+        const u32 total = X.nlen * X.len;
+        for (u32 base = 0; base < total; base += DES_T) {
+            const u32 e = base + lane;
+            u64 mask = __ballot(e < total && X.pen[e] != DES_DEAD);
+            while (mask) {
+                const u32 e2 = base + (u32)__ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const u32 n = (u32)lo + e2 / X.len, u = e2 % X.len;
+                if (HP && des_hairpin(tab, loop, X, u, n, salt, lane) > max_sec) {
+                    if (lane == 0) X.pen[e2] = DES_DEAD;
+                    continue;
+                }
+                int any, end;
+                des_duplex(tab, X, u, n, X, u, n, salt, conc, lane, &any, &end);
+                if ((any > max_sec || end > max_sec) && lane == 0) X.pen[e2] = DES_DEAD;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// 3: the record of the pair `key` names (des_key; ~0: no pair, all zero) at out, by plain vector stores of lane 0, and for HP
+// its two hairpin figures at hp_out.  Every figure is computed again by the whole wave
+template <bool HP>
+__device__ __forceinline__ void des_record(const int* tab, const DesSide& A, const DesSide& B, const DesignGeom& g,
+                                           const kr_design_params* __restrict__ P, u32 lane, u64 key,
+                                           kr_design_record* __restrict__ out, int2* __restrict__ hp_out) {
+    const int* const loop = tab + DES_TAB;
+    const int lo = P->size_lo, salt = P->salt_ds, conc = P->conc_ds;
+    const bool found = key != ~0ull;
+    const u32 ls = found ? (u32)(key >> 23) & 2047u : 0u, ln = found ? (u32)(key >> 17) & 63u : (u32)lo;
+    const u32 rs = found ? (u32)(key >> 6) & 2047u : g.W - (u32)lo, rn = found ? (u32)key & 63u : (u32)lo;
+    const u32 ur = g.W - rs - rn;
+    int lsa = 0, lse = 0, rsa = 0, rse = 0, pa = 0, pe = 0;
+    uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0;
+    if (found) {
+        des_duplex(tab, A, ls, ln, A, ls, ln, salt, conc, lane, &lsa, &lse);
+        des_duplex(tab, B, ur, rn, B, ur, rn, salt, conc, lane, &rsa, &rse);
+        des_duplex(tab, A, ls, ln, B, ur, rn, salt, conc, lane, &pa, &pe);
+        // (kr_design_record, little endian: found, product_size, pair_penalty, the four u16 of the pair; the two Tm, the
+        // two u16 GC counts, the two penalties)
+        w0 = make_uint4(1u, rs + rn - ls, (u32)(key >> 34), ls | (ln << 16));
+        w1 = make_uint4(rs | (rn << 16), (u32)des_oligo_tm(tab, A, ls, ln, P), (u32)des_oligo_tm(tab, B, ur, rn, P),
+                        ((A.pc[ls + ln] & 1023u) - (A.pc[ls] & 1023u)) | (((B.pc[ur + rn] & 1023u) - (B.pc[ur] & 1023u)) << 16));
+    }
+    if (lane == 0) {
+        uint4* o = (uint4*)out;
+        o[0] = w0;
+        o[1] = w1;
+        o[2] = found ? make_uint4(A.pen[(ln - (u32)lo) * A.len + ls], B.pen[(rn - (u32)lo) * B.len + ur], (u32)lsa, (u32)lse) : w0;
+        o[3] = make_uint4((u32)rsa, (u32)rse, (u32)pa, (u32)pe);
+    }
+    if (HP) {
+        int2 hp = make_int2(0, 0);
+        if (found) hp = make_int2(des_hairpin(tab, loop, A, ls, ln, salt, lane), des_hairpin(tab, loop, B, ur, rn, salt, lane));
+        if (lane == 0) *hp_out = hp;
+    }
+}
+
+// k_design_top (--primer-candidates, DESIGN §25): the `top` least keys of a region's passing pairs, 1 <= top <= DES_MAX_TOP,
+// as records out[region * top + j], j = rank - 1, and for HP their hairpin figures hp_out[region * top + j]; a slot beyond
+// the region's pairs is zero.  The tables, 1a and 1b are k_design's.  2 is its branch-and-bound with the bound at the
+// top-th least accepted key so far (~0 while fewer are held): the row skip, the ballot and the re-test read that bound, a
+// pair enters the list only after its pair duplex passes, and every (el, er) is visited once, so no key enters twice.  The
+// list is one register a lane: lane j holds the (j + 1)-th least accepted key, ~0 behind the last, ascending over the wave.
+// An insert is a ballot of the lanes whose key is greater, a __shfl_up of those lanes and the new key into the first of
+// them (what falls off lane top - 1 moves on to the lanes behind it, which nothing reads); the bound is a __shfl of lane
+// top - 1.  Every value of 2 is wave-uniform but that register: no indexed array, no scratch.  3 runs once per slot.
+#define DES_MAX_TOP 8
+
+template <bool HP>
+__global__ __launch_bounds__(DES_T) void k_design_top(const uint8_t* __restrict__ templates, u32 nregions, DesignGeom g,
+                                                      const kr_design_params* __restrict__ P, u32 top,
+                                                      kr_design_record* __restrict__ out, int2* __restrict__ hp_out) {
+    extern __shared__ __align__(16) u32 des_lds[];
+    const u32 region = blockIdx.x, lane = threadIdx.x;
+    if (region >= nregions) return;
+    const int* const tab = (const int*)des_lds;
+    DesSide S[2];
+    des_tables<HP>((unsigned char*)des_lds, templates, region, lane, g, P, S);
+    const int lo = P->size_lo, salt = P->salt_ds, conc = P->conc_ds, max_sec = P->max_sec;
+
+    // ---- 2: the top least pairs
+    const DesSide& A = S[0];
+    const DesSide& B = S[1];
+    const u32 totl = A.nlen * A.len, totr = B.nlen * B.len;
+    u32 minr = DES_DEAD;
+    for (u32 e = lane; e < totr; e += DES_T) minr = min(minr, B.pen[e]);
+    minr = des_wave_min(minr);
+    u64 mine = ~0ull, bound = ~0ull;                // this lane's key of the list; the key of lane top - 1
+    if (minr != DES_DEAD) {
+#pragma unroll 1
+        for (u32 el = 0; el < totl; el++) {
+            const u32 pl = A.pen[el];
+            if (pl == DES_DEAD || (u64)pl + minr > (bound >> 34)) continue;
+            const u32 nl = (u32)lo + el / A.len, ul = el % A.len;
+            for (u32 base = 0; base < totr; base += DES_T) {
+                const u32 er = base + lane;
+                u64 key = ~0ull;
+                if (er < totr) {
+                    const u32 pr = B.pen[er];
+                    if (pr != DES_DEAD) {
+                        const u32 nr = (u32)lo + er / B.len, ur = er % B.len;
+                        const int size = (int)(g.W - ur - ul);
+                        if (size >= P->amp_lo && size <= P->amp_hi) key = des_key(pl + pr, ul, nl, g.W - ur - nr, nr);
+                    }
+                }
+                u64 mask = __ballot(key < bound);
+                while (mask) {
+                    const int l = __ffsll((long long)mask) - 1;
+                    mask &= mask - 1;
+                    const u64 k = des_shfl64(key, l);
+                    if (k >= bound) continue;
+                    const u32 e2 = base + (u32)l;
+                    int any, end;
+                    des_duplex(tab, A, ul, nl, B, e2 % B.len, (u32)lo + e2 / B.len, salt, conc, lane, &any, &end);
+                    if (any > max_sec || end > max_sec) continue;
+                    // (k < bound <= the key of every lane from top - 1 on: a greater lane there is, the first of them takes k)
+                    const u64 up = ((u64)(u32)__shfl_up((int)(mine >> 32), 1, 64) << 32) | (u32)__shfl_up((int)(u32)mine, 1, 64);
+                    const u32 first = (u32)__ffsll((long long)__ballot(mine > k)) - 1u;
+                    mine = lane < first ? mine : lane == first ? k : up;
+                    bound = des_shfl64(mine, (int)top - 1);
+                }
+            }
+        }
+    }
+
+    // ---- 3: the records, a slot a turn
+#pragma unroll 1
+    for (u32 j = 0; j < top; j++) {
+        const u64 slot = (u64)region * top + j;
+        des_record<HP>(tab, A, B, g, P, lane, des_shfl64(mine, (int)j), out + slot, HP ? hp_out + slot : nullptr);
     }
 }

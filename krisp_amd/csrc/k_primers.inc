@@ -17,7 +17,7 @@
 // end) ends the window -- it is no mismatch.  Count per tile, k_loc_offsets, emit on a second visit: sites in position
 // order, at one position by piece and list order.  k_prim_join: a thread per OPENING site walks the following sites of
 // its record up to pos + max_product - smin and tests every CLOSING site with the two entries' own lengths.  No atomics:
-// the same bytes on every run.
+// the same bytes on every run.  k_prim_tally (at the end) counts the product list per pair with integer adds.
 
 struct PrimGeom {
     u32 smin, maxlen;               // the shortest and the longest text
@@ -197,4 +197,28 @@ __global__ __launch_bounds__(LOC_T) void k_prim_join(const kr_product_site* __re
         hit.pad[0] = hit.pad[1] = hit.pad[2] = 0;
         *o++ = hit;
     });
+}
+
+// k_prim_tally (--primer-candidates, DESIGN §25): tally[8 pair + m] += the products of that pair whose two sites hold m
+// mismatches together, m = 0 .. 6, and tally[8 pair + 7] += those of them without a mismatch at either 3' end; the list is
+// only read.  A wavefront takes 64 neighbouring products, in two turns of tally_runs (k_scan.inc): a run of equal keys among
+// them -- a repeat sends most of a genome's products to one pair -- is one integer add of its length.  A product that names
+// no pair of the table or a site with more than 3 mismatches (there is none unless the join is broken) is not counted: no
+// add outside the 8 npairs counters
+__global__ __launch_bounds__(256) void k_prim_tally(const kr_product_hit* __restrict__ hits, u64 nhits, u32 npairs, u32* __restrict__ tally) {
+    const u32 lane = threadIdx.x & 63u;
+    // (the loop's bounds are the wavefront's: every lane of it takes every turn, the shuffle and the ballot are whole)
+    for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < nhits; base += (u64)gridDim.x * 256) {
+        const u64 i = base + lane;
+        u32 key = ~0u, clean = ~0u;
+        if (i < nhits) {
+            const kr_product_hit h = hits[i];
+            if (h.pair < npairs && h.left_mm < 4u && h.right_mm < 4u) {
+                key = 8u * h.pair + h.left_mm + h.right_mm;
+                if (h.left_end_mm == 0 && h.right_end_mm == 0) clean = 8u * h.pair + 7u;
+            }
+        }
+        tally_runs(key, lane, tally);
+        tally_runs(clean, lane, tally);
+    }
 }

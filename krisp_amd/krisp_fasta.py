@@ -40,6 +40,8 @@ from .reports import (                                                        # 
     near_refusal, near_targets, pick_guides, predict_products, primer_pairs, primer_products, primer_products_refusal,
     products_refusal, shortlist_texts, write_assay_hits, write_guide_bulge_hits, write_guide_candidates, write_guide_hits,
     write_guides, write_locations, write_near, write_products,
+    PRIMER_CANDIDATE_HEADER, PRIMER_MAX_CANDIDATES, design_primer_shortlist, pick_pairs, primer_candidates_refusal,
+    primer_tallies, shortlist_pairs, write_primer_candidates,
     PANEL_HEADER, PANEL_MAX_SIZE, panel_candidates, panel_refusal, select_panel, write_panel,
     PANEL_PRODUCT, PANEL_PRODUCT_HEADER, PANEL_SUMMARY, PANEL_SUMMARY_HEADER, panel_kind, panel_oligos, panel_products,
     panel_products_refusal, panel_texts, write_panel_products, write_panel_summary)
@@ -1618,6 +1620,19 @@ def build_parser():
     p.add_argument("--max-product", type=int, default=None, metavar="INT",
                    help="longest product of --out_products / --out_primer_products in bases, at least the two flanks together /\n"
                         "the upper bound of --amp_size (default: 1000)")
+    p.add_argument("--primer-candidates", type=int, default=None, metavar="INT",
+                   help="--design-primers picks a region's pair among its INT best passing pairs (1 .. 8, by penalty, then\n"
+                        "position) by what they amplify: every shortlisted pair is searched in every input genome, ingroup and\n"
+                        "outgroup, as --out_primer_products searches (--primer-mismatches, --max-product, --omit-soft), and the\n"
+                        "pair with the fewest products without a mismatch in either primer's five 3' bases wins, then the fewest\n"
+                        "with 0 mismatches in all, with 1, and so on; ties go to the better pair.  The picked pair takes the\n"
+                        "place of the best one in the CSV and in every output that reads the pairs.  One more pass over the\n"
+                        "inputs; not with --primer3.  (default: the best pair, no search)")
+    p.add_argument("--out_primer_candidates", type=str, metavar="PATH",
+                   help="With --primer-candidates: also write every searched pair of every region as a tab-separated file:\n"
+                        "region, rank, shortlisted, pair_penalty, product_size, left_sequence, right_sequence, left_start,\n"
+                        "left_length, right_start, right_length, products (the counts clean,t0,t1,...: clean 3' ends, then by the\n"
+                        "two primers' mismatches together), picked (0/1), by region and rank")
     p.add_argument("--out_guides", type=str, metavar="PATH",
                    help="Also write a CRISPR guide for every region that can carry one, as a tab-separated file: region, strand,\n"
                         "start, end (template columns, 0-based, half-open), pam5, pam3, protospacer (as read 5'->3' on the guide's\n"
@@ -1775,10 +1790,11 @@ _NEEDS = {
                    ("--guide-hit-bulges", ("--out_guide_hits",))),
 }
 # ... or with one of these options, which the refusal does not name: --guide-candidates searches with the guide hits' two figures,
-# and the panel's products read the product passes' two figures
+# and the panel's products and --primer-candidates read the product passes' two figures
 _PANEL_PRODUCT_OUTPUTS = ("--out_panel_products", "--out_panel_summary")
 _ALSO_WITH = {"--guide-hit-mismatches": ("--guide-candidates",), "--guide-hits-need-pam": ("--guide-candidates",),
-              "--primer-mismatches": _PANEL_PRODUCT_OUTPUTS, "--max-product": _PANEL_PRODUCT_OUTPUTS}
+              "--primer-mismatches": _PANEL_PRODUCT_OUTPUTS + ("--primer-candidates",),
+              "--max-product": _PANEL_PRODUCT_OUTPUTS + ("--primer-candidates",)}
 _PRIMER_OPTIONS = ("tm", "gc", "amp_size", "primer_size", "max_sec_tm", "gc_clamp", "max_end_gc")
 
 
@@ -1835,6 +1851,11 @@ def _check_options(args, parser):
         _refuse("--out_primer_products needs --design-primers")
     needs("products")
     if args.out_primer_products is not None:
+        fill("primer_mismatches", "max_product")
+        check(primer_products_refusal(args.amp_size, args.primer_mismatches, args.max_product))
+    check(primer_candidates_refusal(args.design_primers, args.primer_candidates, args.out_primer_candidates is not None,
+                                    bool(args.primer3)))
+    if args.primer_candidates is not None:
         fill("primer_mismatches", "max_product")
         check(primer_products_refusal(args.amp_size, args.primer_mismatches, args.max_product))
     if args.out_products is not None:
@@ -1916,8 +1937,25 @@ def _render(args, groups, ingroup, device):
         if args.verbose:
             print("Designing a primer pair for every region ... ", file=sys.stderr)
         # (the templates are built once: the guide pass takes them too)
-        templates = design_templates(groups, ingroup) if args.out_guides is not None or args.panel is not None else None
-        records = design_primers(groups, ingroup, device=device, hairpins=args.hairpins, templates=templates, **design)
+        shortlisting = args.primer_candidates is not None
+        templates = design_templates(groups, ingroup) if args.out_guides is not None or args.panel is not None or shortlisting else None
+        if not shortlisting:
+            records = design_primers(groups, ingroup, device=device, hairpins=args.hairpins, templates=templates, **design)
+        else:
+            # (the picked records take the place of design_primers': every consumer below reads the same array)
+            M = args.primer_mismatches
+            shortlist = design_primer_shortlist(groups, ingroup, device=device, hairpins=args.hairpins, templates=templates,
+                                                top=args.primer_candidates, **design)
+            left, right, pairs, index = shortlist_pairs(templates[0], shortlist)
+            if args.verbose:
+                print(f"Searching every genome for {len(pairs):,} candidate primer pairs with up to {M} mismatches each ... ",
+                      file=sys.stderr)
+            tallies = primer_tallies(left, right, pairs, args.files, args.outgroup, args.conserved_left, args.conserved_right,
+                                     args.amplicon, mismatches=M, max_product=args.max_product, omit_soft=args.omit_soft,
+                                     device=device)
+            records, ranks, _ = pick_pairs(shortlist, index, tallies, M)
+            if args.out_primer_candidates is not None:
+                write_primer_candidates(args.out_primer_candidates, templates[0], shortlist, index, tallies, ranks, M)
         csv_text, align_text = primers.render_designed(groups, ingroup, records, dot=args.dot_alignment)
     else:
         csv_text, align_text = amplicon.render(groups, ingroup, dot=args.dot_alignment)

@@ -1,6 +1,7 @@
 """The report passes of `krisp_fasta`: what runs after the diagnostic regions are found, on one device, one genome at a
 time -- where the regions lie (--out_locations), their near matches (--out_near), the products of their flanks
-(--out_products), a primer pair per region and its products (--design-primers, --out_primer_products), a guide per
+(--out_products), a primer pair per region, picked among its best pairs by their products where asked, and its products
+(--design-primers, --primer-candidates, --out_primer_products), a guide per
 region, picked among its best candidates by their outgroup hits where asked (--out_guides, --guide-candidates), and its
 hits (--out_guide_hits, --guide-hit-bulges), the guide hits inside the primers' products (--out_assay_hits) and N mutually
 compatible assays of the designed pairs (--panel) and what their oligos amplify together (--out_panel_products) -- with their refusals, table builders and TSV writers.  krisp_fasta imports every name back: its
@@ -516,6 +517,188 @@ def primer_products(groups, records, ingroup_labels, ingroup_files, outgroup_fil
         # (a file's rows are in (position, length, strand) order already -- positions ascend with (record_index, start))
         parts.append((fi, part, part["region"]))
     return _sorted_parts(parts, PRODUCT)
+
+
+# ----------------------------------------------------------------------------
+# the primer pair picked among a region's best pairs by its products in every genome (--primer-candidates)
+# ----------------------------------------------------------------------------
+PRIMER_MAX_CANDIDATES = 8
+PRIMER_CANDIDATE_HEADER = ("region\trank\tshortlisted\tpair_penalty\tproduct_size\tleft_sequence\tright_sequence\tleft_start\t"
+                           "left_length\tright_start\tright_length\tproducts\tpicked")
+PRIMER_TALLY_COLUMNS = 8            # kr_primers_tally: t0 .. t6, then the clean-end products
+
+
+def primer_candidates_refusal(design_primers, candidates, out_primer_candidates, primer3):
+    """why --primer-candidates / --out_primer_candidates are not taken (one line), or None.  design_primers, primer3,
+    out_primer_candidates: whether they are asked for; candidates: the option's value or None"""
+    if candidates is None:
+        return "--out_primer_candidates needs --primer-candidates" if out_primer_candidates else None
+    if primer3:
+        return "--primer-candidates cannot be combined with --primer3 (the pairs Primer3 designs are not re-ranked)"
+    if not design_primers:
+        return "--primer-candidates needs --design-primers (the pairs it picks)"
+    if candidates < 1 or candidates > PRIMER_MAX_CANDIDATES:
+        return f"--primer-candidates must lie between 1 and {PRIMER_MAX_CANDIDATES} (got {candidates})"
+    return None
+
+
+def design_primer_shortlist(groups, ingroup_labels, tm=(53, 68), gc=(40, 70), amp_size=(70, 150), primer_size=(25, 35), max_sec_tm=40,
+                            gc_clamp=1, max_end_gc=4, device=0, hairpins=False, templates=None, top=PRIMER_MAX_CANDIDATES):
+    """design_primers' passing pairs of every region in design_primers' order -- ascending (pair_penalty, left_start,
+    left_len, right_start, right_len) --, the first `top` (1 .. 8) of them, on the device (kr_design_run_top).
+    Returns a _native.DESIGN_RECORD array [groups, top], with hairpins DESIGN_RECORD_HP: column j = the pair of rank j + 1
+    with all its figures, column 0 = design_primers' record; found = 0 where the region has fewer.  ValueError for figures
+    the pass does not take"""
+    from . import _native, thermo
+    if top < 1 or top > PRIMER_MAX_CANDIDATES:
+        raise ValueError(f"--primer-candidates must lie between 1 and {PRIMER_MAX_CANDIDATES} (got {top})")
+    opts = dict(tm=tuple(tm), gc=tuple(gc), amp_size=tuple(amp_size), primer_size=tuple(primer_size), max_sec_tm=max_sec_tm,
+                gc_clamp=gc_clamp, max_end_gc=max_end_gc)
+    why = thermo.refusal(**opts)
+    if why is not None:
+        raise ValueError(why)
+    rows, L, D, R = design_templates(groups, ingroup_labels) if templates is None else templates
+    if len(rows) == 0:
+        return np.empty((0, top), dtype=_native.DESIGN_RECORD_HP if hairpins else _native.DESIGN_RECORD)
+    with _engine(device) as eng:
+        eng.design_table(thermo.params(**opts))
+        if hairpins:
+            eng.design_hairpins(thermo.hairpin_params())
+        return eng.design_top(rows, L, D, R, top)
+
+
+_BASE_CODE = np.full(256, 255, dtype=np.uint8)
+_BASE_CODE[[ord(x) for x in "ACGT"]] = [0, 1, 2, 3]
+
+
+def _distinct_texts(flat, at, length):
+    """The texts flat[at[i], at[i] + length[i]) of 10 .. 60 letters A, C, G, T, equal texts once, ordered by their bytes ->
+    (the distinct texts as bytes, int64: the text of every i).  No loop over i: a text is packed, two bits a letter, into
+    two uint64 -- 32 letters, then 28 and the length --, whose order is the order of the bytes (A < C < G < T as 0 .. 3; a
+    text sorts behind its prefixes as the padding is A's code and the length breaks the tie)"""
+    key = at.astype(np.int64) * 64 + length.astype(np.int64)
+    ukey, slot = np.unique(key, return_inverse=True)           # (neighbouring ranks often share a primer)
+    uat, ulen = ukey // 64, ukey % 64
+    width = int(ulen.max())
+    hi = np.zeros(len(ukey), dtype=np.uint64)
+    lo = ulen.astype(np.uint64)
+    last = len(flat) - 1
+    for c in range(width):                                      # (the letters' columns, 60 at most)
+        code = _BASE_CODE[flat[np.minimum(uat + c, last)]]
+        inside = c < ulen
+        if (code[inside] > 3).any():
+            raise ValueError("shortlist_pairs: a primer holds a letter other than A, C, G, T")
+        v = np.where(inside, code, 0).astype(np.uint64)
+        if c < 32:
+            hi |= v << np.uint64(62 - 2 * c)
+        else:
+            lo |= v << np.uint64(62 - 2 * (c - 32))
+    order = np.lexsort((lo, hi))
+    hs, ls = hi[order], lo[order]
+    new = np.concatenate([[True], (hs[1:] != hs[:-1]) | (ls[1:] != ls[:-1])])
+    text_of = np.empty(len(ukey), dtype=np.int64)
+    text_of[order] = np.cumsum(new) - 1
+    first = order[new]
+    letters = flat[np.minimum(uat[first][:, None] + np.arange(width)[None, :], last)].tobytes()
+    texts = [letters[i * width:i * width + n] for i, n in enumerate(ulen[first].tolist())]
+    return texts, text_of[np.asarray(slot).ravel()]
+
+
+def shortlist_pairs(templates, shortlist):
+    """The table of the shortlist's search: every filled slot's left text template[left_start, left_start + left_len) and
+    right text template[right_start, right_start + right_len), as primer_pairs cuts them; equal texts are listed once,
+    ordered by their bytes, equal (left, right) pairs of different slots or regions once, ordered by (left, right).
+    -> (left texts, right texts, pairs uint32 [np, 2], int64 [regions, top]: the pair of every slot, -1 for an empty
+    one).  Array indexing and np.unique throughout: no loop over the regions"""
+    index = np.full(shortlist.shape, -1, dtype=np.int64)
+    ri, si = np.nonzero(shortlist["found"])
+    if len(ri) == 0:
+        return [], [], np.empty((0, 2), dtype=np.uint32), index
+    t = np.ascontiguousarray(templates, dtype=np.uint8).reshape(len(shortlist), -1)
+    flat, base = t.ravel(), ri.astype(np.int64) * t.shape[1]
+    s = shortlist[ri, si]
+    left, li = _distinct_texts(flat, base + s["left_start"], s["left_len"])
+    right, rj = _distinct_texts(flat, base + s["right_start"], s["right_len"])
+    upair, inverse = np.unique(li * len(right) + rj, return_inverse=True)
+    index[ri, si] = np.asarray(inverse).ravel()
+    pairs = np.stack([upair // len(right), upair % len(right)], axis=1).astype(np.uint32)
+    return left, right, pairs, index
+
+
+def primer_tallies(left, right, pairs, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1, max_product=1000,
+                   omit_soft=False, device=0):
+    """How often every pair (shortlist_pairs) amplifies in the input genomes: the search of primer_products over
+    all files, ingroup and outgroup, and per file the device's count of the products by pair (kr_primers_tally) -- no
+    product comes to the host.  Returns uint64 [pairs, 8]: column m = the products with left_mismatches +
+    right_mismatches = m (0 .. 6; above 2 `mismatches` there is none), column 7 = those without a mismatch at either 3'
+    end, summed over the files.  ValueError for figures the search does not take (primer_products_refusal)"""
+    why = primer_products_refusal(None, mismatches, max_product)
+    if why is not None:
+        raise ValueError(why)
+    pairs = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    total = np.zeros((len(pairs), PRIMER_TALLY_COLUMNS), dtype=np.uint64)
+    if len(pairs) == 0:
+        return total
+    both = np.array([len(x) for x in left], dtype=np.int64)[pairs[:, 0]] + np.array([len(x) for x in right], dtype=np.int64)[pairs[:, 1]]
+    if max_product < int(both.max()):
+        raise ValueError(f"--max-product must be at least a pair's two primers together, {int(both.max())} bases (got {max_product})")
+    Le, De, Re = codec.effective_geometry(L, amplicon_len - L - R, R)
+    files = list(ingroup_files) + list(outgroup_files)
+    for eng, _, _, _, _ in _scan_genomes(files, Le, De, Re, amplicon_len, omit_soft, device,
+                                         lambda eng: eng.primers_table(list(left) + list(right), len(left), pairs, mismatches,
+                                                                       max_product)):
+        if eng.primers_scan(0):
+            total += eng.primers_tally()
+    return total
+
+
+def _tally_keys(tallies, mismatches):
+    """kr_primers_tally's columns -> the tally the pick compares, (clean, t0, ..., t2M): uint64 [..., 2 M + 2]"""
+    t = np.asarray(tallies, dtype=np.uint64)
+    return np.concatenate([t[..., 7:8], t[..., :2 * int(mismatches) + 1]], axis=-1)
+
+
+def pick_pairs(shortlist, index, tallies, mismatches):
+    """The pick of --primer-candidates: per region the shortlisted pair whose tally (clean, t0, ..., t2M), M = `mismatches`,
+    is lexicographically smallest, the lower rank where tallies tie.  shortlist: DESIGN_RECORD [regions, top]
+    (design_primer_shortlist), index: [regions, top] rows of `tallies` (shortlist_pairs; -1: an empty slot), tallies: uint64
+    [pairs, 8] (primer_tallies; the columns 2M + 1 .. 6 are not looked at).  -> (the picked records, [regions] of the
+    shortlist's dtype -- a region without a pair keeps its record of rank 1, found = 0 --, their 0-based ranks, their
+    tallies as uint64 [regions, 2 M + 2], zeros for a region without a pair).  Masked row minima: no loop over the regions"""
+    n, top = shortlist.shape
+    width = 2 * int(mismatches) + 2
+    alive = index >= 0
+    t = np.zeros((n, top, width), dtype=np.uint64)
+    t[alive] = _tally_keys(tallies, mismatches).reshape(-1, width)[index[alive]]
+    worst = np.uint64(np.iinfo(np.uint64).max)
+    for m in range(width):
+        col = np.where(alive, t[:, :, m], worst)
+        alive &= col == col.min(axis=1, keepdims=True)
+    ranks = np.argmax(alive, axis=1) if n else np.zeros(0, dtype=np.int64)      # (the first slot still alive; 0 where the region has none)
+    rows = np.arange(n)
+    return shortlist[rows, ranks], ranks.astype(np.int64), t[rows, ranks]
+
+
+def write_primer_candidates(path, templates, shortlist, index, tallies, ranks, mismatches):
+    """the TSV of --out_primer_candidates: PRIMER_CANDIDATE_HEADER, then a line per searched pair, by region, then rank.
+    region: the region's rank among the regions with a pair, as --out_primer_products numbers them; rank from 1;
+    shortlisted: the region's searched pairs; the sequences 5'->3' as the CSV shows them (the right primer is the reverse
+    complement of the template under it), starts and lengths on the template; products: the pair's tally clean,t0,...,t2M
+    (primer_tallies); picked = 1 for the region's pick (ranks: pick_pairs')"""
+    keys = _tally_keys(tallies, mismatches)
+    shortlisted = (index >= 0).sum(axis=1)
+    region = np.cumsum(shortlisted > 0) - 1
+    with open(path, "w") as f:
+        f.write(PRIMER_CANDIDATE_HEADER + "\n")
+        for i in np.flatnonzero(shortlisted).tolist():
+            row = bytes(templates[i])
+            for j in range(int(shortlisted[i])):
+                r = shortlist[i, j]
+                ls, ln, rs, rn = (int(r[k]) for k in ("left_start", "left_len", "right_start", "right_len"))
+                right = row[rs:rs + rn].translate(bytes(_COMPLEMENT_BYTES))[::-1]
+                f.write(f"{int(region[i])}\t{j + 1}\t{int(shortlisted[i])}\t{int(r['pair_penalty'])}\t{int(r['product_size'])}\t"
+                        f"{row[ls:ls + ln].decode('ascii')}\t{right.decode('ascii')}\t{ls}\t{ln}\t{rs}\t{rn}\t"
+                        f"{_tally_text(keys[index[i, j]])}\t{int(ranks[i] == j)}\n")
 
 
 # ----------------------------------------------------------------------------
