@@ -492,7 +492,8 @@ typedef struct { uint32_t position; int32_t cross_any, cross_end; uint32_t dropp
 /* the members of the latest run (KR_ERR_STATE before one) */
 int64_t kr_panel_fetch(kr_ctx*, kr_panel_member* out, size_t cap);
 /* two bytes per candidate of the latest run: fate (1 member, 2 dropped as the same locus, 3 dropped for a clash, 0 still
- * alive when the panel was full) and by (the 1-based member that dropped it, a member's own number, 0 for fate 0); cap
+ * alive when the panel was full; after kr_panel_run_clean also 4 dropped for a cross product with a member, 5 a primer
+ * that primes with itself) and by (the 1-based member that dropped it, a member's own number, 0 for fates 0 and 5); cap
  * counts bytes.  Returns the number of bytes written (KR_ERR_STATE before a run) */
 int64_t kr_panel_fates(kr_ctx*, uint8_t* out, size_t cap);
 
@@ -680,6 +681,38 @@ int64_t kr_multiplex_sites(kr_ctx*, kr_product_site* out, size_t cap);
  * counters.  Returns 2 T^2.  The list is only read: a fetch gives the same bytes after it as before it.  No products:
  * zeros without a launch.  KR_ERR_STATE before a scan or after a new table; KR_ERR_CAPACITY for cap < 2 T^2. */
 int64_t kr_multiplex_tally(kr_ctx*, uint32_t* out, size_t cap);
+
+/* ---- a panel without cross and single products in any input genome (krisp_fasta --panel-clean) ------------------------
+ * No seam in the reference.  kr_panel_run decides by a shared window and four duplex figures and never looks at a genome;
+ * here the primer sites of ALL candidates in every input genome are kept on the device, and the selection also drops a
+ * candidate one of whose primers forms a product with itself (fate 5, by 0: before the first round, never alive) or with a
+ * primer of a member, in either order (fate 4, by = the member; tested behind same locus and clash).  DESIGN §26 holds the
+ * definition, tests/panel_clean_reference.py restates it; the kernels are csrc/k_panel_clean.inc.  The state lives in a
+ * locate context beside the other passes' (kr_set_params_locate drops it) and touches none of theirs.
+ *
+ * kr_panel_sites_table: kr_multiplex_table for 1 <= ntexts < 2^24 texts, with its errors for the lengths (10 .. 60), the
+ * mismatches (0 .. 3) and max_product (>= twice the longest text).  Empties the store.  Returns the table's slots.
+ * kr_panel_sites_scan: the sites of uploaded genome `id` (kr_multiplex_scan's, no join) appended to the store, each with
+ * its unit: the genome's record index plus the records of the scans before it (a scan counts separators + 1), so no two
+ * records share a unit.  Returns the genome's site count.  KR_ERR_STATE "kr_panel_sites_table first"; KR_ERR_CAPACITY,
+ * naming the count, when the store (16 + 4 bytes a site) does not fit or would reach 2^32 sites; the earlier content
+ * survives growth.
+ * kr_panel_sites_fetch: the whole store as the device holds it (a genome's sites in position order, genomes in scan
+ * order) and the units beside it; out == NULL: the count only. */
+int64_t kr_panel_sites_table(kr_ctx*, const uint8_t* text, const uint32_t* offsets, uint64_t ntexts, int mismatches,
+                             uint32_t max_product);
+int64_t kr_panel_sites_scan(kr_ctx*, int id);
+int64_t kr_panel_sites_fetch(kr_ctx*, kr_product_site* out, uint32_t* unit, size_t cap);
+/* kr_panel_run with the store: its arguments and checks, and texts = two table rows a candidate (left primer, right primer
+ * as 5'->3' texts; KR_ERR_PARAM for a row >= ntexts).  KR_ERR_STATE "kr_panel_sites_table first" without a table; with an
+ * empty store the members and fates are kr_panel_run's byte for byte.  Three launches a round on the context's stream, one
+ * synchronise behind them all; the same bytes on every run.  kr_panel_fetch and kr_panel_fates serve either run.
+ * Returns the members. */
+int64_t kr_panel_run_clean(kr_ctx*, const uint8_t* templates, const uint16_t* pairs, const uint32_t* texts, uint64_t ncand,
+                           int W, int size);
+/* out[0] = the self-priming candidates of the latest run, out[1 + j] = the candidates member j + 1 dropped as cross;
+ * 1 + members counters, counted from the fates.  Returns their number. */
+int64_t kr_panel_clean_drops(kr_ctx*, uint32_t* out, size_t cap);
 
 /* Host-side ingest (no GPU involved): the text of a FASTA / sequence-per-line file -> the
  * upload buffer of kr_genome_upload, with the reference reader's semantics

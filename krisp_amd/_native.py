@@ -148,6 +148,11 @@ SYMBOLS = [
     ("kr_panel_run", _c.c_int64, [_P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int]),
     ("kr_panel_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_panel_fates", _c.c_int64, [_P, _P, _c.c_size_t]),
+    ("kr_panel_sites_table", _c.c_int64, [_P, _P, _P, _c.c_uint64, _c.c_int, _c.c_uint32]),
+    ("kr_panel_sites_scan", _c.c_int64, [_P, _c.c_int]),
+    ("kr_panel_sites_fetch", _c.c_int64, [_P, _P, _P, _c.c_size_t]),
+    ("kr_panel_run_clean", _c.c_int64, [_P, _P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int]),
+    ("kr_panel_clean_drops", _c.c_int64, [_P, _P, _c.c_size_t]),
     ("kr_guides_table", _c.c_int, [_P, _P]),
     ("kr_guides_run", _c.c_int64, [_P, _P, _P, _P, _c.c_uint64, _c.c_int, _c.c_int, _c.c_int]),
     ("kr_guides_fetch", _c.c_int64, [_P, _P, _c.c_size_t]),
@@ -998,11 +1003,11 @@ class Engine:
         both["left_hairpin"], both["right_hairpin"] = hp[:n, :, 0], hp[:n, :, 1]
         return both
 
-    def panel(self, templates, pairs, size):
+    def panel(self, templates, pairs, size, texts=None):
         """templates: uint8 [candidates, W], pairs: uint16 [candidates, 4] (left_start, left_len, right_start, right_len), in
         the order the selection goes by; after design_table (the model and max_sec) -> (PANEL_MEMBER array of at most
         `size` members in order of acceptance, PANEL_FATE array, one per candidate) (kr_panel_run, kr_panel_fetch,
-        kr_panel_fates)"""
+        kr_panel_fates).  (texts: panel_clean's)"""
         t = np.ascontiguousarray(templates, dtype=np.uint8)
         if t.ndim != 2:
             raise ValueError("panel: templates is a matrix, a row of W letters each")
@@ -1010,13 +1015,53 @@ class Engine:
         if len(q) != len(t):
             raise ValueError(f"panel: {len(t)} templates, {len(q)} pairs")
         n = len(t)
-        members = self._check(self.lib.kr_panel_run(self.ctx, _ptr(t) if n else None, _ptr(q) if n else None, n, t.shape[1], size),
-                              "kr_panel_run")
+        if texts is None:
+            members = self._check(self.lib.kr_panel_run(self.ctx, _ptr(t) if n else None, _ptr(q) if n else None, n, t.shape[1], size),
+                                  "kr_panel_run")
+        else:
+            x = np.ascontiguousarray(texts, dtype=np.uint32).reshape(-1, 2)
+            if len(x) != n:
+                raise ValueError(f"panel_clean: {n} templates, {len(x)} rows of texts")
+            members = self._check(self.lib.kr_panel_run_clean(self.ctx, _ptr(t) if n else None, _ptr(q) if n else None,
+                                                              _ptr(x) if n else None, n, t.shape[1], size), "kr_panel_run_clean")
         out = np.zeros(max(members, 1), dtype=PANEL_MEMBER)
         self._check(self.lib.kr_panel_fetch(self.ctx, _ptr(out), members), "kr_panel_fetch")
         fates = np.zeros(max(n, 1), dtype=PANEL_FATE)
         self._check(self.lib.kr_panel_fates(self.ctx, _ptr(fates), 2 * n), "kr_panel_fates")
         return out[:members], fates[:n]
+
+    def panel_sites_table(self, texts, mismatches, max_product):
+        """texts: a list of 1 .. 2^24 - 1 bytes (upper case, T for U, 5'->3'), each of its own length 10 .. 60: the distinct
+        primer texts of all candidates of panel_clean.  Empties the site store -> slots of the seed table
+        (kr_panel_sites_table).  A state of its own beside multiplex_table's and primers_table's"""
+        texts = [bytes(t) for t in texts]
+        offsets = np.zeros(len(texts) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum([len(t) for t in texts], dtype=np.int64)
+        text = np.frombuffer(b"".join(texts) + b"\0", dtype=np.uint8)      # (never empty: a pointer to pass)
+        return self._check(self.lib.kr_panel_sites_table(self.ctx, _ptr(text), _ptr(offsets), len(texts), mismatches, max_product),
+                           "kr_panel_sites_table")
+
+    def panel_sites_scan(self, gid):
+        """appends the primer sites of uploaded genome gid to the store -> that genome's site count (kr_panel_sites_scan)"""
+        return self._check(self.lib.kr_panel_sites_scan(self.ctx, gid), "kr_panel_sites_scan")
+
+    def panel_sites(self):
+        """the store as the device holds it -> (PRODUCT_SITE array, uint32 array of the sites' record numbers)
+        (kr_panel_sites_fetch)"""
+        n = self._check(self.lib.kr_panel_sites_fetch(self.ctx, None, None, 0), "kr_panel_sites_fetch")
+        sites, unit = np.empty(max(n, 1), dtype=PRODUCT_SITE), np.empty(max(n, 1), dtype=np.uint32)
+        self._check(self.lib.kr_panel_sites_fetch(self.ctx, _ptr(sites), _ptr(unit), n), "kr_panel_sites_fetch")
+        return sites[:n], unit[:n]
+
+    def panel_clean(self, templates, pairs, texts, size):
+        """panel() with the site store: texts = uint32 [candidates, 2], the rows of panel_sites_table's texts that are the
+        candidate's left and right primer -> (members, fates, drops): fates 4 (a product with a member's primer in some
+        scanned genome) and 5 (a primer that forms a product with itself) beside panel()'s; drops = uint32 [1 + members]:
+        the self-priming candidates, then what each member dropped as cross (kr_panel_run_clean, kr_panel_clean_drops)"""
+        members, fates = self.panel(templates, pairs, size, texts=texts)
+        drops = np.zeros(1 + len(members), dtype=np.uint32)
+        self._check(self.lib.kr_panel_clean_drops(self.ctx, _ptr(drops), len(drops)), "kr_panel_clean_drops")
+        return members, fates, drops
 
     def guides_table(self, guide_size, pam5=(), pam3=(), gc=(30, 70), min_mismatches=1):
         """the options of guides(): pam5 / pam3 = the motifs as sequences of 4-bit IUPAC masks, read 5'->3' on the guide's

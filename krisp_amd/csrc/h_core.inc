@@ -352,6 +352,17 @@ struct kr_ctx {
         DevBuf tally;                   // kr_multiplex_tally's counters
         void bufs(Bufs& v) { Prim::bufs(v); v.push_back(&tally); }
     } mux;
+    // the clean panel selection's site store (kr_panel_sites_*, kr_panel_run_clean: h_panel_clean.inc), in the same context:
+    // tab = the primer pass's state a third time (a table of all candidates' texts, nright = 0, no pair list; its sites and
+    // rec are the latest scan's); sites / unit = the store of every scan since the table, nstore sites, units records
+    struct Pclean {
+        Prim tab;
+        u64 nstore = 0, units = 0, nown = 0;   // (nown: the owners' list of the latest run)
+        DevBuf sites, unit;
+        DevBuf rows, ooff, own;         // a run's: the candidates' table rows, the texts' owners
+        void bufs(Bufs& v) { tab.bufs(v); v.insert(v.end(), {&sites, &unit, &rows, &ooff, &own}); }
+        void reset() { tab.reset(); nstore = units = 0; }
+    } pclean;
     // the primer design pass (kr_design_*: h_design.inc): no genome, no geometry of another pass
     struct Design {
         bool on = false;
@@ -798,7 +809,7 @@ void kr_destroy(kr_ctx* c) {
     {
         kr_ctx::Bufs sb;                // the wide path's and the one-genome scans': every pass hands over its own
         c->wide.bufs(sb);
-        c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb); c->assay.bufs(sb); c->mux.bufs(sb);
+        c->loc.bufs(sb); c->near.bufs(sb); c->ghit.bufs(sb); c->gbulge.bufs(sb); c->prod.bufs(sb); c->prim.bufs(sb); c->assay.bufs(sb); c->mux.bufs(sb); c->pclean.bufs(sb);
         for (DevBuf* b : sb) release(c, *b);
         auto& ds = c->design;
         DevBuf* db[] = {&ds.par, &ds.tmpl, &ds.rec, &ds.hprec};

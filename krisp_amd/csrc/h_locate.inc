@@ -22,7 +22,7 @@ int kr_set_params_locate(kr_ctx* c, int L, int D, int R, int softmask_mode, size
     l.ngroups = l.slots = 0;
     l.nhits = -1;
     // a table of another geometry (the primer pass: of another soft-mask mode) is no table: kr_*_table again
-    c->near.reset(); c->ghit.reset(); c->gbulge.reset(); c->prod.reset(); c->prim.reset(); c->assay.reset(); c->mux.reset();
+    c->near.reset(); c->ghit.reset(); c->gbulge.reset(); c->prod.reset(); c->prim.reset(); c->assay.reset(); c->mux.reset(); c->pclean.reset();
     c->wide.on = false;
     c->max_bases = max_bases;
     c->have_params = true;

@@ -5,26 +5,30 @@
 // running figures (8 bytes), and pick[0 .. size].
 #define PAN_MAX_SIZE 64
 
-int64_t kr_panel_run(kr_ctx* c, const uint8_t* templates, const uint16_t* pairs, uint64_t ncand, int W, int size) {
-    if (!c || !c->design.on) return fail(c, KR_ERR_STATE, "kr_design_table first");
+// what kr_panel_run_clean adds to the launches (h_panel_clean.inc): before round 0, and behind every round's k_panel_round
+static int pclean_before(kr_ctx* c, const uint32_t* texts, u64 ncand);
+static void pclean_round(kr_ctx* c, u32 r, u64 ncand);
+
+// kr_panel_run (texts == nullptr) and kr_panel_run_clean (texts: two table rows a candidate, checked by the caller)
+static int64_t panel_run(kr_ctx* c, const char* who, const uint8_t* templates, const uint16_t* pairs, uint64_t ncand, int W, int size,
+                         const uint32_t* texts) {
     auto& p = c->panel;
-    p.nmem = -1;
-    if (W < 1 || W > (int)PANEL_MAX_TEMPLATE) return fail(c, KR_ERR_PARAM, "kr_panel_run: a template of 1 .. %u bytes (got %d)", PANEL_MAX_TEMPLATE, W);
-    if (size < 1 || size > PAN_MAX_SIZE) return fail(c, KR_ERR_PARAM, "kr_panel_run: a panel of 1 .. %d members (got %d)", PAN_MAX_SIZE, size);
-    if (ncand && (!templates || !pairs)) return fail(c, KR_ERR_PARAM, "kr_panel_run: null argument");
-    if (ncand >= (uint64_t)PAN_NONE) return fail(c, KR_ERR_CAPACITY, "kr_panel_run: fewer than 2^32 - 1 candidates (got %llu)", (unsigned long long)ncand);
+    if (W < 1 || W > (int)PANEL_MAX_TEMPLATE) return fail(c, KR_ERR_PARAM, "%s: a template of 1 .. %u bytes (got %d)", who, PANEL_MAX_TEMPLATE, W);
+    if (size < 1 || size > PAN_MAX_SIZE) return fail(c, KR_ERR_PARAM, "%s: a panel of 1 .. %d members (got %d)", who, PAN_MAX_SIZE, size);
+    if (ncand && (!templates || !pairs)) return fail(c, KR_ERR_PARAM, "%s: null argument", who);
+    if (ncand >= (uint64_t)PAN_NONE) return fail(c, KR_ERR_CAPACITY, "%s: fewer than 2^32 - 1 candidates (got %llu)", who, (unsigned long long)ncand);
     for (u64 i = 0; i < ncand; i++) {
         const uint16_t* q = pairs + 4 * i;
         for (int s = 0; s < 2; s++)
             if (q[2 * s + 1] < 10 || q[2 * s + 1] > 60 || (int)q[2 * s] + (int)q[2 * s + 1] > W)
-                return fail(c, KR_ERR_PARAM, "kr_panel_run: candidate %llu: a primer of 10 .. 60 bases inside the template of %d (got start %u, "
-                            "length %u)", (unsigned long long)i, W, (unsigned)q[2 * s], (unsigned)q[2 * s + 1]);
+                return fail(c, KR_ERR_PARAM, "%s: candidate %llu: a primer of 10 .. 60 bases inside the template of %d (got start %u, "
+                            "length %u)", who, (unsigned long long)i, W, (unsigned)q[2 * s], (unsigned)q[2 * s + 1]);
     }
     try {
         p.members.assign((size_t)size, kr_panel_member{});
         p.fates.assign(2 * (size_t)ncand, 0);
     } catch (const std::bad_alloc&) {
-        return fail(c, KR_ERR_CAPACITY, "kr_panel_run: no host memory for %llu fates", (unsigned long long)ncand);
+        return fail(c, KR_ERR_CAPACITY, "%s: no host memory for %llu fates", who, (unsigned long long)ncand);
     }
     p.members.clear();
     p.ncand = ncand;
@@ -44,10 +48,13 @@ int64_t kr_panel_run(kr_ctx* c, const uint8_t* templates, const uint16_t* pairs,
     HIPCHK(c, hipMemsetAsync(p.cross.p, 0, (size_t)ncand * 8, c->stream));
     // (persistent workgroups: four a CU, a wave per candidate at a time)
     const u32 grid = (u32)std::max<u64>(1, std::min<u64>((u64)c->ncu * 4, (ncand + PAN_WAVES - 1) / PAN_WAVES));
-    for (int r = 0; r < size; r++)
+    if (texts && (rc = pclean_before(c, texts, ncand))) return rc;
+    for (int r = 0; r < size; r++) {
         hipLaunchKernelGGL(k_panel_round, dim3(grid), dim3(PAN_T), 0, c->stream, (const uint8_t*)p.tmpl.p, (const ushort4*)p.pairs.p,
                            (u32)ncand, (u32)W, (u32)r, (const kr_design_params*)c->design.par.p, (u32*)p.pick.p, (uint8_t*)p.state.p,
                            (int2*)p.cross.p);
+        if (texts) pclean_round(c, (u32)r, ncand);
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(pick.data(), p.pick.p, npick * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(p.fates.data(), p.state.p, (size_t)ncand * 2, hipMemcpyDeviceToHost, c->stream));
@@ -67,6 +74,12 @@ int64_t kr_panel_run(kr_ctx* c, const uint8_t* templates, const uint16_t* pairs,
         if ((fate == 2 || fate == 3) && by >= 1 && by <= p.members.size()) p.members[by - 1].dropped[fate - 2]++;
     }
     return p.nmem = (int64_t)p.members.size();
+}
+
+int64_t kr_panel_run(kr_ctx* c, const uint8_t* templates, const uint16_t* pairs, uint64_t ncand, int W, int size) {
+    if (!c || !c->design.on) return fail(c, KR_ERR_STATE, "kr_design_table first");
+    c->panel.nmem = -1;
+    return panel_run(c, "kr_panel_run", templates, pairs, ncand, W, size, nullptr);
 }
 
 int64_t kr_panel_fetch(kr_ctx* c, kr_panel_member* out, size_t cap) {

@@ -125,9 +125,11 @@ static int prod_join(kr_ctx* c, kr_ctx::Prod& st, const Geom& pg, u64 ns, const 
 
 // a product pass's scan behind scan_genome, up to its join: the windows of `width` bases (the shortest text's), the
 // separators, the sites -- sites(nw, ntiles, &ns): the pass's choice of prod_sites_launch by its M -- and their records
-// (launched: the join follows on the stream) -> *ns sites.  The pass's counts stand at -1 until its caller sets them
+// (launched: the join follows on the stream) -> *ns sites (*nseps_out: the genome's separators).  The pass's counts stand at
+// -1 until its caller sets them
 template <typename S>
-static int prod_scan_sites(kr_ctx* c, const Genome& G, kr_ctx::Prod& st, u64 width, const char* who, S&& sites, u64* ns) {
+static int prod_scan_sites(kr_ctx* c, const Genome& G, kr_ctx::Prod& st, u64 width, const char* who, S&& sites, u64* ns,
+                           u64* nseps_out = nullptr) {
     int rc;
     st.nsites = st.nhits = -1;
     *ns = 0;
@@ -138,6 +140,7 @@ static int prod_scan_sites(kr_ctx* c, const Genome& G, kr_ctx::Prod& st, u64 wid
     // (the pass's own list: k_prod_rec reads it, and a kr_locate_seps of the caller writes loc.seps)
     if ((rc = scan_seps(c, G, who, st.seps, [&](u64 total) { return ensure(c, st.seps, total * 8); }, &nseps))) return rc;
     if (nseps >= (1ull << 32)) return fail(c, KR_ERR_CAPACITY, "%s: 2^32 or more records in one genome", who);
+    if (nseps_out) *nseps_out = nseps;
     if ((rc = sites(nw, ntiles, ns))) return rc;
     if (*ns) {
         const u32 grid = scan_stride_grid(c, (*ns + 255) / 256);

@@ -58,6 +58,8 @@
 #include "k_design.inc"      // the primer design pass: a wavefront per region, integer thermodynamics, the best pair
 #include "panel_step.inc"    // what the panel pass does per window, table slot and primer base, in plain C++ (shared with a host check)
 #include "k_panel.inc"       // the panel pass: a launch per round, the member's windows in an LDS table, a wavefront per candidate
+#include "pclean_step.inc"   // what the clean panel selection does per stored site and owner, in plain C++ (shared with a host check)
+#include "k_panel_clean.inc" // the clean panel selection: the site store, self-priming, a member's cross products, the next member
 #include "k_coarse.inc"      // a genome that stopped behind pass 1 against a short candidate list: LDS table per top byte, hit list
 #include "k_guides.inc"      // the guide pass: a wavefront per region, the window next to a PAM that differs most from the outgroup rows
 #include "h_core.inc"        // context, buffers, parameters, upload, sort, finalize   (opens extern "C")
@@ -75,6 +77,7 @@
 #include "h_multiplex.inc"   // kr_multiplex_*: in-silico PCR with all the oligos of a panel in one tube
 #include "h_design.inc"      // kr_design_*: a primer pair per region from the model's integers and the primer options
 #include "h_panel.inc"       // kr_panel_*: N mutually compatible assays of the designed pairs, selected on the device
+#include "h_panel_clean.inc" // kr_panel_sites_*, kr_panel_run_clean: the panel kept free of cross and single products in every genome
 #include "h_guides.inc"      // kr_guides_*: a CRISPR guide per region from its template, its outgroup rows and the guide options
 #include "h_pgzip.inc"       // one gzip member inflated on several threads (host only)
 #include "h_ingest.inc"      // file -> inflate -> parse -> pinned upload buffer (host side)

@@ -43,6 +43,7 @@ from .reports import (                                                        # 
     PRIMER_CANDIDATE_HEADER, PRIMER_MAX_CANDIDATES, design_primer_shortlist, pick_pairs, primer_candidates_refusal,
     primer_tallies, shortlist_pairs, write_primer_candidates,
     PANEL_HEADER, PANEL_MAX_SIZE, panel_candidates, panel_refusal, select_panel, write_panel,
+    panel_candidate_texts, panel_clean_refusal, select_panel_clean,
     PANEL_PRODUCT, PANEL_PRODUCT_HEADER, PANEL_SUMMARY, PANEL_SUMMARY_HEADER, panel_kind, panel_oligos, panel_products,
     panel_products_refusal, panel_texts, write_panel_products, write_panel_summary)
 
@@ -1704,6 +1705,14 @@ def build_parser():
                         "data row in the CSV), pair_penalty, product_size, left_sequence, right_sequence, cross_any, cross_end (the\n"
                         "greatest duplex figures of its primers with the primers of the members before it), dropped_same_locus,\n"
                         "dropped_clash (the candidates this member dropped, by cause)")
+    p.add_argument("--panel-clean", action="store_true",
+                   help="With --panel: keep cross and single products out of the panel.  One pass over the inputs keeps the\n"
+                        "sites of every candidate's primers on the device (--primer-mismatches, --max-product and --omit-soft as\n"
+                        "--out_panel_products reads them); a candidate one of whose primers forms a product with itself is never\n"
+                        "a member, and after every member a later candidate is also dropped when one of its primers forms a\n"
+                        "product with one of the member's, in either order, in any genome, the outgroups included.  With the\n"
+                        "same three figures --out_panel_products then holds pair rows only.  --out_panel gains the column\n"
+                        "dropped_cross.  (default: the panel is picked without a look at the genomes)")
     p.add_argument("--out_panel_products", type=str, metavar="PATH",
                    help="With --panel: multiplex in-silico PCR.  With all the panel's primers in one tube, every product they\n"
                         "amplify in every genome, the outgroups included: any primer may open a product and any primer may close\n"
@@ -1793,8 +1802,8 @@ _NEEDS = {
 # and the panel's products and --primer-candidates read the product passes' two figures
 _PANEL_PRODUCT_OUTPUTS = ("--out_panel_products", "--out_panel_summary")
 _ALSO_WITH = {"--guide-hit-mismatches": ("--guide-candidates",), "--guide-hits-need-pam": ("--guide-candidates",),
-              "--primer-mismatches": _PANEL_PRODUCT_OUTPUTS + ("--primer-candidates",),
-              "--max-product": _PANEL_PRODUCT_OUTPUTS + ("--primer-candidates",)}
+              "--primer-mismatches": _PANEL_PRODUCT_OUTPUTS + ("--primer-candidates", "--panel-clean"),
+              "--max-product": _PANEL_PRODUCT_OUTPUTS + ("--primer-candidates", "--panel-clean")}
 _PRIMER_OPTIONS = ("tm", "gc", "amp_size", "primer_size", "max_sec_tm", "gc_clamp", "max_end_gc")
 
 
@@ -1894,6 +1903,9 @@ def _check_options(args, parser):
         fill("primer_mismatches", "max_product")
         check(panel_products_refusal(args.panel, args.out_panel_products is not None, args.out_panel_summary is not None,
                                      args.amp_size, args.primer_size, args.primer_mismatches, args.max_product))
+    if args.panel_clean:
+        fill("primer_mismatches", "max_product")
+        check(panel_clean_refusal(args.panel, True, args.amp_size, args.primer_size, args.primer_mismatches, args.max_product))
     return args
 
 
@@ -1995,8 +2007,17 @@ def _run_reports(args, groups, ingroup, device, records, templates):
         say(f"Picking a panel of {args.panel} assays ... ")
         order = panel_candidates(records, guides)
         design = {name: getattr(args, name) for name in _PRIMER_OPTIONS}
-        members, _fates = select_panel(templates[0], records, order, args.panel, device=device, **design)
-        write_panel(args.out_panel, templates[0], records, order, members)
+        drops = None
+        if args.panel_clean:
+            say(f"Searching every genome for the primers of {len(order):,} candidates with up to {args.primer_mismatches} mismatches each ... ")
+            members, _fates, drops = select_panel_clean(templates[0], records, order, args.panel, *files, *geometry,
+                                                        mismatches=args.primer_mismatches, max_product=args.max_product, **where,
+                                                        **design)
+            print(f"--panel-clean: {int(drops[0])} of {len(order)} candidates prime with themselves and are left out",
+                  file=sys.stderr)
+        else:
+            members, _fates = select_panel(templates[0], records, order, args.panel, device=device, **design)
+        write_panel(args.out_panel, templates[0], records, order, members, drops)
         if args.out_panel_products is not None or args.out_panel_summary is not None:
             say(f"Predicting what the panel's primers amplify together, with up to {args.primer_mismatches} mismatches each ... ")
             rows, summary = panel_products(panel_oligos(templates[0], records, order, members), *files, *geometry,

@@ -52,11 +52,12 @@ def _group_flanks(groups, L, R):
 LOCATE_MAX_BASES = (1 << 33) - 65     # the packed path's limit (KR_MAX_BASES)
 
 
-def _scan_genomes(files, Le, De, Re, k, omit_soft, device, table):
+def _scan_genomes(files, Le, De, Re, k, omit_soft, device, table, last=None):
     """The per-file loop of the passes that scan one genome at a time (locate_regions, near_matches, predict_products,
     primer_products): a locate context on `device`, table(eng) once, then every file uploaded alone as genome 0.
     Yields (eng, file index, path, RNA, names): names() -> (the record separators, the record IDs), their count checked.
-    (The next file is read and inflated on a host thread while the device holds the current one: two texts at most.)"""
+    (The next file is read and inflated on a host thread while the device holds the current one: two texts at most.)
+    last: called as last(eng) behind the last file, before the engine closes (select_panel_clean's selection)."""
     from concurrent.futures import ThreadPoolExecutor
     with _engine(device) as eng, ThreadPoolExecutor(max_workers=1) as pool:
         eng.set_params_locate(Le, De, Re, omit_soft, max_bases=LOCATE_MAX_BASES)
@@ -83,6 +84,8 @@ def _scan_genomes(files, Le, De, Re, k, omit_soft, device, table):
 
             yield eng, fi, path, rna, names
             del text, names
+        if last is not None:
+            last(eng)
 
 
 def _record_coords(seps, pos):
@@ -1347,14 +1350,15 @@ def select_panel(templates, records, order, size, device=0, tm=(53, 68), gc=(40,
         return eng.panel(rows, pairs, size)
 
 
-def write_panel(path, templates, records, order, members):
+def write_panel(path, templates, records, order, members, drops=None):
     """the TSV of --out_panel: PANEL_HEADER, then a line per member in order of acceptance.  templates, records, order as
     select_panel takes them, members: its.  region = the pair's data row in the CSV of --design-primers (the region's rank
-    among the regions with a pair); penalty and figures as the CSV prints its own, from the integers"""
+    among the regions with a pair); penalty and figures as the CSV prints its own, from the integers.  drops
+    (select_panel_clean's): one more column, dropped_cross, behind dropped_clash"""
     from . import thermo
     rank = np.cumsum(records["found"] != 0) - 1
     with open(path, "w") as f:
-        f.write(PANEL_HEADER + "\n")
+        f.write(PANEL_HEADER + ("\tdropped_cross" if drops is not None else "") + "\n")
         for j, m in enumerate(members):
             i = int(order[int(m["position"])])
             r = records[i]
@@ -1362,7 +1366,90 @@ def write_panel(path, templates, records, order, members):
             ls, ln, rs, rn = (int(r[k]) for k in ("left_start", "left_len", "right_start", "right_len"))
             f.write(f"{j + 1}\t{int(rank[i])}\t{thermo.milli(int(r['pair_penalty']))}\t{int(r['product_size'])}\t{t[ls:ls + ln]}\t"
                     f"{_guide_rc(t[rs:rs + rn])}\t{thermo.celsius(int(m['cross_any']))}\t{thermo.celsius(int(m['cross_end']))}\t"
-                    f"{int(m['dropped'][0])}\t{int(m['dropped'][1])}\n")
+                    f"{int(m['dropped'][0])}\t{int(m['dropped'][1])}" + (f"\t{int(drops[1 + j])}" if drops is not None else "") + "\n")
+
+
+# ----------------------------------------------------------------------------
+# a panel without cross and single products in any input genome (--panel-clean)
+# ----------------------------------------------------------------------------
+def panel_clean_refusal(panel, panel_clean, amp_size, primer_size, mismatches, max_product):
+    """why --panel-clean is not taken (one line), or None.  panel: --panel's value or None; panel_clean: whether the option
+    is given; mismatches, max_product: the figures after the defaults"""
+    if not panel_clean:
+        return None
+    if panel is None:
+        return "--panel-clean needs --panel (the selection it keeps clean)"
+    if mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES:
+        return f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    if max_product < amp_size[1]:
+        return (f"--max-product must be at least the upper bound of --amp_size, {amp_size[1]} bases (got {max_product}): a "
+                "member's designed product itself would not be found")
+    if max_product < 2 * primer_size[1]:
+        return (f"--max-product must be at least twice the upper bound of --primer_size, {2 * primer_size[1]} bases (got "
+                f"{max_product}): two primers of the candidates would not fit one product")
+    if max_product >= 1 << 31:
+        return f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    return None
+
+
+def panel_candidate_texts(templates, records, order):
+    """The table of the clean selection: the primer texts of ALL candidates `order`, 5'->3' exactly as write_panel prints
+    left_sequence and right_sequence, equal texts once, ordered by their bytes (as panel_texts orders a panel's)
+    -> (texts: a list of bytes, rows: uint32 [candidates, 2], the table rows of each candidate's left and right primer)"""
+    both = []
+    for i in np.asarray(order, dtype=np.int64).tolist():
+        r = records[i]
+        t = bytes(templates[i]).decode("ascii")
+        ls, ln, rs, rn = (int(r[k]) for k in ("left_start", "left_len", "right_start", "right_len"))
+        both.append((t[ls:ls + ln].encode("ascii"), _guide_rc(t[rs:rs + rn]).encode("ascii")))
+    texts = sorted({x for pair in both for x in pair})
+    at = {t: n for n, t in enumerate(texts)}
+    rows = np.array([[at[a], at[b]] for a, b in both], dtype=np.uint32).reshape(-1, 2)
+    return texts, rows
+
+
+def select_panel_clean(templates, records, order, size, ingroup_files, outgroup_files, L, R, amplicon_len, mismatches=1,
+                       max_product=1000, omit_soft=False, device=0, tm=(53, 68), gc=(40, 70), amp_size=(70, 150),
+                       primer_size=(25, 35), max_sec_tm=40, gc_clamp=1, max_end_gc=4):
+    """select_panel that reads the genomes (kr_panel_sites_*, kr_panel_run_clean): one pass over the input files
+    keeps the sites of ALL candidates' primers (within `mismatches` substitutions, as primer_products finds them) on the
+    device, and the selection in the same engine also drops a candidate one of whose primers forms a product of at most
+    `max_product` bases with itself (fate 5, before the first round) or, in either order, with a primer of a member (fate 4,
+    tested behind same locus and clash).  With the same three figures the --out_panel_products of the result holds `pair`
+    rows only.  -> (members, fates, drops): select_panel's two and uint32 [1 + members]: the self-priming candidates, then
+    what each member dropped as cross.  ValueError for figures the passes do not take"""
+    from . import _native, thermo
+    if size < 1 or size > PANEL_MAX_SIZE:
+        raise ValueError(f"--panel must lie between 1 and {PANEL_MAX_SIZE} (got {size})")
+    opts = dict(tm=tuple(tm), gc=tuple(gc), amp_size=tuple(amp_size), primer_size=tuple(primer_size), max_sec_tm=max_sec_tm,
+                gc_clamp=gc_clamp, max_end_gc=max_end_gc)
+    why = thermo.refusal(**opts)
+    if why is None and (mismatches < 0 or mismatches > PRODUCT_MAX_MISMATCHES):
+        why = f"--primer-mismatches must lie between 0 and {PRODUCT_MAX_MISMATCHES} (got {mismatches})"
+    if why is None and max_product >= 1 << 31:
+        why = f"--max-product must be smaller than 2^31 bases (got {max_product})"
+    order = np.asarray(order, dtype=np.int64)
+    texts, rows = panel_candidate_texts(templates, records, order)
+    if why is None and texts and max_product < 2 * max(len(t) for t in texts):
+        why = f"--max-product must be at least twice the longest primer, {2 * max(len(t) for t in texts)} bases (got {max_product})"
+    if why is not None:
+        raise ValueError(why)
+    if len(order) == 0:
+        return np.empty(0, dtype=_native.PANEL_MEMBER), np.empty(0, dtype=_native.PANEL_FATE), np.zeros(1, dtype=np.uint32)
+    trows = np.ascontiguousarray(templates, dtype=np.uint8)[order]
+    pairs = np.stack([records[f][order] for f in ("left_start", "left_len", "right_start", "right_len")], axis=1).astype(np.uint16)
+    k = amplicon_len
+    Le, De, Re = codec.effective_geometry(L, k - L - R, R)
+    out = []
+
+    def select(eng):
+        eng.design_table(thermo.params(**opts))     # (kr_design_table touches no scan state: the store stands)
+        out.append(eng.panel_clean(trows, pairs, rows, size))
+
+    for eng, _fi, _path, _rna, _recs in _scan_genomes(list(ingroup_files) + list(outgroup_files), Le, De, Re, k, omit_soft, device,
+                                                      lambda eng: eng.panel_sites_table(texts, mismatches, max_product), last=select):
+        eng.panel_sites_scan(0)
+    return out[0]
 
 
 # ----------------------------------------------------------------------------
