@@ -15,6 +15,7 @@ interoperability with the reference's intermediate files and for stage-level
 parity tests.  There is no CPU implementation of the hot path behind any of them.
 """
 import argparse
+import json
 import math
 import os
 import sys
@@ -23,7 +24,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import amplicon, codec, fasta
+from . import _native, amplicon, codec, distributed, fasta
 from .codec import _is_wide
 from .fasta import _FASTA_EXT, basename, simplename                          # noqa: F401
 from .kstream import kstream
@@ -119,7 +120,6 @@ def _check_geometry(L, D, R):
 def _check_wide(L, D, R):
     """geometries of the wide path (kr_wide_run): flanks of up to WIDE_MAX_FLANK bases (one key each, or -- longer than 32
     bases -- ranked piece by piece through up to eight keys), amplicons of up to WIDE_MAX_K"""
-    from . import _native
     if not (1 <= L <= _native.WIDE_MAX_FLANK and 1 <= R <= _native.WIDE_MAX_FLANK and L + D + R <= _native.WIDE_MAX_K):
         raise UnsupportedGeometry(
             f"{L}/{D}/{R}: amplicons longer than 32 bases need 1 <= conserved-left, conserved-right "
@@ -196,6 +196,16 @@ def _prefix_key(left, right):
     return key
 
 
+def _touched_prefix_cands(specials):
+    """the (left,right) pairs IUPAC windows touch, and those of them with plain flanks as a candidate list (their
+    _prefix_key once each, ascending; empty when no pair is plain): the device looks their ACGT members up from it"""
+    touched = {(l, r) for sp in specials for (l, d, r) in sp}
+    pure = sorted({_prefix_key(l, r) for (l, r) in touched if _pure(l) and _pure(r)})
+    cands = np.zeros(len(pure), dtype=_native.CAND)
+    cands["prefix"] = np.array(pure, dtype=np.uint64)
+    return touched, cands
+
+
 def _special_groups(eng, ids, labels, specials, geo, ingroup, do_filter, rna_genomes=None):
     """The reference keeps k-mers with IUPAC letters (kstream.py:11-18); the device cannot pack
     them, so they arrive here as strings: specials[g] = [(left, diag, right), ...] of genome g.
@@ -204,16 +214,11 @@ def _special_groups(eng, ids, labels, specials, geo, ingroup, do_filter, rna_gen
     rules applied -- present in every genome (intersectAmplicons.py:232-310), ingroup-unique
     column (Amplicon.py:495-521).  Rare by nature; everything else stays on the device.
     Returns (set of touched (left,right), list of surviving groups)."""
-    from . import _native
-    L, D, R = geo
-    touched = {(l, r) for sp in specials for (l, d, r) in sp}
+    touched, cands = _touched_prefix_cands(specials)
     if not touched:
         return touched, []
-    pure = sorted({_prefix_key(l, r) for (l, r) in touched if _pure(l) and _pure(r)})
     recs = None
-    if pure:
-        cands = np.zeros(len(pure), dtype=_native.CAND)
-        cands["prefix"] = np.array(pure, dtype=np.uint64)
+    if len(cands):
         eng.load_cands(cands)
         recs = eng.collect(ids)
     return touched, _special_groups_from(recs, ids, labels, specials, geo, ingroup, do_filter, rna_genomes)
@@ -267,7 +272,6 @@ def _wide_probe_members(eng, texts, gis, probes, probe_text, geo, pid):
     """the ACGT members of the touched (left,right) pairs with plain flanks in the genomes gis (texts[i] = genome gis[i]):
     one kr_wide_run per genome against a probe genome made of the pairs (left + A..A + right) returns every window of
     that genome whose flanks are one of them.  -> {(left,right): {(left,diag,right): {genome: count}}}"""
-    from . import _native
     L, D, R = geo
     members = {}
     if not probes:
@@ -445,7 +449,6 @@ def _mixed_wide_groups(groups, run):
 def _find_regions_device_ingest(files, run):
     """find_regions' packed path; a genome set the plan thought would fit and the device then could not hold (the plan
     is an estimate: candidate lists, slices of a skewed genome, another process on the device) is run again in batches"""
-    from . import _native
     try:
         return _device_ingest_flow(files, run, None)
     except _native.KrispHipError as e:
@@ -461,7 +464,6 @@ def _device_ingest_flow(files, run, force_batch):
     hands each text to the GPU (parse -> sort) as it arrives (the device reader equals kr_fasta_to_bases byte for byte:
     tests/test_gpu_kernels.py)."""
     from concurrent.futures import ThreadPoolExecutor
-    from . import _native
     Le, De, Re = run.geo
     try:
         est = max(fasta.estimate_text_bytes(f) for f in files)
@@ -594,6 +596,28 @@ def _plan_batch(eng, nfiles, est_bases):
     return max(1, fit)
 
 
+def _interleave(a, b):
+    """a[0], b[0], a[1], b[1], ... and the longer list's tail: a first batch, a round-robin shard holds both kinds"""
+    n = min(len(a), len(b))
+    return [x for pair in zip(a, b) for x in pair] + a[n:] + b[n:]
+
+
+def _first_min(flags, apply_f):
+    """the least size of the first batch of genomes with these ingroup flags: it must hold both sides when there are two
+    and the filter applies -- with one side only nothing prunes, and its candidate list is every (left,right) pair of its
+    genomes (more than 2^32 entries at 3 Gbp -- the library refuses such a list, kr_intersect: KR_ERR_CAPACITY)"""
+    return 2 if (any(flags) and not all(flags) and apply_f) else 1
+
+
+def _batches(order, bsz, first_min):
+    """`order` in slices of bsz, the first of max(bsz, first_min) (_first_min; `order` is interleaved: _interleave)"""
+    a = 0
+    while a < len(order):
+        m = max(bsz, first_min) if a == 0 else bsz
+        yield order[a:a + m]
+        a += m
+
+
 def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
     """find_regions for a genome set that does not fit the GPU at once (the reference has no such limit: it sorts in
     external memory, kstream.py:108-119, and merges files pairwise, intersectAmplicons.py:232-310).  The genomes go
@@ -605,45 +629,32 @@ def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
     outgroup, no filter: every conserved pair is a candidate) or IUPAC windows touch groups whose ACGT members must be
     looked up, a second pass sorts every batch again and collects then.  Same records, same order, same text as the
     in-core flow (tests/test_gpu_cli.py).  -> (records, RNA per genome, touched (left,right) pairs, their groups, stats)"""
-    from . import _native
     Le, De, Re = run.geo
     labels, flags = run.labels, run.flags
     n = len(files)
-    ing = [i for i in range(n) if flags[i]]
-    outg = [i for i in range(n) if not flags[i]]
-    order = []
-    for j in range(max(len(ing), len(outg))):
-        order += ing[j:j + 1] + outg[j:j + 1]
+    order = _interleave([i for i in range(n) if flags[i]], [i for i in range(n) if not flags[i]])
     apply_f = run.do_filter and not run.quirk_all_fail
     rank_of = {g: r for r, g in enumerate(sorted(range(n), key=lambda i: labels[i]))}
     rna, specials, counts = [None] * n, [None] * n, [0] * n
     pmask = np.uint64((~0 << (64 - 2 * (Le + Re))) & 0xFFFFFFFFFFFFFFFF) if Le + Re < 32 else np.uint64(0xFFFFFFFFFFFFFFFF)
     stats = {"streamed": True, "batch": batch, "passes": 1, "batches": 0}
-    read_s = [None]
-    maxb = [max_bases]
-
-    # the first batch must hold both sides when there are two: with one side only nothing prunes, and its candidate list
-    # is every (left,right) pair of its genomes (ADVICE r5: more than 2^32 entries at 3 Gbp -- the library refuses such a
-    # list, kr_intersect: KR_ERR_CAPACITY)
-    first_min = 2 if (ing and outg and apply_f) else 1
-
-    def batches(bsz):
-        a = 0
-        while a < n:
-            m = max(bsz, first_min) if a == 0 else bsz
-            yield order[a:a + m]
-            a += m
+    read_s = None
+    first_min = _first_min(flags, apply_f)
+    running = None          # number of running candidates; the list itself stays on the device between the batches of pass 1
+    eager = True            # (kr_genome_free does not touch it: no copy to the host and back per batch -- ADVICE r5)
+    kept = []
 
     def load_batch(ids_b, futs, first_pass):
         """texts -> device, sorted; a batch that does not fit after all is given back whole (KrispHipError, code capacity)"""
+        nonlocal read_s, max_bases
         done = []
         texts = {g: futs[g].result() for g in ids_b}
-        if read_s[0] is None:
-            read_s[0] = time.time() - run.t0
+        if read_s is None:
+            read_s = time.time() - run.t0
         biggest = max(len(t) for t, _ in texts.values())
-        if biggest > maxb[0]:
+        if biggest > max_bases:
             # (the plan came from the files' sizes: a text longer than it said -- nothing is resident between batches)
-            maxb[0] = biggest
+            max_bases = biggest
             eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=biggest)
         try:
             for g in ids_b:
@@ -667,7 +678,7 @@ def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
     def run_pass(bsz, first_pass, work):
         """every batch through load_batch + work(ids_b); the next batch's files are read while this one is on the device;
         a batch the device cannot hold is halved and tried again (the plan is an estimate)"""
-        todo = list(batches(bsz))
+        todo = list(_batches(order, bsz, first_min))
         futs = {}
         while todo:
             ids_b = todo.pop(0)
@@ -679,14 +690,14 @@ def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
             except _native.KrispHipError as e:
                 if e.code != _native.ERR_CAPACITY or len(ids_b) == 1:
                     raise
-                if first_pass and running[0] is None and len(ids_b) <= first_min:
+                if first_pass and running is None and len(ids_b) <= first_min:
                     err = _native.KrispHipError(
                         f"the device cannot hold one ingroup and one outgroup genome sorted at once ({e}); the first batch "
                         "needs both sides for the diagnostic filter to prune")
                     err.code = e.code
                     raise err from e
                 half = (len(ids_b) + 1) // 2
-                if first_pass and running[0] is None:
+                if first_pass and running is None:
                     half = max(half, first_min)
                 todo = [ids_b[:half], ids_b[half:]] + todo
                 for g in ids_b:
@@ -705,49 +716,44 @@ def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
     mixed = any(kinds) and not all(kinds)
     if mixed:
         eng.set_mixed_alphabets(True)
-    running = [None]        # number of running candidates; the list itself stays on the device between the batches of pass 1
-    eager = [True]          # (kr_genome_free does not touch it: no copy to the host and back per batch -- ADVICE r5)
-    kept = []
 
     def pass1(ids_b):
+        nonlocal running, eager
         bflags = [flags[g] for g in ids_b]
-        if running[0] is None:
-            running[0] = eng.intersect(ids_b, bflags, apply_filter=apply_f)
+        if running is None:
+            running = eng.intersect(ids_b, bflags, apply_filter=apply_f)
         else:
             # (a later batch looks the running candidates up in its genomes -- kr_cands_probe: presence in every genome,
             # their diagnostic bases into the masks, the filter -- instead of being intersected whole: the candidate list
             # of a batch that holds one side only is every prefix of its genomes, 24 bytes each)
-            running[0] = eng.probe_cands(ids_b, bflags, apply_filter=apply_f)
+            running = eng.probe_cands(ids_b, bflags, apply_filter=apply_f)
         if run.verbose:
             for g in ids_b:
                 print(f"=> Extracted and sorted {counts[g]:,} {run.k}-kmers from {files[g]}", file=sys.stderr)
-        if run.quirk_all_fail or not running[0]:
+        if run.quirk_all_fail or not running:
             return
-        if eager[0] and running[0] <= STREAM_EAGER_MAX:
+        if eager and running <= STREAM_EAGER_MAX:
             kept.append(eng.collect(sorted(ids_b, key=lambda g: rank_of[g])))
         else:
-            eager[0] = False
+            eager = False
             kept.clear()
 
     run_pass(batch, True, pass1)
-    if mixed and running[0]:
-        running[0] = _mixed_prefix_filter(eng, Le, Re)
-    final = eng.cands().copy() if running[0] else np.empty(0, dtype=_native.CAND)
+    if mixed and running:
+        running = _mixed_prefix_filter(eng, Le, Re)
+    final = eng.cands().copy() if running else np.empty(0, dtype=_native.CAND)
     stats["mixed_rna"] = [bool(r) for r in rna] if mixed else None
-    touched = {(l, r) for sp in specials for (l, d, r) in sp} if not run.quirk_all_fail else set()
-    pure = sorted({_prefix_key(l, r) for (l, r) in touched if _pure(l) and _pure(r)})
+    touched, tc = _touched_prefix_cands([] if run.quirk_all_fail else specials)
     srecs = []
-    if (len(final) and not eager[0] and not run.quirk_all_fail) or pure:
+    if (len(final) and not eager and not run.quirk_all_fail) or len(tc):
         stats["passes"] = 2
-        tc = np.zeros(len(pure), dtype=_native.CAND)
-        tc["prefix"] = np.array(pure, dtype=np.uint64)
 
         def pass2(ids_b):
             by = sorted(ids_b, key=lambda g: rank_of[g])
-            if len(final) and not eager[0]:
+            if len(final) and not eager:
                 eng.load_cands(final)
                 kept.append(eng.collect(by))
-            if pure:
+            if len(tc):
                 eng.load_cands(tc)
                 srecs.append(eng.collect(by))
         run_pass(max(1, stats["batch"]), False, pass2)
@@ -763,7 +769,7 @@ def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
         recs = np.concatenate(srecs) if srecs else None
         sgroups = _special_groups_from(recs, list(range(n)), labels, specials, run.geo, run.ingroup_labels, run.do_filter,
                                        rna_genomes=[bool(r) for r in rna] if mixed else None)
-    stats.update(read_s=read_s[0] or 0.0, kmers=int(sum(counts)) + sum(len(sp) for sp in specials), candidates=int(len(final)))
+    stats.update(read_s=read_s or 0.0, kmers=int(sum(counts)) + sum(len(sp) for sp in specials), candidates=int(len(final)))
     return records, [bool(r) for r in rna], touched, sgroups, stats
 
 
@@ -776,7 +782,6 @@ def _find_regions_wide(files, run, host_parse):
     whose probe text is longer than its genomes.  -> (groups, stats), or None: the probe text does not fit, take the host
     parse."""
     from concurrent.futures import ThreadPoolExecutor
-    from . import _native
     Le, De, Re = run.geo
     with ThreadPoolExecutor(max_workers=run.workers) as pool:
         if host_parse:
@@ -898,278 +903,281 @@ class PeerFailed(RuntimeError):
     """another rank of a multi-GPU run raised; this rank stops with it instead of waiting in a collective"""
 
 
-def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft):
-    """one rank of the multi-GPU flow (see find_regions_distributed); `connect(engine)` gives the
-    engine its communicator.  Returns (groups, stats) on rank 0 and (None, stats) elsewhere."""
-    from . import _native
-    from . import distributed as D
-    # interleave ingroup / outgroup files so that a round-robin shard holds both kinds
-    ing, outg = list(ingroup_files), list(outgroup_files)
-    order = []
-    for i in range(max(len(ing), len(outg))):
-        if i < len(ing):
-            order.append(ing[i])
-        if i < len(outg):
-            order.append(outg[i])
-    # (amplicons longer than one key: kr_wide_run, collective inside; a lone genome is labelled by its file here)
-    run = _describe_run([simplename(f) for f in order], ing, L, R, amplicon_len, omit_soft, device, False)
-    if len(order) < world:
-        raise ValueError(f"{len(order)} genomes cannot be sharded over {world} GPUs")
-    Le, De, Re = run.geo
-    mine = D.shard(list(range(len(order))), rank, world)
+class _Rank(NamedTuple):
+    """one rank of a multi-GPU run as its phases see it (_rank_read_and_agree fills it)"""
+    eng: object                 # its context, connected to the other ranks'
+    rank: int
+    world: int
+    order: list                 # the run's files, ingroup and outgroup interleaved: a genome's number is its place here
+    mine: list                  # the genomes this rank holds (distributed.shard)
+    loaded: list                # fasta.ingest of each of them: (bases, is RNA, windows with IUPAC letters)
+    run: _Run
+    max_bases: int              # the longest genome of any rank
+    mixed: bool                 # DNA and RNA genomes in one run
+    all_rna: bool
+    rna_all: list               # a mixed run: RNA or not, per genome of the run (else None)
+    specials_all: list          # every genome's IUPAC windows as (left, diag, right) when any rank has one (else None)
 
-    with _native.Engine(device=device) as eng:
-        connect(eng)
 
-        def together(fn):
-            """run fn() on this rank; every rank learns whether all succeeded before anyone goes on"""
-            err, out = None, None
-            try:
-                out = fn()
-            except BaseException as e:  # noqa: BLE001
-                err = e
-            failed = eng.comm_allreduce([1.0 if err is not None else 0.0], "max")[0] > 0
-            if err is not None:
-                raise err
-            if failed:
-                raise PeerFailed(f"rank {rank}: another rank failed")
-            return out
+def _together(eng, rank, fn):
+    """run fn() on this rank; every rank learns whether all succeeded before anyone goes on (one all-reduce per call)"""
+    err, out = None, None
+    try:
+        out = fn()
+    except BaseException as e:  # noqa: BLE001
+        err = e
+    failed = eng.comm_allreduce([1.0 if err is not None else 0.0], "max")[0] > 0
+    if err is not None:
+        raise err
+    if failed:
+        raise PeerFailed(f"rank {rank}: another rank failed")
+    return out
 
-        run = run._replace(t0=time.time())          # (the clock starts once the rank is connected)
-        loaded = together(lambda: [fasta.ingest(order[g], run.k, run.omit_soft) for g in mine])
-        kinds = eng.comm_allreduce([1.0 if any(sp for _, _, sp in loaded) else 0.0,
-                                    1.0 if any(r for _, r, _ in loaded) else 0.0,
-                                    float(max(len(b) for b, _, _ in loaded)),
-                                    1.0 if any(not r for _, r, _ in loaded) else 0.0], "max")
-        mixed = bool(kinds[1] and kinds[3])
-        all_rna = bool(kinds[1]) and not mixed
-        rna_all = None
-        if mixed:
-            # DNA and RNA genomes in one run (round 6; find_regions has the rules): every rank learns every genome's alphabet,
-            # every context filters in mode 2, the candidates whose (left,right) pair holds T / U go, rank 0 decides the rest on text
-            if kinds[0]:
-                raise MixedAlphabet("some genomes are RNA (U) and some DNA (T), and windows hold IUPAC letters")
-            import json
-            rna_all = [False] * len(order)
-            for blob in eng.comm_allgather(json.dumps({int(g): bool(r) for g, (_, r, _) in zip(mine, loaded)}).encode()):
-                for g, r in json.loads(blob.decode()).items():
-                    rna_all[int(g)] = bool(r)
-            eng.set_mixed_alphabets(True)
-        # windows with IUPAC letters (kept by the reference, kstream.py:11-18; the device alphabet cannot carry them):
-        # every rank learns all of them -- they are rare --, the groups they touch are rebuilt on rank 0 from the
-        # ranks' device look-ups of the ACGT members (below), as find_regions does on one GPU
-        specials_all = None
+
+def _allgather_json(eng, obj):
+    """every rank's `obj`, in rank order, on every rank (one kr_comm_allgather).  Plain data only -- numbers, strings,
+    lists, dicts (whose keys come back as strings) --: nothing executable crosses ranks"""
+    return [json.loads(blob.decode()) for blob in eng.comm_allgather(json.dumps(obj).encode())]
+
+
+def _rank_read_and_agree(eng, rank, world, order, run):
+    """phase 1: the rank reads its files (distributed.shard), and the ranks agree on what the run holds: the longest
+    genome, the alphabets, every window with IUPAC letters.  -> _Rank"""
+    mine = distributed.shard(list(range(len(order))), rank, world)
+    loaded = _together(eng, rank, lambda: [fasta.ingest(order[g], run.k, run.omit_soft) for g in mine])
+    kinds = eng.comm_allreduce([1.0 if any(sp for _, _, sp in loaded) else 0.0,
+                                1.0 if any(r for _, r, _ in loaded) else 0.0,
+                                float(max(len(b) for b, _, _ in loaded)),
+                                1.0 if any(not r for _, r, _ in loaded) else 0.0], "max")
+    mixed = bool(kinds[1] and kinds[3])
+    rna_all = None
+    if mixed:
+        # DNA and RNA genomes in one run (find_regions has the rules): every rank learns every genome's alphabet, every
+        # context filters in mode 2, the candidates whose (left,right) pair holds T / U go, rank 0 decides the rest on text
         if kinds[0]:
-            import json         # (plain data: genome number -> [left, diag, right] strings; nothing executable crosses ranks)
-            mine_sp = {g: [codec.split_window(w, Le, De, Re) for w in sp] for g, (_, _, sp) in zip(mine, loaded)}
-            specials_all = [[] for _ in order]
-            for blob in eng.comm_allgather(json.dumps(mine_sp).encode()):
-                for g, sp in json.loads(blob.decode()).items():
-                    specials_all[int(g)] = [tuple(w) for w in sp]
-        stats = {"read_s": time.time() - run.t0}
-        t1 = time.time()
-        filt = run.do_filter and not run.quirk_all_fail
+            raise MixedAlphabet("some genomes are RNA (U) and some DNA (T), and windows hold IUPAC letters")
+        mine_rna = {g: bool(r) for g, (_, r, _) in zip(mine, loaded)}
+        got = {int(g): r for part in _allgather_json(eng, mine_rna) for g, r in part.items()}
+        rna_all = [got[g] for g in range(len(order))]
+        eng.set_mixed_alphabets(True)
+    # windows with IUPAC letters (kept by the reference, kstream.py:11-18; the device alphabet cannot carry them):
+    # every rank learns all of them -- they are rare --, the groups they touch are rebuilt on rank 0 from the
+    # ranks' device look-ups of the ACGT members, as find_regions does on one GPU
+    specials_all = None
+    if kinds[0]:
+        mine_sp = {g: [codec.split_window(w, *run.geo) for w in sp] for g, (_, _, sp) in zip(mine, loaded)}
+        got = {int(g): sp for part in _allgather_json(eng, mine_sp) for g, sp in part.items()}
+        specials_all = [[tuple(w) for w in got[g]] for g in range(len(order))]
+    return _Rank(eng, rank, world, order, mine, loaded, run, int(kinds[2]), mixed, bool(kinds[1]) and not mixed,
+                 rna_all, specials_all)
 
-        if run.wide:
-            if run.quirk_all_fail:
-                eng.comm_barrier()
-                stats.update(device_s=0.0, kmers=0, candidates=0, records=0)
-                return ([] if rank == 0 else None), stats
 
-            def wide_part():
-                # the spectra lists, the group list and the kept groups' masks are exchanged inside kr_wide_run
-                # (the same calls in the same order on every rank); hits name genomes by their global number
-                eng.set_params_wide(Le, De, Re, omit_soft=run.omit_soft, max_bases=int(kinds[2]))
-                for g, (bases, _, _) in zip(mine, loaded):
-                    eng.upload(g, bases)
-                nh = eng.wide_run(mine, [run.flags[g] for g in mine], apply_filter=run.do_filter)
-                return nh, int(sum(eng.wide_fetch(_native.WIDE_COUNTS).tolist())), int(eng.wide_fetch(_native.WIDE_NGROUPS)[0])
+def _wide_shard_run(rk):
+    """the rank's genomes through kr_wide_run, which exchanges the spectra lists, the group list and the kept groups'
+    masks itself (the same calls in the same order on every rank).  -> (hits: genomes by their global number, k-mers, groups)"""
+    eng, run = rk.eng, rk.run
+    eng.set_params_wide(*run.geo, omit_soft=run.omit_soft, max_bases=rk.max_bases)
+    for g, (bases, _, _) in zip(rk.mine, rk.loaded):
+        eng.upload(g, bases)
+    nh = eng.wide_run(rk.mine, [run.flags[g] for g in rk.mine], apply_filter=run.do_filter)
+    return nh, int(sum(eng.wide_fetch(_native.WIDE_COUNTS).tolist())), int(eng.wide_fetch(_native.WIDE_NGROUPS)[0])
 
-            nh, counts, ngroups = together(wide_part)
-            hits = eng.wide_fetch(_native.WIDE_HITS) if (rank == 0 and nh) else np.empty(0, dtype=_native.WIDE_HIT)
-            # windows with IUPAC letters (round 4; one GPU only before): every rank knows all of them (specials_all), so
-            # every rank derives the same touched (left,right) pairs and the same probe genome, looks the pairs' ACGT
-            # members up in ITS genomes -- a context of its own without a communicator: the look-ups are local, one
-            # kr_wide_run per genome -- and rank 0 gets everybody's findings and rebuilds the touched groups
-            wide_sp = None
-            if specials_all is not None:
-                import json
-                touched_w, probes, probe_text = _touched_pairs(specials_all, De)
 
-                def probe_part():
-                    if not probes:
-                        return {}
-                    with _native.Engine(device=device) as e2:
-                        e2.set_params_wide(Le, De, Re, omit_soft=run.omit_soft, max_bases=max(int(kinds[2]), len(probe_text)))
-                        for g, (bases, _, _) in zip(mine, loaded):
-                            e2.upload(g, bases)
-                        return _wide_probe_members(e2, [b for b, _, _ in loaded], list(mine), probes, probe_text,
-                                                   (Le, De, Re), pid=len(order))
+def _wide_shard_probe(rk, probes, probe_text):
+    """the ACGT members of the touched pairs with plain flanks in THIS rank's genomes -- in a context of its own without
+    a communicator: the look-ups are local, one kr_wide_run per genome.  -> _wide_probe_members' dict"""
+    if not probes:
+        return {}
+    with _native.Engine(device=rk.run.device) as e2:
+        e2.set_params_wide(*rk.run.geo, omit_soft=rk.run.omit_soft, max_bases=max(rk.max_bases, len(probe_text)))
+        for g, (bases, _, _) in zip(rk.mine, rk.loaded):
+            e2.upload(g, bases)
+        return _wide_probe_members(e2, [b for b, _, _ in rk.loaded], list(rk.mine), probes, probe_text, rk.run.geo,
+                                   pid=len(rk.order))
 
-                local = together(probe_part)
-                flat = [[list(P), list(seq), int(g), int(cnt)] for P, seqs in local.items() for seq, m in seqs.items()
-                        for g, cnt in m.items()]
-                members_w = {}
-                for blob in eng.comm_allgather(json.dumps(flat).encode()):
-                    for P, seq, g, cnt in json.loads(blob.decode()):
-                        m = members_w.setdefault(tuple(P), {}).setdefault(tuple(seq), {})
-                        m[g] = m.get(g, 0) + cnt
-                wide_sp = (touched_w, members_w)
-            eng.comm_barrier()
-            stats.update(device_s=time.time() - t1, kmers=counts, candidates=ngroups, records=int(len(hits)))
-            if rank != 0:
-                return None, stats
-            # rank 0 cuts the windows' text: its own genomes are in memory, the others' files are read here
-            texts = [None] * len(order)
-            for g, (bases, _, _) in zip(mine, loaded):
-                texts[g] = bases
-            for g in sorted(set(hits["genome"].tolist())):
-                if texts[g] is None:
-                    texts[g] = fasta.ingest(order[g], run.k, run.omit_soft)[0]
-            wg = _groups_from_hits(hits, texts, run.labels, Le, De, Re, rna_genomes=rna_all)
-            if mixed:
-                wg = _mixed_wide_groups(wg, run)
-                stats["candidates"] = len(wg)
-                return wg, stats
-            if wide_sp is not None:
-                touched_w, members_w = wide_sp
-                sg = _special_groups_wide_from(members_w, len(order), run.labels, specials_all, touched_w, run.ingroup_labels,
-                                               run.do_filter)
-                wg = _merge_groups(wg, touched_w, sg)
-            return (_to_rna(wg) if all_rna else wg), stats
 
-        # Round 6 (VERDICT r5 item 6): a rank whose shard does not fit its GPU sorted at once takes it in batches, as
-        # find_regions does on one GPU (_find_regions_streaming): the first batch intersected, later batches probed, the
-        # batch freed; the exchange of the candidate lists is the same; the records are then collected batch by batch in a
-        # second pass over the shard and travel to rank 0 as bytes (kr_comm_allgather) instead of from the device buffer of
-        # ONE kr_collect.  KRISP_STREAM_BATCH=n forces batches of n genomes per rank (tests).
-        bases_of = {g: b for g, (b, _, _) in zip(mine, loaded)}
-        flag_of = {g: run.flags[g] for g in mine}
-        batched = [None]
-
-        def shard_batches():
-            B = batched[0]
-            both = any(flag_of.values()) and not all(flag_of.values()) and filt
-            at, first = 0, True
-            while at < len(mine):
-                m = max(B, 2) if (first and both) else B        # (the first batch holds both sides: nothing prunes else)
-                yield mine[at:at + m]
-                at, first = at + m, False
-
-        def device_part():
-            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=int(kinds[2]))
-            batched[0] = _plan_batch(eng, len(mine), int(kinds[2])) if len(mine) > 1 else None
-            if batched[0] is None:
-                for g in mine:
-                    eng.upload(g, bases_of[g])
-                    eng.sort(g)
-                eng.intersect(mine, [flag_of[g] for g in mine], apply_filter=filt)    # safe local pruning
-                return sum(eng.count(g) for g in mine)
-            total, running = 0, None
-            for ids_b in shard_batches():
-                for g in ids_b:
-                    eng.upload(g, bases_of[g])
-                    eng.sort(g)
-                fl = [flag_of[g] for g in ids_b]
-                running = eng.intersect(ids_b, fl, apply_filter=filt) if running is None else \
-                    eng.probe_cands(ids_b, fl, apply_filter=filt)
-                total += sum(eng.count(g) for g in ids_b)
-                for g in ids_b:
-                    eng.free(g)
-            return total
-
-        def collect_shard():
-            """this rank's records of the candidates now on the device -> numpy (batched shards: a pass over the batches)"""
-            cands = eng.cands().copy()
-            parts = []
-            for ids_b in shard_batches():
-                for g in ids_b:
-                    eng.upload(g, bases_of[g])
-                    eng.sort(g)
-                eng.load_cands(cands)
-                if len(cands):
-                    parts.append(eng.collect(ids_b))
-                for g in ids_b:
-                    eng.free(g)
-            return np.concatenate(parts) if parts else np.empty(0, dtype=_native.RECORD)
-
-        def gather_host_records(recs):
-            """every rank's record array -> rank 0 (None elsewhere), as bytes through kr_comm_allgather"""
-            got = eng.comm_allgather(np.ascontiguousarray(recs).tobytes())
-            if rank != 0:
-                return None
-            parts = [np.frombuffer(b, dtype=_native.RECORD) for b in got if len(b)]
-            return np.concatenate(parts) if parts else np.empty(0, dtype=_native.RECORD)
-
-        counts = together(device_part)
-        # (every rank learns whether ANY rank took its shard in batches: the records then travel as bytes on all of them)
-        any_batched = eng.comm_allreduce([1.0 if batched[0] is not None else 0.0], "max")[0] > 0
-        if any_batched and batched[0] is None:
-            batched[0] = len(mine)
-        ncand = eng.cands_reduce(apply_filter=filt)
-        eng.cands_bcast()
-        if mixed:
-            together(lambda: _mixed_prefix_filter(eng, Le, Re))       # (the same list on every rank: the same cut)
-        if any_batched:
-            myrec = together(lambda: np.empty(0, dtype=_native.RECORD) if run.quirk_all_fail else collect_shard())
-            nrec = len(myrec)
-            allrec = gather_host_records(myrec) if not run.quirk_all_fail else None
-        else:
-            nrec = together(lambda: 0 if run.quirk_all_fail else eng.collect(mine, fetch=False))
-            total = eng.records_gather() if not run.quirk_all_fail else 0
-            allrec = eng.fetch_records(total) if rank == 0 and not run.quirk_all_fail else None
-        sprec, touched = None, set()
-        if specials_all is not None and not run.quirk_all_fail:
-            # the ACGT members of every (left,right) group an IUPAC window touches: each rank looks them up in ITS
-            # genomes (the touched prefixes as a candidate list), rank 0 gets all the records
-            touched = {(l, r) for sp in specials_all for (l, d, r) in sp}
-            pure = sorted({_prefix_key(l, r) for (l, r) in touched if _pure(l) and _pure(r)})
-
-            def special_lookups():
-                if not pure:
-                    return 0
-                cands = np.zeros(len(pure), dtype=_native.CAND)
-                cands["prefix"] = np.array(pure, dtype=np.uint64)
-                eng.load_cands(cands)
-                return collect_shard() if any_batched else eng.collect(mine, fetch=False)
-
-            sp_local = together(special_lookups)
-            if pure and any_batched:
-                sprec = gather_host_records(sp_local)
-            elif pure:
-                tot2 = eng.records_gather()
-                sprec = eng.fetch_records(tot2) if rank == 0 else None
+def _rank_wide(rk, stats):
+    """phase 2 of a run whose amplicons are longer than one key: kr_wide_run, the IUPAC windows' probe look-ups, rank
+    0's text cutting.  -> (groups on rank 0, None elsewhere; stats)"""
+    eng, rank, run = rk.eng, rk.rank, rk.run
+    t1 = time.time()
+    if run.quirk_all_fail:
         eng.comm_barrier()
-        stats.update(device_s=time.time() - t1, kmers=int(counts) + (sum(len(sp) for sp in specials_all) if specials_all else 0),
-                     candidates=int(max(ncand, 0)), records=int(nrec))
+        stats.update(device_s=0.0, kmers=0, candidates=0, records=0)
+        return ([] if rank == 0 else None), stats
+    nh, counts, ngroups = _together(eng, rank, lambda: _wide_shard_run(rk))
+    hits = eng.wide_fetch(_native.WIDE_HITS) if (rank == 0 and nh) else np.empty(0, dtype=_native.WIDE_HIT)
+    # windows with IUPAC letters: every rank knows all of them (specials_all), so every rank derives the same touched
+    # (left,right) pairs and the same probe genome and looks the pairs' ACGT members up in ITS genomes; rank 0 gets
+    # everybody's findings and rebuilds the touched groups
+    touched, members = set(), {}
+    if rk.specials_all is not None:
+        touched, probes, probe_text = _touched_pairs(rk.specials_all, run.geo[1])
+        local = _together(eng, rank, lambda: _wide_shard_probe(rk, probes, probe_text))
+        flat = [[list(P), list(seq), int(g), int(cnt)] for P, seqs in local.items() for seq, m in seqs.items()
+                for g, cnt in m.items()]
+        for part in _allgather_json(eng, flat):
+            for P, seq, g, cnt in part:
+                m = members.setdefault(tuple(P), {}).setdefault(tuple(seq), {})
+                m[g] = m.get(g, 0) + cnt
+    eng.comm_barrier()
+    stats.update(device_s=time.time() - t1, kmers=counts, candidates=ngroups, records=int(len(hits)))
     if rank != 0:
         return None, stats
-    sgroups = []
-    if touched:
-        sgroups = _special_groups_from(sprec, list(range(len(order))), run.labels, specials_all, run.geo,
-                                       run.ingroup_labels, run.do_filter)
-    # (a mixed run holds no IUPAC windows: MixedAlphabet above)
-    return _packed_result(allrec, run, rna_all if mixed else [all_rna] * len(order), touched, sgroups, stats)
+    # rank 0 cuts the windows' text: its own genomes are in memory, the others' files are read here
+    texts = {g: bases for g, (bases, _, _) in zip(rk.mine, rk.loaded)}
+    for g in sorted(set(hits["genome"].tolist()) - set(texts)):
+        texts[g] = fasta.ingest(rk.order[g], run.k, run.omit_soft)[0]
+    wg = _groups_from_hits(hits, [texts.get(g) for g in range(len(rk.order))], run.labels, *run.geo, rna_genomes=rk.rna_all)
+    if rk.mixed:
+        wg = _mixed_wide_groups(wg, run)
+        stats["candidates"] = len(wg)
+        return wg, stats
+    if rk.specials_all is not None:
+        sg = _special_groups_wide_from(members, len(rk.order), run.labels, rk.specials_all, touched, run.ingroup_labels,
+                                       run.do_filter)
+        wg = _merge_groups(wg, touched, sg)
+    return (_to_rna(wg) if rk.all_rna else wg), stats
+
+
+def _shard_batches(rk, bsz):
+    """the rank's genomes through its device, bsz at a time: upload and sort a batch, hand it to the caller's loop body,
+    free it.  bsz None: the whole shard at once, and it stays on the device"""
+    eng, run = rk.eng, rk.run
+    bases_of = {g: b for g, (b, _, _) in zip(rk.mine, rk.loaded)}
+    first_min = _first_min([run.flags[g] for g in rk.mine], run.do_filter and not run.quirk_all_fail)
+    for ids_b in ([rk.mine] if bsz is None else _batches(rk.mine, bsz, first_min)):
+        for g in ids_b:
+            eng.upload(g, bases_of[g])
+            eng.sort(g)
+        yield ids_b
+        if bsz is not None:
+            for g in ids_b:
+                eng.free(g)
+
+
+def _shard_intersect(rk, filt):
+    """the rank's candidates from its own genomes (safe local pruning).  A shard that does not fit its GPU sorted at once
+    goes through it in batches, as find_regions does on one GPU (_find_regions_streaming): the first intersected, the
+    later ones probed; KRISP_STREAM_BATCH=n forces batches of n per rank (tests).  -> (batch size or None, k-mers)"""
+    eng, run = rk.eng, rk.run
+    eng.set_params(*run.geo, omit_soft=run.omit_soft, max_bases=rk.max_bases)
+    bsz = _plan_batch(eng, len(rk.mine), rk.max_bases) if len(rk.mine) > 1 else None
+    total, running = 0, None
+    for ids_b in _shard_batches(rk, bsz):
+        fl = [run.flags[g] for g in ids_b]
+        running = eng.intersect(ids_b, fl, apply_filter=filt) if running is None else \
+            eng.probe_cands(ids_b, fl, apply_filter=filt)
+        total += sum(eng.count(g) for g in ids_b)
+    return bsz, total
+
+
+def _shard_collect(rk, bsz, cands=None):
+    """the rank's records of the candidates on the device (of `cands`, loaded first, if given).  bsz None: the shard is
+    there -- one kr_collect, the records stay in its buffer -> their number; else a pass over the batches -> the records"""
+    eng = rk.eng
+    if cands is not None:
+        eng.load_cands(cands)
+    if bsz is None:
+        return eng.collect(rk.mine, fetch=False)
+    cands = eng.cands().copy()
+    parts = []
+    for ids_b in _shard_batches(rk, bsz):
+        eng.load_cands(cands)
+        if len(cands):
+            parts.append(eng.collect(ids_b))
+    return np.concatenate(parts) if parts else np.empty(0, dtype=_native.RECORD)
+
+
+def _records_to_rank0(rk, any_batched, bsz, cands=None, wanted=True):
+    """every rank's records of the candidates (of `cands`) -> rank 0: one _together (_shard_collect; no work in it if not
+    wanted), then, if wanted, their way there -- as bytes (kr_comm_allgather) when any rank took its shard in batches,
+    else from the device buffers (kr_records_gather).  -> (this rank's number of records, all records on rank 0)"""
+    eng = rk.eng
+    local = _together(eng, rk.rank, lambda: _shard_collect(rk, bsz, cands) if wanted else 0)
+    if not wanted:
+        return 0, None
+    if not any_batched:
+        total = eng.records_gather()
+        return local, (eng.fetch_records(total) if rk.rank == 0 else None)
+    got = eng.comm_allgather(np.ascontiguousarray(local).tobytes())
+    if rk.rank != 0:
+        return len(local), None
+    parts = [np.frombuffer(b, dtype=_native.RECORD) for b in got if len(b)]
+    return len(local), (np.concatenate(parts) if parts else np.empty(0, dtype=_native.RECORD))
+
+
+def _rank_packed(rk, stats):
+    """phase 2 of a run of packed keys: local candidates, their reduction over the ranks, the survivors' records and the
+    IUPAC look-ups' records to rank 0.  -> (records, touched pairs, the look-ups' records)"""
+    eng, rank, run = rk.eng, rk.rank, rk.run
+    t1 = time.time()
+    filt = run.do_filter and not run.quirk_all_fail
+    bsz, counts = _together(eng, rank, lambda: _shard_intersect(rk, filt))
+    # every rank learns whether ANY rank took its shard in batches: the records are then collected in a second pass over
+    # the shard and travel to rank 0 as bytes on all of them, instead of from the device buffer of ONE kr_collect
+    any_batched = eng.comm_allreduce([1.0 if bsz is not None else 0.0], "max")[0] > 0
+    if any_batched and bsz is None:
+        bsz = len(rk.mine)
+    ncand = eng.cands_reduce(apply_filter=filt)
+    eng.cands_bcast()
+    if rk.mixed:                # (the same list on every rank: the same cut)
+        _together(eng, rank, lambda: _mixed_prefix_filter(eng, run.geo[0], run.geo[2]))
+    nrec, allrec = _records_to_rank0(rk, any_batched, bsz, wanted=not run.quirk_all_fail)
+    sprec, touched = None, set()
+    if rk.specials_all is not None and not run.quirk_all_fail:
+        # the ACGT members of every (left,right) group an IUPAC window touches: each rank looks them up in ITS
+        # genomes (the touched prefixes as a candidate list), rank 0 gets all the records
+        touched, tc = _touched_prefix_cands(rk.specials_all)
+        _, sprec = _records_to_rank0(rk, any_batched, bsz, cands=tc, wanted=len(tc) > 0)
+    eng.comm_barrier()
+    stats.update(device_s=time.time() - t1, kmers=int(counts) + sum(len(sp) for sp in rk.specials_all or []),
+                 candidates=int(max(ncand, 0)), records=int(nrec))
+    return allrec, touched, sprec
+
+
+def _distributed_rank(rank, world, device, connect, ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft):
+    """one rank of the multi-GPU flow (see find_regions_distributed); `connect(engine)` gives the
+    engine its communicator.  Returns (groups, stats) on rank 0 and (None, stats) elsewhere.  Every rank issues the same
+    collectives in the same order (DESIGN.md section 8 lists them): the phases below, read top to bottom."""
+    # (interleaved so that a round-robin shard holds both kinds; a lone genome is labelled by its file here)
+    order = _interleave(list(ingroup_files), list(outgroup_files))
+    run = _describe_run([simplename(f) for f in order], list(ingroup_files), L, R, amplicon_len, omit_soft, device, False)
+    if len(order) < world:
+        raise ValueError(f"{len(order)} genomes cannot be sharded over {world} GPUs")
+    with _native.Engine(device=device) as eng:
+        connect(eng)
+        run = run._replace(t0=time.time())          # (the clock starts once the rank is connected)
+        rk = _rank_read_and_agree(eng, rank, world, order, run)
+        stats = {"read_s": time.time() - run.t0}
+        if run.wide:                                # (amplicons longer than one key: kr_wide_run)
+            return _rank_wide(rk, stats)
+        allrec, touched, sprec = _rank_packed(rk, stats)
+    if rank != 0:
+        return None, stats
+    sgroups = _special_groups_from(sprec, list(range(len(order))), run.labels, rk.specials_all, run.geo,
+                                   run.ingroup_labels, run.do_filter) if touched else []
+    # (a mixed run holds no IUPAC windows: MixedAlphabet in _rank_read_and_agree)
+    return _packed_result(allrec, run, rk.rna_all if rk.mixed else [rk.all_rna] * len(order), touched, sgroups, stats)
 
 
 def find_regions_distributed(ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=False,
                              transport="rccl", verbose=False):
-    """find_regions over several GPUs: one process per GPU (started by torch.distributed.run,
-    mpirun, srun ...: RANK / LOCAL_RANK / WORLD_SIZE in the environment; no PyTorch involved).
-    Genomes are sharded round-robin over the ranks (ingroup and outgroup files interleaved so that
-    every rank can prune with the monotone filter), each rank sorts and intersects its own, the
-    candidate lists are tree-reduced between the GPUs (kr_cands_reduce: RCCL, device to device),
-    the survivors broadcast, every rank collects its genomes' records and rank 0 gathers them.
-    Returns (groups, stats) on rank 0 and (None, stats) elsewhere.  Amplicons longer than one key
-    take kr_wide_run, which exchanges the flank spectra, the group list and the kept groups' masks
-    between the ranks itself.  No IUPAC letters, no RNA: those need look-ups across all genomes
-    and stay on one GPU.  A rank that fails (missing file, illegal character, out of memory) makes every
-    rank raise before the next collective: nobody is left waiting."""
-    from . import distributed as D
-    rank, local_rank, world = D.env_rank_world()
+    """find_regions over several GPUs: one process per GPU (started by torch.distributed.run, mpirun, srun ...: RANK /
+    LOCAL_RANK / WORLD_SIZE in the environment; no PyTorch involved).  Genomes are sharded round-robin over the ranks
+    (ingroup and outgroup files interleaved so that every rank can prune with the monotone filter); each rank sorts and
+    intersects its own -- in batches when its shard does not fit its GPU sorted at once --, the candidate lists are
+    tree-reduced between the GPUs (kr_cands_reduce: RCCL, device to device), the survivors broadcast, every rank collects
+    its genomes' records and rank 0 gathers them.  Amplicons longer than one key take kr_wide_run, which exchanges the
+    flank spectra, the group list and the kept groups' masks between the ranks itself.  Windows with IUPAC letters go to
+    every rank; each looks the ACGT members of the groups they touch up in its genomes, rank 0 rebuilds those groups.  An
+    all-RNA run is written with U; one that mixes DNA and RNA genomes filters in the mixed mode and rank 0 decides on text
+    (MixedAlphabet if it holds IUPAC windows too).  A rank that fails (missing file, illegal character, out of memory)
+    makes every rank raise before the next collective.  Returns (groups, stats) on rank 0 and (None, stats) elsewhere."""
+    rank, local_rank, world = distributed.env_rank_world()
     if transport == "dir":                 # rehearsal: the ranks share the visible GPU(s)
         local_rank %= max(1, int(os.environ.get("KRISP_VISIBLE_GPUS", "1")))
-    return _distributed_rank(rank, world, local_rank, lambda eng: D.connect(eng, rank, world, transport=transport),
+    return _distributed_rank(rank, world, local_rank, lambda eng: distributed.connect(eng, rank, world, transport=transport),
                              ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft)
 
 
@@ -1182,7 +1190,6 @@ def find_regions_multi_device(ingroup_files, outgroup_files, L, R, amplicon_len,
     duplicate devices): that is how a one-GPU box rehearses it.  Returns (groups, stats)."""
     import tempfile
     import threading
-    from . import _native
     world = len(devices)
     if world < 1:
         raise ValueError("find_regions_multi_device: no device listed")
@@ -1190,15 +1197,12 @@ def find_regions_multi_device(ingroup_files, outgroup_files, L, R, amplicon_len,
     cid = _native.comm_unique_id() if use_rccl else None
     results, errors = [None] * world, [None] * world
     with tempfile.TemporaryDirectory(prefix="krisp_comm_") as td:
-        def connect_for(rank):
-            if use_rccl:
-                return lambda eng: eng.comm_init(rank, world, cid)
-            return lambda eng: eng.comm_init_dir(rank, world, td)
-
         def work(rank):
+            connect = (lambda eng: eng.comm_init(rank, world, cid)) if use_rccl else \
+                (lambda eng: eng.comm_init_dir(rank, world, td))
             try:
-                results[rank] = _distributed_rank(rank, world, devices[rank], connect_for(rank), ingroup_files,
-                                                  outgroup_files, L, R, amplicon_len, omit_soft)
+                results[rank] = _distributed_rank(rank, world, devices[rank], connect, ingroup_files, outgroup_files,
+                                                  L, R, amplicon_len, omit_soft)
             except BaseException as e:  # noqa: BLE001
                 errors[rank] = e
         threads = [threading.Thread(target=work, args=(r,), name=f"krisp-gpu{devices[r]}") for r in range(world)]
@@ -1232,7 +1236,6 @@ def _extract_sorted_wide(fasta_file, L, R, k, output, omit, device, verbose):
     the genome alone through kr_wide_run without a filter -- every window then belongs to a
     (left,right) group, the groups come in (left,right) order -- and the members of a group put in
     diag order here; lines 'left,diag,right' as kstream.py:832 writes them."""
-    from . import _native
     Le, De, Re = codec.effective_geometry(L, k - L - R, R)
     _check_wide(Le, De, Re)
     bases, rna, special = fasta.ingest(fasta_file, k, omit)
@@ -1344,7 +1347,6 @@ def mergeFiles(files, output, parallel=1, workdir=None, verbose=True, device=0):
     one line 'left,diag,right,labels' per distinct sequence.  The keys of each file
     are packed on the host and adopted by the device as a sorted genome
     (kr_genome_load_sorted); the intersection and the collect run there."""
-    from . import _native
     files = list(files)
     t0 = time.time()
     if len(files) == 1:
@@ -1412,7 +1414,6 @@ def _merge_files_wide(contents, labels, L, D, R, device):
     """mergeFiles for k-mer files of amplicons longer than one key: every file becomes a "genome"
     whose records are its lines (one window each, forward strand only: the file already holds both
     strands), kr_wide_run finds the (left,right) pairs present in all files and where their members lie."""
-    from . import _native
     _check_wide(L, D, R)
     k = L + D + R
     texts, rnas, specials = [], [], []
@@ -1500,7 +1501,6 @@ def filterAlignments(kmerfile, output, ingroup, device=0):
     ingroup and outgroup base sets are disjoint (Amplicon.py:495-521).  The host only
     re-encodes the text (one (in, out) base-set mask pair per group, include/krisp_hip.h
     kr_cand); the predicate itself is evaluated on the device (kr_cands_merge)."""
-    from . import _native
     groups = _parse_merged(kmerfile)
     ingroup = frozenset(ingroup)
     keep = list(range(len(groups)))
@@ -1913,8 +1913,7 @@ def _discover(args):
     """the regions, by the route the launch asks for: a thread per listed device, a process per GPU, or one device
     -> (groups, stats, the device the report passes run on); None on a rank that writes no output"""
     devices = [int(x) for x in str(args.devices).split(",")] if getattr(args, "devices", None) else None
-    from . import distributed as _dist
-    _rank, local_rank, launch_world = _dist.env_rank_world()   # torchrun / mpirun / srun alike (one place decides: distributed.py)
+    _rank, local_rank, launch_world = distributed.env_rank_world()   # torchrun / mpirun / srun alike (one place decides: distributed.py)
     L, R, k = args.conserved_left, args.conserved_right, args.amplicon
     if devices and len(devices) > 1 and launch_world == 1:
         # one process, a thread per device
