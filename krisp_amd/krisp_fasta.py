@@ -20,6 +20,7 @@ import math
 import os
 import sys
 import time
+from collections import namedtuple
 from typing import NamedTuple
 
 import numpy as np
@@ -83,10 +84,8 @@ def _mixed_prefix_filter(eng, L, R):
     cands = eng.cands()
     if not len(cands):
         return 0
-    lr = L + R
-    top = np.uint64((~0 << (64 - 2 * lr)) & 0xFFFFFFFFFFFFFFFF) if lr < 32 else np.uint64(0xFFFFFFFFFFFFFFFF)
     p = cands["prefix"]
-    threes = (p >> np.uint64(1)) & p & np.uint64(0x5555555555555555) & top
+    threes = (p >> np.uint64(1)) & p & np.uint64(0x5555555555555555) & codec.prefix_mask(L, R)
     keep = threes == 0
     if not keep.all():
         cands = cands[keep]
@@ -131,52 +130,35 @@ for _a, _b in zip(b"ACGT", b"TGCA"):
     _COMP_U8[_a] = _b
 
 
+def _hit_windows(sel, text, k):
+    """member windows of kr_wide_run hits of ONE genome as an (n, k) byte matrix: cut from the text
+    the host holds, soft-mask mapped, reverse complemented for strand 1"""
+    t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    W = t[sel["pos"].astype(np.int64)[:, None] + np.arange(k, dtype=np.int64)] & np.uint8(0xDF)
+    rc = sel["strand"] == 1
+    W[rc] = _COMP_U8[W[rc][:, ::-1]]
+    return W
+
+
 def _groups_from_hits(hits, texts, labels, L, D, R, rna_genomes=None):
-    """kr_wide_run hits (group, genome, position, strand) -> groups of amplicon.Amplicon in the
-    reference's order: groups by (left,right), sequences by diag; the window text is cut from
-    the genome the host already holds (soft-mask mapped, kstream.py:622-642; reverse
-    complemented for strand 1, kstream.py:644-659)."""
+    """kr_wide_run hits (group, genome, position, strand) -> groups of amplicon.Amplicon in the reference's order: groups
+    by (left,right), sequences by diag; the window text is cut from the genome the host already holds (_hit_windows:
+    soft-mask mapped, kstream.py:622-642; reverse complemented for strand 1, kstream.py:644-659)."""
     if len(hits) == 0:
         return []
-    k = L + D + R
-    ar = np.arange(k, dtype=np.int64)
-    rows = []
+    windows, genomes = [], []
     for gi, text in enumerate(texts):
         sel = hits[hits["genome"] == gi]
         if len(sel) == 0:
             continue
-        t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
-        W = t[sel["pos"].astype(np.int64)[:, None] + ar] & np.uint8(0xDF)
-        rc = sel["strand"] == 1
-        W[rc] = _COMP_U8[W[rc][:, ::-1]]
+        W = _hit_windows(sel, text, L + D + R)
         if rna_genomes is not None and rna_genomes[gi]:
             W[W == ord("T")] = ord("U")                 # (an RNA genome's k-mers are written with U: kstream.py:599)
-        # rows order as the reference's merged file does: (left, right) groups, sequences by diag inside
-        # (the device's group numbers need not ascend with (left, right): KR_OPT_WIDE_ORDERED)
-        row = np.empty((len(sel), k + 4), dtype=np.uint8)
-        row[:, 0:L] = W[:, :L]
-        row[:, L:L + R] = W[:, L + D:]
-        row[:, L + R:k] = W[:, L:L + D]
-        row[:, k:] = np.full(len(sel), gi, dtype=">u4").view(np.uint8).reshape(-1, 4)
-        rows.append(row)
-    uniq, counts = np.unique(np.concatenate(rows), axis=0, return_counts=True)
-    groups, last_cand, last_seq = [], None, None
-    for row, cnt in zip(uniq, counts):
-        cand = bytes(row[0:L + R])
-        seq = bytes(row[0:k])
-        gi = int.from_bytes(bytes(row[k:]), "big")
-        if cand != last_cand:
-            groups.append([])
-            last_cand, last_seq = cand, None
-        if seq != last_seq:
-            txt = seq.decode("ascii")
-            groups[-1].append(amplicon.Amplicon(txt[:L], txt[L + R:], txt[L:L + R], []))
-            last_seq = seq
-        groups[-1][-1].labels.extend([labels[gi]] * int(cnt))
-    for g in groups:
-        for a in g:
-            a.labels.sort()
-    return groups
+        windows.append(W)
+        genomes.append(np.full(len(sel), gi, dtype=np.uint32))
+    # (ordered as the reference's merged file is, not by the device's group numbers, which need not ascend with
+    # (left, right): KR_OPT_WIDE_ORDERED)
+    return amplicon.groups_from_windows(np.concatenate(windows), np.concatenate(genomes), labels, L, D, R)
 
 
 # ----------------------------------------------------------------------------
@@ -207,12 +189,10 @@ def _touched_prefix_cands(specials):
 
 
 def _special_groups(eng, ids, labels, specials, geo, ingroup, do_filter, rna_genomes=None):
-    """The reference keeps k-mers with IUPAC letters (kstream.py:11-18); the device cannot pack
-    them, so they arrive here as strings: specials[g] = [(left, diag, right), ...] of genome g.
-    Every (left,right) group they touch is rebuilt exactly: its ACGT members are looked up on
-    the device (kr_cands_load + kr_collect), the IUPAC members added, then the reference's
-    rules applied -- present in every genome (intersectAmplicons.py:232-310), ingroup-unique
-    column (Amplicon.py:495-521).  Rare by nature; everything else stays on the device.
+    """The reference keeps k-mers with IUPAC letters (kstream.py:11-18); the device cannot pack them, so they arrive here
+    as strings: specials[g] = [(left, diag, right), ...] of genome g.  Every (left,right) group they touch is rebuilt
+    exactly: its ACGT members are looked up on the device (kr_cands_load + kr_collect), the IUPAC members added, then the
+    reference's rules applied (_touched_groups).  Rare by nature; everything else stays on the device.
     Returns (set of touched (left,right), list of surviving groups)."""
     touched, cands = _touched_prefix_cands(specials)
     if not touched:
@@ -229,43 +209,14 @@ def _special_groups_from(recs, ids, labels, specials, geo, ingroup, do_filter, r
     gathered from every rank of a multi-GPU run) and the IUPAC members themselves (specials[g] of genome ids[g]).
     rna_genomes (a run that mixes DNA and RNA genomes): the text of an RNA genome's members carries U -- the reference
     compares text, so a group is a (left,right) pair every genome holds letter for letter"""
-    L, D, R = geo
     members = {}            # (left,right) -> {(left,diag,right) -> {genome index -> count}}
-
-    def text_of(gi, l, d, r):
-        if rna_genomes is not None and rna_genomes[gi]:
-            return l.replace("T", "U"), d.replace("T", "U"), r.replace("T", "U")
-        return l, d, r
-    if recs is not None:
-        for rec in recs:
-            gi = ids.index(int(rec["genome"]))
-            l, d, r = text_of(gi, *codec.key_columns(rec["key"], L, D, R))
-            members.setdefault((l, r), {}).setdefault((l, d, r), {})
-            m = members[(l, r)][(l, d, r)]
-            m[gi] = m.get(gi, 0) + int(rec["count"])
-    for gi, sp in enumerate(specials):
-        for (l, d, r) in sp:
-            l, d, r = text_of(gi, l, d, r)
-            m = members.setdefault((l, r), {}).setdefault((l, d, r), {})
-            m[gi] = m.get(gi, 0) + 1
-    groups = []
-    for P in sorted(members):
-        seqs = members[P]
-        present = set()
-        for m in seqs.values():
-            present.update(m)
-        if len(present) != len(ids):
-            continue
-        group = []
-        for seq in sorted(seqs, key=lambda t: t[1]):
-            labs = []
-            for gi, cnt in seqs[seq].items():
-                labs += [labels[gi]] * cnt
-            group.append(amplicon.Amplicon(seq[0], seq[1], seq[2], labs))
-        if do_filter and not amplicon.ingroup_unique_columns(group, ingroup):
-            continue
-        groups.append(group)
-    return groups
+    for rec in (recs if recs is not None else ()):
+        l, d, r = codec.key_columns(rec["key"], *geo)
+        m = members.setdefault((l, r), {}).setdefault((l, d, r), {})
+        gi = ids.index(int(rec["genome"]))
+        m[gi] = m.get(gi, 0) + int(rec["count"])
+    touched = {(l, r) for sp in specials for (l, d, r) in sp}
+    return _touched_groups(members, len(ids), labels, specials, touched, ingroup, do_filter, rna_genomes)
 
 
 def _wide_probe_members(eng, texts, gis, probes, probe_text, geo, pid):
@@ -293,10 +244,11 @@ def _wide_probe_members(eng, texts, gis, probes, probe_text, geo, pid):
     return members
 
 
-def _special_groups_wide_from(members, n, labels, specials, touched, ingroup, do_filter, rna_genomes=None):
-    """the groups IUPAC windows touch, from the ACGT members the device found (_wide_probe_members, of one context or
-    merged over the ranks) and the IUPAC members themselves (specials[g] of genome g), under the reference's rules:
-    present in every genome (intersectAmplicons.py:232-310), an ingroup-unique column (Amplicon.py:495-521)"""
+def _touched_groups(members, n, labels, specials, touched, ingroup, do_filter, rna_genomes=None):
+    """the groups IUPAC windows touch, from the ACGT members the device found (_special_groups_from's records or
+    _wide_probe_members, of one context or merged over the ranks) and the IUPAC members themselves (specials[g] of genome
+    g), under the reference's rules: present in every one of the n genomes (intersectAmplicons.py:232-310), an
+    ingroup-unique column (Amplicon.py:495-521)"""
     for gi, sp in enumerate(specials):
         for (l, d, r) in sp:
             m = members.setdefault((l, r), {}).setdefault((l, d, r), {})
@@ -316,34 +268,23 @@ def _special_groups_wide_from(members, n, labels, specials, touched, ingroup, do
         members = conv
         touched = set(conv)
     groups = []
-    for P in sorted(members):
-        if P not in touched:
-            continue
+    for P in sorted(touched.intersection(members)):
         seqs = members[P]
-        present = set()
-        for m in seqs.values():
-            present.update(m)
-        if len(present) != n:
+        if len(set().union(*seqs.values())) != n:
             continue
-        group = []
-        for seq in sorted(seqs, key=lambda t: t[1]):
-            labs = []
-            for gi, cnt in sorted(seqs[seq].items()):
-                labs += [labels[gi]] * cnt
-            group.append(amplicon.Amplicon(seq[0], seq[1], seq[2], sorted(labs)))
-        if do_filter and not amplicon.ingroup_unique_columns(group, ingroup):
-            continue
-        groups.append(group)
+        group = [amplicon.Amplicon(*seq, [labels[gi] for gi, cnt in seqs[seq].items() for _ in range(cnt)])
+                 for seq in sorted(seqs, key=lambda t: t[1])]
+        if not do_filter or amplicon.ingroup_unique_columns(group, ingroup):
+            groups.append(group)
     return groups
 
 
 def _special_groups_wide(eng, texts, labels, specials, touched, probes, probe_text, geo, ingroup, do_filter, rna_genomes=None):
-    """Wide-path twin of _special_groups.  A touched (left,right) pair with an IUPAC letter in a
-    flank can only hold IUPAC k-mers (the host has them all); a pair with plain flanks also
-    holds ACGT windows, which the device locates (_wide_probe_members)."""
+    """Wide-path twin of _special_groups.  A touched (left,right) pair with an IUPAC letter in a flank can only hold IUPAC
+    k-mers (the host has them all); a pair with plain flanks also holds ACGT windows, which the device locates."""
     n = len(texts)
     members = _wide_probe_members(eng, texts, list(range(n)), probes, probe_text, geo, pid=n)
-    return _special_groups_wide_from(members, n, labels, specials, touched, ingroup, do_filter, rna_genomes)
+    return _touched_groups(members, n, labels, specials, touched, ingroup, do_filter, rna_genomes)
 
 
 def _merge_groups(device_groups, touched, special_groups):
@@ -412,19 +353,17 @@ def _packed_result(records, run, rna, touched, sgroups, stats):
     same: tests/test_host_glue.py)"""
     if run.quirk_all_fail:
         return [], stats
-    Le, De, Re = run.geo
-    if any(rna) and not all(rna):
-        groups = _mixed_finish(records, run.labels, run.geo, rna, run.ingroup_labels, run.do_filter)
-        if touched:
-            groups = _merge_groups(groups, touched, sgroups)
-        stats["candidates"] = len(groups)
-        return groups, stats
     if not touched and not any(rna):
         # (plain records: the renderer works from them directly, the list of groups is built only if someone walks it)
-        return amplicon.RecordGroups(records, run.labels, Le, De, Re), stats
-    groups = amplicon.groups_from_records(records, run.labels, Le, De, Re)
+        return amplicon.RecordGroups(records, run.labels, *run.geo), stats
+    if _mixed(rna):
+        groups = _mixed_finish(records, run.labels, run.geo, rna, run.ingroup_labels, run.do_filter)
+    else:
+        groups = amplicon.groups_from_records(records, run.labels, *run.geo)
     if touched:
         groups = _merge_groups(groups, touched, sgroups)
+    if _mixed(rna):
+        stats["candidates"] = len(groups)
     return (_to_rna(groups) if all(rna) else groups), stats
 
 
@@ -446,25 +385,59 @@ def _mixed_wide_groups(groups, run):
     return groups
 
 
+def _mixed(flags):
+    """some of them and not all: DNA and RNA genomes in one run, ingroup and outgroup genomes in one batch"""
+    return any(flags) and not all(flags)
+
+
+def _say_counts(files, counts, run):
+    if run.verbose:
+        for f, cnt in zip(files, counts):
+            print(f"=> Extracted and sorted {cnt:,} {run.k}-kmers from {f}", file=sys.stderr)
+
+
+def _free_quietly(eng, ids):
+    for g in ids:
+        try:
+            eng.free(g)
+        except _native.KrispHipError:
+            pass
+
+
+def _forced_batch():
+    """KRISP_STREAM_BATCH=n: batches of n genomes whatever the device holds (tests); None when not set"""
+    forced = os.environ.get("KRISP_STREAM_BATCH")
+    return int(forced) if forced else None
+
+
+class _Stages:
+    """a flow's stage_s: stamp(name) books the time since the stamp before it (since `start`, for the first) under name"""
+
+    def __init__(self):
+        self.start = self.last = time.time()
+        self.s = {}
+
+    def stamp(self, name):
+        now = time.time()
+        self.s[name], self.last = now - self.last, now
+
+
 def _find_regions_device_ingest(files, run):
     """find_regions' packed path; a genome set the plan thought would fit and the device then could not hold (the plan
     is an estimate: candidate lists, slices of a skewed genome, another process on the device) is run again in batches"""
     try:
         return _device_ingest_flow(files, run, None)
     except _native.KrispHipError as e:
-        if e.code != _native.ERR_CAPACITY or len(files) < 2 or os.environ.get("KRISP_STREAM_BATCH"):
+        if e.code != _native.ERR_CAPACITY or len(files) < 2 or _forced_batch() is not None:
             raise
         if run.verbose:
             print(f"=> the genome set does not fit the device at once ({e}): in batches", file=sys.stderr)
     return _device_ingest_flow(files, run, (len(files) + 1) // 2)
 
 
-def _device_ingest_flow(files, run, force_batch):
-    """find_regions' packed path with the reader on the device: the host threads read and inflate, the main thread
-    hands each text to the GPU (parse -> sort) as it arrives (the device reader equals kr_fasta_to_bases byte for byte:
-    tests/test_gpu_kernels.py)."""
-    from concurrent.futures import ThreadPoolExecutor
-    Le, De, Re = run.geo
+def _ingest_plan(files, run):
+    """what the files' sizes say before one is read (no device involved) -> (est: the longest text in bytes, from above,
+    0 if a file cannot be asked; whether the context's memory is reserved ahead of the texts; reader threads)"""
     try:
         est = max(fasta.estimate_text_bytes(f) for f in files)
     except OSError:
@@ -473,99 +446,112 @@ def _device_ingest_flow(files, run, force_batch):
     # files whose inflate takes every host thread by itself (one large gzip member, a bz2 stream of many blocks) are read
     # one after the other: the first genome is parsed and sorted on the device while the second still inflates
     # (plain text files use no inflate threads: they keep their readers side by side -- ADVICE r4)
-    workers = run.workers
-    if ahead and est >= int(os.environ.get("KRISP_STREAM_MIN", STREAM_MIN)) and \
-            any(str(f).lower().endswith((".gz", ".bz2", ".bgz")) for f in files):
-        workers = 1
+    alone = ahead and est >= int(os.environ.get("KRISP_STREAM_MIN", STREAM_MIN)) and \
+        any(str(f).lower().endswith((".gz", ".bz2", ".bgz")) for f in files)
+    return est, ahead, 1 if alone else run.workers
+
+
+def _reserve_ahead(eng, nfiles, est, run):
+    """large genomes: the context gets its memory (device memory another process has just given back takes the driver
+    15-40 ms per GB to hand over: seconds at 3 Gbp) while the host threads read and inflate -- planned from the files'
+    sizes, planned again by _texts_to_device if they said too little.  -> planned bases per genome, 0: not taken"""
+    # kr_reserve is an optimisation (include/krisp_hip.h), and the plan is an ESTIMATE from the files' sizes (5 x
+    # the compressed bytes where real sequence text is 3.3-4.5 x): a reservation that does not fit says nothing
+    # about the run itself -- the reserved buffers go back and the unplanned route sizes the context from the
+    # texts once they are read (ADVICE r4)
+    try:
+        eng.set_params(*run.geo, omit_soft=run.omit_soft, max_bases=est)
+        eng.reserve(list(range(nfiles)), est, with_text=True)
+    except _native.KrispHipError as e:
+        if run.verbose:
+            print(f"=> memory plan for {est:,} bases per genome not taken ({e}): sizing from the texts instead", file=sys.stderr)
+        _free_quietly(eng, range(nfiles))
+        return 0
+    return est
+
+
+def _texts_to_device(eng, futures, files, planned, run):
+    """every file's text -> its genome on the device, parsed and sorted (_ingest_genome).  While the plan stands
+    (`planned` bases per genome reserved, no text longer than that so far) a genome goes as its text arrives, the files
+    behind it still being read; the first text longer than the plan -- or no plan -- makes the texts wait for all sizes,
+    and everything goes under max(len).  Each future is dropped as its result is taken (a Future keeps its result): a
+    text handed over is unreferenced from then on.  -> (RNA per genome, IUPAC windows per genome, read_s, _Stages begun
+    when the first text arrived and stamped to where the waiting texts are freed)"""
+    got, waiting, stages = [], [], None
+    for i in range(len(files)):
+        text, universal = futures[i].result()
+        futures[i] = None
+        if stages is None:
+            read_s = time.time() - run.t0       # (until the first text is there: from then on the device has work)
+            stages = _Stages()
+        if planned and len(text) <= planned and not waiting:
+            got.append(_ingest_genome(eng, i, text, universal, run))
+        else:
+            waiting.append((text, universal))   # (no plan, or a file larger than planned: all sizes first)
+        del text
+    if waiting:
+        if len(waiting) < len(files):
+            # (a later file said too little about itself: everything again under a plan that holds them all -- the
+            # texts already handed over are read once more)
+            waiting = [fasta.read_text(f) for f in files[:len(files) - len(waiting)]] + waiting
+        true_max = max(max(len(t) for t, _ in waiting), 1)
+        for i in (range(len(files)) if planned else ()):
+            eng.free(i)
+        eng.set_params(*run.geo, omit_soft=run.omit_soft, max_bases=true_max)
+        got = [_ingest_genome(eng, i, text, universal, run) for i, (text, universal) in enumerate(waiting)]
+    stages.stamp("texts arrive, parse + sort launches")
+    del waiting
+    stages.stamp("texts freed")
+    return [r for _, r, _ in got], [sp for _, _, sp in got], read_s, stages
+
+
+def _intersect_packed(eng, ids, rna, run):
+    """one n-way intersection of the sorted genomes -- of DNA and RNA genomes in the filter's mode 2 (set before it), less
+    the candidates text tells apart --, and the counts behind it, which resolve the sorts.  -> (candidates, k-mers per genome)"""
+    if _mixed(rna):
+        eng.set_mixed_alphabets(True)
+    ncand = eng.intersect(ids, run.flags, apply_filter=run.do_filter and not run.quirk_all_fail)
+    if _mixed(rna) and ncand:
+        ncand = _mixed_prefix_filter(eng, run.geo[0], run.geo[2])
+    return ncand, [eng.count(i) for i in ids]
+
+
+def _collect_packed(eng, ids, ncand, rna, specials, run):
+    """the candidates' records, then the groups IUPAC windows touch.  -> (records, touched pairs, their groups)"""
+    # (genomes listed by label: kr_collect's (key, position in the call) order is then the renderer's)
+    by_label = sorted(ids, key=lambda i: run.labels[i])
+    records = eng.collect(by_label) if (ncand and not run.quirk_all_fail) else np.empty(0, dtype=_native.RECORD)
+    touched, sgroups = set(), []
+    if any(specials) and not run.quirk_all_fail:
+        touched, sgroups = _special_groups(eng, ids, run.labels, specials, run.geo, run.ingroup_labels, run.do_filter,
+                                           rna_genomes=rna if _mixed(rna) else None)
+    return records, touched, sgroups
+
+
+def _device_ingest_flow(files, run, force_batch):
+    """find_regions' packed path with the reader on the device: the host threads read and inflate, the main thread
+    hands each text to the GPU (parse -> sort) as it arrives (the device reader equals kr_fasta_to_bases byte for byte:
+    tests/test_gpu_kernels.py).  The phases and the device calls they make, in order: DESIGN.md section 1."""
+    from concurrent.futures import ThreadPoolExecutor
+    est, ahead, workers = _ingest_plan(files, run)
+    ids = list(range(len(files)))
     with ThreadPoolExecutor(max_workers=workers) as pool, _engine(run.device) as eng:
         # a genome set the device cannot hold sorted at once goes through it in batches (the streaming flow below)
         batch = force_batch or (_plan_batch(eng, len(files), est) if len(files) > 1 else None)
         if batch is not None:
-            t1 = time.time()
-            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=max(est, 1))
-            records, rna, touched, sgroups, stats = _find_regions_streaming(eng, pool, files, run, batch, max(est, 1))
-            stats["device_s"] = time.time() - t1
-            return _packed_result(records, run, rna, touched, sgroups, stats)
+            return _find_regions_streaming(eng, pool, files, run, batch, max(est, 1))
         futures = [pool.submit(fasta.read_text, f) for f in files]
-        # large genomes: the context gets its memory (device memory another process has just given back takes the driver 15-40 ms per GB to hand over: seconds at 3 Gbp) while the
-        # host threads read and inflate -- planned from the files' sizes, planned again below if they said too little
-        planned = 0
-        if ahead:
-            # kr_reserve is an optimisation (include/krisp_hip.h), and the plan is an ESTIMATE from the files' sizes (5 x
-            # the compressed bytes where real sequence text is 3.3-4.5 x): a reservation that does not fit says nothing
-            # about the run itself -- the reserved buffers go back and the unplanned flow below sizes the context from the
-            # texts once they are read
-            planned = est
-            try:
-                eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=planned)
-                eng.reserve(list(range(len(files))), planned, with_text=True)
-            except _native.KrispHipError as e:
-                if run.verbose:
-                    print(f"=> memory plan for {planned:,} bases per genome not taken ({e}): sizing from the texts instead", file=sys.stderr)
-                for i in range(len(files)):
-                    try:
-                        eng.free(i)
-                    except _native.KrispHipError:
-                        pass
-                planned = 0
-        rna, specials = [], []
-        first, t1 = [], None
-        for i, fu in enumerate(futures):
-            text, universal = fu.result()
-            if t1 is None:
-                read_s = time.time() - run.t0       # (until the first text is there: from then on the device has work)
-                t1 = time.time()
-            if planned and len(text) <= planned and not first:
-                # the plan stands: this genome goes to the device now, the files behind it are still being read
-                _n, r, sp = _ingest_genome(eng, i, text, universal, run)
-                rna.append(r)
-                specials.append(sp)
-                del text
-            else:
-                first.append((text, universal))     # (no plan, or a file larger than planned: all sizes first)
-        if first:
-            done = len(files) - len(first)
-            if done:
-                # (a later file said too little about itself: everything again under a plan that holds them all -- the
-                # texts already handed over are read once more)
-                first = [fasta.read_text(f) for f in files[:done]] + first
-                rna, specials = [], []
-            true_max = max(max(len(t) for t, _ in first), 1)
-            for i in (range(len(files)) if planned else ()):
-                eng.free(i)
-            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=true_max)
-            for i, (text, universal) in enumerate(first):
-                _n, r, sp = _ingest_genome(eng, i, text, universal, run)
-                rna.append(r)
-                specials.append(sp)
-        t2 = time.time()
-        del first
-        t3 = time.time()
-        mixed = any(rna) and not all(rna)
-        if mixed:
-            eng.set_mixed_alphabets(True)
-        ids = list(range(len(files)))
-        ncand = eng.intersect(ids, run.flags, apply_filter=run.do_filter and not run.quirk_all_fail)
-        if mixed and ncand:
-            ncand = _mixed_prefix_filter(eng, Le, Re)
-        counts = [eng.count(i) for i in ids]
-        t4 = time.time()
-        if run.verbose:
-            for f, cnt in zip(files, counts):
-                print(f"=> Extracted and sorted {cnt:,} {run.k}-kmers from {f}", file=sys.stderr)
-        # (genomes listed by label: kr_collect's (key, position in the call) order is then the renderer's)
-        by_label = sorted(ids, key=lambda i: run.labels[i])
-        records = eng.collect(by_label) if (ncand and not run.quirk_all_fail) else np.empty(0, dtype=_native.RECORD)
-        touched, sgroups = set(), []
-        if any(specials) and not run.quirk_all_fail:
-            touched, sgroups = _special_groups(eng, ids, run.labels, specials, run.geo, run.ingroup_labels, run.do_filter,
-                                               rna_genomes=rna if mixed else None)
-        t5 = time.time()
+        planned = _reserve_ahead(eng, len(files), est, run) if ahead else 0
+        rna, specials, read_s, stages = _texts_to_device(eng, futures, files, planned, run)
+        ncand, counts = _intersect_packed(eng, ids, rna, run)
+        stages.stamp("sorts + intersect")
+        _say_counts(files, counts, run)
+        records, touched, sgroups = _collect_packed(eng, ids, ncand, rna, specials, run)
+        stages.stamp("collect")
     # (device_s ends where the context is gone: its buffers freed, the reader threads joined)
-    stats = {"read_s": read_s, "device_s": time.time() - t1,
-             "kmers": int(sum(counts)) + sum(len(sp) for sp in specials), "candidates": int(ncand),
-             "stage_s": {"texts arrive, parse + sort launches": t2 - t1, "texts freed": t3 - t2, "sorts + intersect": t4 - t3,
-                         "collect": t5 - t4, "context freed": time.time() - t5}}
+    stages.stamp("context freed")
+    stats = {"read_s": read_s, "device_s": stages.last - stages.start,
+             "kmers": int(sum(counts)) + sum(len(sp) for sp in specials), "candidates": int(ncand), "stage_s": stages.s}
     return _packed_result(records, run, rna, touched, sgroups, stats)
 
 
@@ -580,9 +566,9 @@ def _plan_batch(eng, nfiles, est_bases):
     genome: the bases and two 8-byte keys per base (+ 2 % slack for key-space slices); scratch: codes + pass-1 output
     per sort lane (three at most), the pass-0 array of two genome lanes when the genome is sorted in slices (> 2^28
     bases), the text buffer of the device reader, candidate buffers.  KRISP_STREAM_BATCH=n forces batches of n."""
-    forced = os.environ.get("KRISP_STREAM_BATCH")
-    if forced:
-        return max(1, int(forced)) if int(forced) < nfiles else None
+    forced = _forced_batch()
+    if forced is not None:
+        return max(1, forced) if forced < nfiles else None
     if est_bases <= 0:
         return None
     per_genome = 17.4 * est_bases
@@ -606,7 +592,7 @@ def _first_min(flags, apply_f):
     """the least size of the first batch of genomes with these ingroup flags: it must hold both sides when there are two
     and the filter applies -- with one side only nothing prunes, and its candidate list is every (left,right) pair of its
     genomes (more than 2^32 entries at 3 Gbp -- the library refuses such a list, kr_intersect: KR_ERR_CAPACITY)"""
-    return 2 if (any(flags) and not all(flags) and apply_f) else 1
+    return 2 if (_mixed(flags) and apply_f) else 1
 
 
 def _batches(order, bsz, first_min):
@@ -618,159 +604,243 @@ def _batches(order, bsz, first_min):
         a += m
 
 
+def _intersect_or_probe(eng, running, ids_b, flags, filt):
+    """the batch ids_b against the running candidates (`running` of them, None before the first batch): the first batch
+    is intersected; a later one looks the running candidates up in its genomes -- kr_cands_probe: presence in every
+    genome, their diagnostic bases into the masks, the filter -- instead of being intersected whole: the candidate list
+    of a batch that holds one side only is every prefix of its genomes, 24 bytes each.  -> the number left"""
+    fl = [flags[g] for g in ids_b]
+    if running is None:
+        return eng.intersect(ids_b, fl, apply_filter=filt)
+    return eng.probe_cands(ids_b, fl, apply_filter=filt)
+
+
+class _Stream:
+    """the streaming flow's state: what its passes work from and what they have learnt so far"""
+
+    def __init__(self, eng, pool, files, run, batch, max_bases):
+        n = len(files)
+        self.eng, self.pool, self.files, self.run = eng, pool, files, run
+        self.max_bases = max_bases      # what the context is sized for: raised when a text is longer than its file said
+        self.order = _interleave([i for i in range(n) if run.flags[i]], [i for i in range(n) if not run.flags[i]])
+        self.apply_f = run.do_filter and not run.quirk_all_fail
+        self.first_min = _first_min(run.flags, self.apply_f)
+        self.rank_of = {g: r for r, g in enumerate(sorted(range(n), key=lambda i: run.labels[i]))}
+        self.rna, self.specials, self.counts = [None] * n, [None] * n, [0] * n     # per genome (pass 1 fills them)
+        self.read_s = None              # until the first batch's texts were there
+        # number of running candidates; the list itself stays on the device between the batches of pass 1 (kr_genome_free
+        self.running = None             # does not touch it: no copy to the host and back per batch -- ADVICE r5)
+        self.eager = True               # the running set is small enough to collect every batch's records of it at once
+        self.kept = []                  # those records (pass 1), or the final candidates' (pass 2): a part per batch
+        # after pass 1: the candidates it leaves, _touched_prefix_cands of the IUPAC windows
+        self.final, self.touched, self.tc = None, set(), None
+        self.srecs = []                 # pass 2: the records of `tc`, a part per batch
+        self.stats = {"streamed": True, "batch": batch, "passes": 1, "batches": 0}
+
+
+def _stream_load(st, ids_b, futs, first_pass):
+    """texts -> device, sorted; a batch that does not fit after all is given back whole (KrispHipError, code capacity)"""
+    eng, run, done = st.eng, st.run, []
+    texts = {g: futs[g].result() for g in ids_b}
+    if st.read_s is None:
+        st.read_s = time.time() - run.t0
+    biggest = max(len(t) for t, _ in texts.values())
+    if biggest > st.max_bases:
+        # (the plan came from the files' sizes: a text longer than it said -- nothing is resident between batches)
+        st.max_bases = biggest
+        eng.set_params(*run.geo, omit_soft=run.omit_soft, max_bases=biggest)
+    try:
+        for g in ids_b:
+            text, universal = texts.pop(g)
+            done.append(g)          # (before the ingest: a genome that fails half way holds buffers, too -- ADVICE r5)
+            _n, r, sp = _ingest_genome(eng, g, text, universal, run)
+            del text
+            if first_pass:
+                st.rna[g], st.specials[g] = r, sp
+        for g in ids_b:
+            st.counts[g] = eng.count(g)
+    except _native.KrispHipError:
+        _free_quietly(eng, done)
+        raise
+
+
+def _halve_batch(ids_b, first_min, first, e):
+    """a batch the device could not hold (e: the capacity error) -> its two halves; `first`: it is the first batch of
+    the first pass, which keeps first_min genomes (_first_min).  What cannot be halved raises: one genome e itself, a
+    first batch of first_min the error that says why it must stay whole"""
+    if len(ids_b) == 1:
+        raise e
+    if first and len(ids_b) <= first_min:
+        err = _native.KrispHipError(
+            f"the device cannot hold one ingroup and one outgroup genome sorted at once ({e}); the first batch "
+            "needs both sides for the diagnostic filter to prune")
+        err.code = e.code
+        raise err from e
+    half = max((len(ids_b) + 1) // 2, first_min if first else 1)
+    return ids_b[:half], ids_b[half:]
+
+
+def _stream_pass(st, bsz, first_pass, work):
+    """every batch through _stream_load + work(st, ids_b); the next batch's files are read while this one is on the
+    device; a batch the device cannot hold is halved and tried again (the plan is an estimate)"""
+    todo = list(_batches(st.order, bsz, st.first_min))
+    futs = {}
+    while todo:
+        ids_b = todo.pop(0)
+        for g in ids_b + (todo[0] if todo else []):
+            if g not in futs:
+                futs[g] = st.pool.submit(fasta.read_text, st.files[g])
+        try:
+            _stream_load(st, ids_b, futs, first_pass)
+        except _native.KrispHipError as e:
+            if e.code != _native.ERR_CAPACITY:
+                raise
+            halves = _halve_batch(ids_b, st.first_min, first_pass and st.running is None, e)
+            todo = list(halves) + todo
+            for g in ids_b:
+                futs[g] = st.pool.submit(fasta.read_text, st.files[g])
+            st.stats["batch"] = min(st.stats["batch"], len(halves[0]))
+            continue
+        work(st, ids_b)
+        for g in ids_b:
+            st.eng.free(g)
+            del futs[g]
+        st.stats["batches"] += 1
+
+
+def _stream_pass1(st, ids_b):
+    """the batch prunes the running candidates; its records of them are kept while that set is small"""
+    st.running = _intersect_or_probe(st.eng, st.running, ids_b, st.run.flags, st.apply_f)
+    _say_counts([st.files[g] for g in ids_b], [st.counts[g] for g in ids_b], st.run)
+    if st.run.quirk_all_fail or not st.running:
+        return
+    if st.eager and st.running <= STREAM_EAGER_MAX:
+        st.kept.append(st.eng.collect(sorted(ids_b, key=lambda g: st.rank_of[g])))
+    else:
+        st.eager = False
+        st.kept.clear()
+
+
+def _stream_pass2(st, ids_b):
+    """the batch's records of the final candidates (if pass 1 could not keep them) and of the touched pairs"""
+    by = sorted(ids_b, key=lambda g: st.rank_of[g])
+    if len(st.final) and not st.eager:
+        st.eng.load_cands(st.final)
+        st.kept.append(st.eng.collect(by))
+    if len(st.tc):
+        st.eng.load_cands(st.tc)
+        st.srecs.append(st.eng.collect(by))
+
+
+def _stream_assemble(st, mixed):
+    """the end of the flow: the kept records of the final candidates' prefixes in (key, label rank) order -- what one
+    collect in label order gives the in-core flow --, and the touched groups from the second pass's records.
+    -> (records, the touched pairs' groups)"""
+    run, n = st.run, len(st.files)
+    records = np.empty(0, dtype=_native.RECORD)
+    if st.kept and len(st.final):
+        records = np.concatenate(st.kept)
+        records = records[np.isin(records["key"] & codec.prefix_mask(run.geo[0], run.geo[2]), st.final["prefix"])]
+        ranks = np.array([st.rank_of[g] for g in range(n)], dtype=np.int64)[records["genome"]]
+        records = records[np.lexsort((ranks, records["key"]))]
+    sgroups = []
+    if st.touched:
+        recs = np.concatenate(st.srecs) if st.srecs else None
+        sgroups = _special_groups_from(recs, list(range(n)), run.labels, st.specials, run.geo, run.ingroup_labels,
+                                       run.do_filter, rna_genomes=[bool(r) for r in st.rna] if mixed else None)
+    return records, sgroups
+
+
 def _find_regions_streaming(eng, pool, files, run, batch, max_bases):
     """find_regions for a genome set that does not fit the GPU at once (the reference has no such limit: it sorts in
-    external memory, kstream.py:108-119, and merges files pairwise, intersectAmplicons.py:232-310).  The genomes go
-    through the device in batches of `batch`: sort the batch; the first batch is intersected (with the diagnostic filter:
-    the predicate is monotone, so partial masks may prune -- in and out genomes are interleaved so that the first batch
-    holds both), every later batch looks the running candidates up in its genomes (kr_cands_probe: presence, masks OR-ed,
-    filter); collect the batch's records of the running candidates (a superset of the final ones) and free the batch.  The records of
-    the final candidates are what remains of those; only when the running set was too large to collect from (no
-    outgroup, no filter: every conserved pair is a candidate) or IUPAC windows touch groups whose ACGT members must be
-    looked up, a second pass sorts every batch again and collects then.  Same records, same order, same text as the
-    in-core flow (tests/test_gpu_cli.py).  -> (records, RNA per genome, touched (left,right) pairs, their groups, stats)"""
-    Le, De, Re = run.geo
-    labels, flags = run.labels, run.flags
-    n = len(files)
-    order = _interleave([i for i in range(n) if flags[i]], [i for i in range(n) if not flags[i]])
-    apply_f = run.do_filter and not run.quirk_all_fail
-    rank_of = {g: r for r, g in enumerate(sorted(range(n), key=lambda i: labels[i]))}
-    rna, specials, counts = [None] * n, [None] * n, [0] * n
-    pmask = np.uint64((~0 << (64 - 2 * (Le + Re))) & 0xFFFFFFFFFFFFFFFF) if Le + Re < 32 else np.uint64(0xFFFFFFFFFFFFFFFF)
-    stats = {"streamed": True, "batch": batch, "passes": 1, "batches": 0}
-    read_s = None
-    first_min = _first_min(flags, apply_f)
-    running = None          # number of running candidates; the list itself stays on the device between the batches of pass 1
-    eager = True            # (kr_genome_free does not touch it: no copy to the host and back per batch -- ADVICE r5)
-    kept = []
-
-    def load_batch(ids_b, futs, first_pass):
-        """texts -> device, sorted; a batch that does not fit after all is given back whole (KrispHipError, code capacity)"""
-        nonlocal read_s, max_bases
-        done = []
-        texts = {g: futs[g].result() for g in ids_b}
-        if read_s is None:
-            read_s = time.time() - run.t0
-        biggest = max(len(t) for t, _ in texts.values())
-        if biggest > max_bases:
-            # (the plan came from the files' sizes: a text longer than it said -- nothing is resident between batches)
-            max_bases = biggest
-            eng.set_params(Le, De, Re, omit_soft=run.omit_soft, max_bases=biggest)
-        try:
-            for g in ids_b:
-                text, universal = texts.pop(g)
-                done.append(g)          # (before the ingest: a genome that fails half way holds buffers, too -- ADVICE r5)
-                _n, r, sp = _ingest_genome(eng, g, text, universal, run)
-                del text
-                if first_pass:
-                    rna[g] = r
-                    specials[g] = sp
-            for g in ids_b:
-                counts[g] = eng.count(g)
-        except _native.KrispHipError:
-            for g in done:
-                try:
-                    eng.free(g)
-                except _native.KrispHipError:
-                    pass
-            raise
-
-    def run_pass(bsz, first_pass, work):
-        """every batch through load_batch + work(ids_b); the next batch's files are read while this one is on the device;
-        a batch the device cannot hold is halved and tried again (the plan is an estimate)"""
-        todo = list(_batches(order, bsz, first_min))
-        futs = {}
-        while todo:
-            ids_b = todo.pop(0)
-            for g in ids_b + (todo[0] if todo else []):
-                if g not in futs:
-                    futs[g] = pool.submit(fasta.read_text, files[g])
-            try:
-                load_batch(ids_b, futs, first_pass)
-            except _native.KrispHipError as e:
-                if e.code != _native.ERR_CAPACITY or len(ids_b) == 1:
-                    raise
-                if first_pass and running is None and len(ids_b) <= first_min:
-                    err = _native.KrispHipError(
-                        f"the device cannot hold one ingroup and one outgroup genome sorted at once ({e}); the first batch "
-                        "needs both sides for the diagnostic filter to prune")
-                    err.code = e.code
-                    raise err from e
-                half = (len(ids_b) + 1) // 2
-                if first_pass and running is None:
-                    half = max(half, first_min)
-                todo = [ids_b[:half], ids_b[half:]] + todo
-                for g in ids_b:
-                    futs[g] = pool.submit(fasta.read_text, files[g])
-                stats["batch"] = min(stats["batch"], half)
-                continue
-            work(ids_b)
-            for g in ids_b:
-                eng.free(g)
-                del futs[g]
-            stats["batches"] += 1
-
+    external memory, kstream.py:108-119, and merges files pairwise, intersectAmplicons.py:232-310): the genomes go through
+    the device in batches of `batch`.  Pass 1 sorts a batch, prunes the running candidates with it (the filter's predicate
+    is monotone, so partial masks may prune -- in and out genomes are interleaved so that the first batch holds both),
+    keeps the batch's records of them (a superset of the final ones') and frees it.  Only when the running set was too
+    large to collect from (no outgroup, no filter: every conserved pair is a candidate) or IUPAC windows touch groups
+    whose ACGT members must be looked up, pass 2 sorts every batch again and collects then.  Same records, same order, same
+    text as the in-core flow (tests/test_gpu_cli.py); the phases and their device calls: DESIGN.md section 8.  -> (groups, stats)"""
+    t1 = time.time()
+    eng.set_params(*run.geo, omit_soft=run.omit_soft, max_bases=max_bases)
+    st = _Stream(eng, pool, files, run, batch, max_bases)
     # every genome's alphabet before the first batch (fasta.sniff_rna reads the head of a file): a run that mixes DNA and
     # RNA genomes filters in mode 2 from the first batch on (kr_set_mixed_alphabets)
-    kinds = [bool(fasta.sniff_rna(f)) for f in files]
-    mixed = any(kinds) and not all(kinds)
+    mixed = _mixed([bool(fasta.sniff_rna(f)) for f in files])
     if mixed:
         eng.set_mixed_alphabets(True)
+    _stream_pass(st, batch, True, _stream_pass1)
+    if mixed and st.running:
+        st.running = _mixed_prefix_filter(eng, run.geo[0], run.geo[2])
+    st.final = eng.cands().copy() if st.running else np.empty(0, dtype=_native.CAND)
+    st.touched, st.tc = _touched_prefix_cands([] if run.quirk_all_fail else st.specials)
+    if (len(st.final) and not st.eager and not run.quirk_all_fail) or len(st.tc):
+        st.stats["passes"] = 2
+        _stream_pass(st, max(1, st.stats["batch"]), False, _stream_pass2)
+    records, sgroups = _stream_assemble(st, mixed)
+    rna = [bool(r) for r in st.rna]
+    st.stats.update(mixed_rna=rna if mixed else None, read_s=st.read_s or 0.0, candidates=int(len(st.final)),
+                    kmers=int(sum(st.counts)) + sum(len(sp) for sp in st.specials), device_s=time.time() - t1)
+    return _packed_result(records, run, rna, st.touched, sgroups, st.stats)
 
-    def pass1(ids_b):
-        nonlocal running, eager
-        bflags = [flags[g] for g in ids_b]
-        if running is None:
-            running = eng.intersect(ids_b, bflags, apply_filter=apply_f)
-        else:
-            # (a later batch looks the running candidates up in its genomes -- kr_cands_probe: presence in every genome,
-            # their diagnostic bases into the masks, the filter -- instead of being intersected whole: the candidate list
-            # of a batch that holds one side only is every prefix of its genomes, 24 bytes each)
-            running = eng.probe_cands(ids_b, bflags, apply_filter=apply_f)
-        if run.verbose:
-            for g in ids_b:
-                print(f"=> Extracted and sorted {counts[g]:,} {run.k}-kmers from {files[g]}", file=sys.stderr)
-        if run.quirk_all_fail or not running:
-            return
-        if eager and running <= STREAM_EAGER_MAX:
-            kept.append(eng.collect(sorted(ids_b, key=lambda g: rank_of[g])))
-        else:
-            eager = False
-            kept.clear()
 
-    run_pass(batch, True, pass1)
-    if mixed and running:
-        running = _mixed_prefix_filter(eng, Le, Re)
-    final = eng.cands().copy() if running else np.empty(0, dtype=_native.CAND)
-    stats["mixed_rna"] = [bool(r) for r in rna] if mixed else None
-    touched, tc = _touched_prefix_cands([] if run.quirk_all_fail else specials)
-    srecs = []
-    if (len(final) and not eager and not run.quirk_all_fail) or len(tc):
-        stats["passes"] = 2
+# what the host keeps of a wide run's genomes once they are on the device: their bases (None where the device parsed the
+# files); per genome the number of bases, RNA or not, the IUPAC windows as (left, diag, right); _touched_pairs of those
+_WideSetup = namedtuple("_WideSetup", "texts nb rna specials touched probes probe_text")
 
-        def pass2(ids_b):
-            by = sorted(ids_b, key=lambda g: rank_of[g])
-            if len(final) and not eager:
-                eng.load_cands(final)
-                kept.append(eng.collect(by))
-            if len(tc):
-                eng.load_cands(tc)
-                srecs.append(eng.collect(by))
-        run_pass(max(1, stats["batch"]), False, pass2)
-    if kept and len(final):
-        records = np.concatenate(kept)
-        records = records[np.isin(records["key"] & pmask, final["prefix"])]
-        ranks = np.array([rank_of[g] for g in range(n)], dtype=np.int64)[records["genome"]]
-        records = records[np.lexsort((ranks, records["key"]))]
-    else:
-        records = np.empty(0, dtype=_native.RECORD)
-    sgroups = []
+
+def _wide_setup_host(eng, loaded, run):
+    """loaded: fasta.ingest of every file.  The bases are uploaded; the context also holds the probe text.  -> _WideSetup"""
+    texts = [b for b, _, _ in loaded]
+    specials = [[codec.split_window(w, *run.geo) for w in sp] for _, _, sp in loaded]
+    touched, probes, probe_text = _touched_pairs(specials, run.geo[1])
+    eng.set_params_wide(*run.geo, omit_soft=run.omit_soft, max_bases=max(max(len(t) for t in texts), len(probe_text)))
+    for i, t in enumerate(texts):
+        eng.upload(i, t)
+    return _WideSetup(texts, [len(t) for t in texts], [bool(r) for _, r, _ in loaded], specials, touched, probes, probe_text)
+
+
+def _wide_setup_device(eng, loaded, run):
+    """loaded: fasta.read_text of every file, each let go once the device has parsed it (_ingest_genome).
+    -> _WideSetup without texts, or None: the probe text is longer than the context was sized for -- the host parse"""
+    maxb = max(max(len(t) for t, _ in loaded), 64)
+    eng.set_params_wide(*run.geo, omit_soft=run.omit_soft, max_bases=maxb)
+    got = []
+    for i, (text, universal) in enumerate(loaded):
+        got.append(_ingest_genome(eng, i, text, universal, run))
+        loaded[i] = None
+    nb, rna, specials = [n for n, _, _ in got], [bool(r) for _, r, _ in got], [sp for _, _, sp in got]
+    touched, probes, probe_text = _touched_pairs(specials, run.geo[1])
+    return None if len(probe_text) > maxb else _WideSetup(None, nb, rna, specials, touched, probes, probe_text)
+
+
+def _wide_text_groups(hits, texts, run, rna, touched, sgroups):
+    """the groups of a wide run where text decides (one GPU's and rank 0's): a run that mixes DNA and RNA genomes goes
+    through _mixed_wide_groups, the groups IUPAC windows touch are replaced by `sgroups` (rebuilt by the caller from its
+    own look-ups), an all-RNA run is written with U"""
+    mixed = _mixed(rna)
+    groups = _groups_from_hits(hits, texts, run.labels, *run.geo, rna_genomes=rna if mixed else None)
+    if mixed:
+        groups = _mixed_wide_groups(groups, run)
+        touched = touched | {(g[0].left, g[0].right) for g in sgroups}
     if touched:
-        recs = np.concatenate(srecs) if srecs else None
-        sgroups = _special_groups_from(recs, list(range(n)), labels, specials, run.geo, run.ingroup_labels, run.do_filter,
-                                       rna_genomes=[bool(r) for r in rna] if mixed else None)
-    stats.update(read_s=read_s or 0.0, kmers=int(sum(counts)) + sum(len(sp) for sp in specials), candidates=int(len(final)))
-    return records, [bool(r) for r in rna], touched, sgroups, stats
+        groups = _merge_groups(groups, touched, sgroups)
+    return _to_rna(groups) if all(rna) else groups
+
+
+def _wide_result(eng, run, su, nhits, hits, ngroups):
+    """the hits of one GPU's kr_wide_run -> (groups, their number)"""
+    mixed = _mixed(su.rna)
+    if not mixed and not su.touched:
+        # the member windows are cut on the device (kr_wide_fetch_windows) and rendered from their rows in the library
+        # (amplicon.WindowGroups: no object per window; the list of groups only if someone walks it; the RNA letters are its)
+        rows = eng.wide_windows(run.k) if nhits else np.empty((0, run.k), dtype=np.uint8)
+        return amplicon.WindowGroups(rows, hits["cand"], hits["genome"], run.labels, *run.geo, rna=all(su.rna)), ngroups
+    # (the device parsed the files: their bases come back now that text decides)
+    texts = su.texts if su.texts is not None else [eng.fetch_bases(i, n).copy() for i, n in enumerate(su.nb)]
+    sgroups = _special_groups_wide(eng, texts, run.labels, su.specials, su.touched, su.probes, su.probe_text, run.geo, run.ingroup_labels,
+                                   run.do_filter, rna_genomes=su.rna if mixed else None) if su.touched else []
+    groups = _wide_text_groups(hits, texts, run, su.rna, su.touched, sgroups)
+    return groups, (len(groups) if mixed else ngroups)
 
 
 def _find_regions_wide(files, run, host_parse):
@@ -779,86 +849,31 @@ def _find_regions_wide(files, run, host_parse):
     BGZF file), and the host sees a genome's bases again only where it needs them -- IUPAC windows (scan_special), mixed
     DNA / RNA runs, the groups IUPAC windows touch -- through kr_genome_fetch_bases.  host_parse: the files are parsed on
     the host threads (fasta.ingest) and their bases uploaded -- for a run whose groups all fail the filter, and for one
-    whose probe text is longer than its genomes.  -> (groups, stats), or None: the probe text does not fit, take the host
-    parse."""
+    whose probe text is longer than its genomes: without host_parse that one returns None.  -> (groups, stats)"""
     from concurrent.futures import ThreadPoolExecutor
-    Le, De, Re = run.geo
     with ThreadPoolExecutor(max_workers=run.workers) as pool:
-        if host_parse:
-            loaded = list(pool.map(lambda f: fasta.ingest(f, run.k, run.omit_soft), files))
-        else:
-            loaded = list(pool.map(fasta.read_text, files))
+        loaded = list(pool.map((lambda f: fasta.ingest(f, run.k, run.omit_soft)) if host_parse else fasta.read_text, files))
     stats = {"read_s": time.time() - run.t0}
     t1 = time.time()
     if run.quirk_all_fail:
         stats.update(device_s=0.0, kmers=0, candidates=0)
         return [], stats
-    ids = list(range(len(files)))
     with _engine(run.device) as eng:
-        # k-mers holding IUPAC letters (kept by the reference): the (left,right) groups they touch
-        # are rebuilt on the host; those with plain flanks need their ACGT members from every
-        # genome, found on the device through a probe "genome" of the touched flank pairs
-        if host_parse:
-            texts = [b for b, _, _ in loaded]
-            rna = [bool(r) for _, r, _ in loaded]
-            specials = [[codec.split_window(w, Le, De, Re) for w in sp] for _, _, sp in loaded]
-            touched, probes, probe_text = _touched_pairs(specials, De)
-            eng.set_params_wide(Le, De, Re, omit_soft=run.omit_soft,
-                                max_bases=max(max(len(t) for t in texts), len(probe_text)))
-            for i, t in enumerate(texts):
-                eng.upload(i, t)
-        else:
-            texts = None                # (the bases come back from the device when a branch below needs them)
-            maxb = max(max(len(t) for t, _ in loaded), 64)
-            eng.set_params_wide(Le, De, Re, omit_soft=run.omit_soft, max_bases=maxb)
-            nb, rna, specials = [], [], []
-            for i, (text, universal) in enumerate(loaded):
-                n, r, sp = _ingest_genome(eng, i, text, universal, run)
-                nb.append(n)
-                rna.append(bool(r))
-                specials.append(sp)
-                loaded[i] = None
-            touched, probes, probe_text = _touched_pairs(specials, De)
-            if len(probe_text) > maxb:
-                return None
-
-        def host_texts():
-            nonlocal texts
-            if texts is None:
-                texts = [eng.fetch_bases(i, nb[i]).copy() for i in ids]
-            return texts
-        mixed = any(rna) and not all(rna)
-        if mixed:
+        # k-mers holding IUPAC letters (kept by the reference): the (left,right) groups they touch are rebuilt on the host;
+        # those with plain flanks need their ACGT members from every genome, found through a probe "genome" of these pairs
+        su = (_wide_setup_host if host_parse else _wide_setup_device)(eng, loaded, run)
+        if su is None:
+            return None
+        if _mixed(su.rna):
             eng.set_mixed_alphabets(True)
-        nhits = eng.wide_run(ids, run.flags, apply_filter=run.do_filter)
+        nhits = eng.wide_run(list(range(len(files))), run.flags, apply_filter=run.do_filter)
         hits = eng.wide_fetch(_native.WIDE_HITS) if nhits else np.empty(0, dtype=_native.WIDE_HIT)
         ngroups = int(eng.wide_fetch(_native.WIDE_NGROUPS)[0])
         counts = eng.wide_fetch(_native.WIDE_COUNTS).tolist()
         stats["wide_batch"] = int(eng.wide_fetch(_native.WIDE_BATCH_USED)[0])       # (0: every genome sorted at once)
-        if run.verbose:
-            for f, cnt in zip(files, counts):
-                print(f"=> Extracted and sorted {cnt:,} {run.k}-kmers from {f}", file=sys.stderr)
-        if mixed:
-            groups = _mixed_wide_groups(_groups_from_hits(hits, host_texts(), run.labels, Le, De, Re, rna_genomes=rna), run)
-            if touched:
-                sgroups = _special_groups_wide(eng, host_texts(), run.labels, specials, touched, probes, probe_text,
-                                               run.geo, run.ingroup_labels, run.do_filter, rna_genomes=rna)
-                groups = _merge_groups(groups, touched | {(g[0].left, g[0].right) for g in sgroups}, sgroups)
-            ngroups = len(groups)
-        elif touched:
-            groups = _groups_from_hits(hits, host_texts(), run.labels, Le, De, Re)
-            sgroups = _special_groups_wide(eng, host_texts(), run.labels, specials, touched, probes, probe_text,
-                                           run.geo, run.ingroup_labels, run.do_filter)
-            groups = _merge_groups(groups, touched, sgroups)
-            if all(rna):
-                groups = _to_rna(groups)
-        else:
-            # the member windows are cut on the device (kr_wide_fetch_windows) and rendered from their rows in the
-            # library (amplicon.WindowGroups: no object per window; the list of groups only if someone walks it; the RNA
-            # letters are the renderer's)
-            rows = eng.wide_windows(run.k) if nhits else np.empty((0, run.k), dtype=np.uint8)
-            groups = amplicon.WindowGroups(rows, hits["cand"], hits["genome"], run.labels, Le, De, Re, rna=all(rna))
-    stats.update(device_s=time.time() - t1, kmers=int(sum(counts)) + sum(len(sp) for sp in specials), candidates=ngroups)
+        _say_counts(files, counts, run)
+        groups, ngroups = _wide_result(eng, run, su, nhits, hits, ngroups)
+    stats.update(device_s=time.time() - t1, kmers=int(sum(counts)) + sum(len(sp) for sp in su.specials), candidates=ngroups)
     return groups, stats
 
 
@@ -869,10 +884,8 @@ def find_regions(ingroup_files, outgroup_files, L, R, amplicon_len, omit_soft=Fa
                  device=0, verbose=False, keep_merged=False, wide=None):
     """FASTA files -> list of surviving groups (amplicon.Amplicon lists).
 
-    = extractSortedKmers per file + mergeFiles + filterAlignments of the reference
-    (krisp_fasta.py:237-272), on the GPU: one sort per genome, one n-way
-    intersection with the diagnostic filter fused in, one collect.
-    Returns (groups, stats)."""
+    = extractSortedKmers per file + mergeFiles + filterAlignments of the reference (krisp_fasta.py:237-272), on the GPU:
+    one sort per genome, one n-way intersection with the diagnostic filter fused in, one collect.  Returns (groups, stats)."""
     files = list(ingroup_files) + list(outgroup_files)
     # mergeFiles moves the lone k-mer file; its lines carry no label, so later stages
     # label them with the file they read: simplename('merged_file.txt') (shared.py:373)
@@ -1028,16 +1041,14 @@ def _rank_wide(rk, stats):
     texts = {g: bases for g, (bases, _, _) in zip(rk.mine, rk.loaded)}
     for g in sorted(set(hits["genome"].tolist()) - set(texts)):
         texts[g] = fasta.ingest(rk.order[g], run.k, run.omit_soft)[0]
-    wg = _groups_from_hits(hits, [texts.get(g) for g in range(len(rk.order))], run.labels, *run.geo, rna_genomes=rk.rna_all)
+    # (a mixed run holds no IUPAC windows: MixedAlphabet in _rank_read_and_agree)
+    sg = _touched_groups(members, len(rk.order), run.labels, rk.specials_all, touched, run.ingroup_labels,
+                         run.do_filter) if rk.specials_all is not None else []
+    wg = _wide_text_groups(hits, [texts.get(g) for g in range(len(rk.order))], run,
+                           rk.rna_all if rk.mixed else [rk.all_rna] * len(rk.order), touched, sg)
     if rk.mixed:
-        wg = _mixed_wide_groups(wg, run)
         stats["candidates"] = len(wg)
-        return wg, stats
-    if rk.specials_all is not None:
-        sg = _special_groups_wide_from(members, len(rk.order), run.labels, rk.specials_all, touched, run.ingroup_labels,
-                                       run.do_filter)
-        wg = _merge_groups(wg, touched, sg)
-    return (_to_rna(wg) if rk.all_rna else wg), stats
+    return wg, stats
 
 
 def _shard_batches(rk, bsz):
@@ -1065,9 +1076,7 @@ def _shard_intersect(rk, filt):
     bsz = _plan_batch(eng, len(rk.mine), rk.max_bases) if len(rk.mine) > 1 else None
     total, running = 0, None
     for ids_b in _shard_batches(rk, bsz):
-        fl = [run.flags[g] for g in ids_b]
-        running = eng.intersect(ids_b, fl, apply_filter=filt) if running is None else \
-            eng.probe_cands(ids_b, fl, apply_filter=filt)
+        running = _intersect_or_probe(eng, running, ids_b, run.flags, filt)
         total += sum(eng.count(g) for g in ids_b)
     return bsz, total
 
@@ -1221,16 +1230,6 @@ def find_regions_multi_device(ingroup_files, outgroup_files, L, R, amplicon_len,
 # ----------------------------------------------------------------------------
 # stage functions (reference signatures)
 # ----------------------------------------------------------------------------
-def _hit_windows(sel, text, k):
-    """member windows of kr_wide_run hits of ONE genome as an (n, k) byte matrix: cut from the text
-    the host holds, soft-mask mapped, reverse complemented for strand 1"""
-    t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
-    W = t[sel["pos"].astype(np.int64)[:, None] + np.arange(k, dtype=np.int64)] & np.uint8(0xDF)
-    rc = sel["strand"] == 1
-    W[rc] = _COMP_U8[W[rc][:, ::-1]]
-    return W
-
-
 def _extract_sorted_wide(fasta_file, L, R, k, output, omit, device, verbose):
     """extractSortedKmers for amplicons longer than one key (krisp_fasta.py:16-66 takes any k):
     the genome alone through kr_wide_run without a filter -- every window then belongs to a
@@ -1438,7 +1437,7 @@ def _merge_files_wide(contents, labels, L, D, R, device):
         t = b"\n".join(rec)
         texts.append(np.frombuffer(t.replace(b"U", b"T") if rna else t, dtype=np.uint8))
     ids = list(range(len(texts)))
-    mixed = any(rnas) and not all(rnas)
+    mixed = _mixed(rnas)
     touched, probes, probe_text = _touched_pairs(specials, D)
     with _native.Engine(device=device) as eng:
         eng.set_params_wide(L, D, R, omit_soft=False, max_bases=max(1, max(len(t) for t in texts), len(probe_text)))
