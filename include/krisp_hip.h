@@ -850,6 +850,9 @@ enum { KR_OPT_SLICE_BASES = 1,       /* -1 automatic; 0..4: sort every genome in
                                         key's high word, L >= 5 and R < L allow it, kr_genome_partition writes the forward record of every
                                         window only and kr_intersect asks each key both ways (the same candidates, records and counts);
                                         0: both strands are partitioned */
+       KR_OPT_COARSE_ONE_PASS = 15,  /* 1 (default; KR_COARSE_ONE_PASS in the environment): the probe of one-strand genomes streams a bucket
+                                        past the forward AND the reverse candidates of its digit in one pass, each key tested once for
+                                        both readings; 0: one reading after the other (the same kernel, the same results) */
        KR_OPT_WIDE_ORDERED = 6 };    /* wide path: 0 (default) flanks of >= 20 bases are numbered through minimizer buckets (look-ups
                                         of neighbouring windows share memory sectors): the same groups and hits, but `cand` no longer
                                         ascends with (left, right); 1: order-preserving ranks, groups in the reference's order */
@@ -917,7 +920,8 @@ int     kr_debug_place(kr_ctx*, double* out8);
  * buffers held, [7] the option's value */
 int     kr_debug_coarse_pool(kr_ctx*, double* out8);
 /* KR_OPT_COARSE_ONE_STRAND's counters: out8[0] partitions that wrote one strand, [1] intersections that probed one-strand genomes,
- * [2] / [3] the forward / reverse rounds of all of them, [4] / [5] of the latest, [6] the option's value, [7] 0 */
+ * [2] / [3] the forward / reverse rounds of all of them, [4] / [5] of the latest, [6] the option's value, [7] the passes of the
+ * latest call (KR_OPT_COARSE_ONE_PASS: a pass holds a forward and a reverse round) */
 int     kr_debug_coarse_strand(kr_ctx*, int64_t* out8);
 /* what the multi-GPU exchange has cost this context so far: out[0] host synchronisations, [1] point-to-point calls,
  * [2] collectives, [3] microseconds inside kr_cands_reduce / kr_cands_bcast, [4] kr_cands_reduce calls, [5] entries of the

@@ -58,6 +58,7 @@ OPT_COARSE_REST = 11
 OPT_COARSE_POOL = 12
 OPT_JOIN2 = 13
 OPT_COARSE_ONE_STRAND = 14
+OPT_COARSE_ONE_PASS = 15
 ERR_KEY, ERR_HOST = -5, -6
 STRANDS_BOTH, STRANDS_FORWARD, STRANDS_CANONICAL = 0, 1, 2
 STAGES = ["pack", "hist8", "reduce8", "scatter1", "hist2", "scan2", "scatter2", "chunks", "localsort",
@@ -1194,11 +1195,12 @@ class Engine:
 
     def debug_coarse_strand(self):
         """KR_OPT_COARSE_ONE_STRAND's counters (kr_debug_coarse_strand): partitions that wrote one strand, intersections that
-        probed such genomes, their forward / reverse rounds in all and of the latest call, the option's value"""
+        probed such genomes, their forward / reverse rounds in all and of the latest call, the option's value, the passes of the
+        latest call (KR_OPT_COARSE_ONE_PASS)"""
         o = np.zeros(8, dtype=np.int64)
         self._check(self.lib.kr_debug_coarse_strand(self.ctx, _ptr(o)), "kr_debug_coarse_strand")
         return dict(partitions=int(o[0]), calls=int(o[1]), rounds_forward=int(o[2]), rounds_reverse=int(o[3]),
-                    last_forward=int(o[4]), last_reverse=int(o[5]), on=int(o[6]))
+                    last_forward=int(o[4]), last_reverse=int(o[5]), on=int(o[6]), last_passes=int(o[7]))
 
     def debug_coarse_pool(self):
         """the pool of placed pass-1 targets of coarse genomes (kr_debug_coarse_pool)"""

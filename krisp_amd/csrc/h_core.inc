@@ -155,6 +155,9 @@ struct kr_ctx {
     int64_t coarse_done = 0, coarse_promoted = 0;   // genomes kr_intersect took in the coarse state; coarse genomes sorted fine after all
     int coarse_one = 1;         // KR_OPT_COARSE_ONE_STRAND / KR_COARSE_ONE_STRAND env: 1 = a coarse partition writes one strand where one_strand_form() holds
     int64_t one_partitions = 0, one_calls = 0, one_rounds[2] = {0, 0}, one_last[2] = {0, 0};   // ... its counters (kr_debug_coarse_strand)
+    int coarse_pass = 1;        // KR_OPT_COARSE_ONE_PASS / KR_COARSE_ONE_PASS env: 1 = a pass of the one-strand probe holds a forward AND a
+                                // reverse round of its digit (co_pass.inc); 0 = one round after the other
+    int64_t one_last_passes = 0;    // ... the passes of the latest call
     DevBuf co_ent;              // ... the candidates' entries by class, behind them the class counts, bounds and cursors (k_strand_*)
     int coarse_pool = 1;        // KR_OPT_COARSE_POOL / KR_COARSE_POOL env: 1 = coarse genomes that are partitioned again and again write
                                 // their pass 1 into placed buffers (coarse_pool_grow); 0 = always into their own key arrays
@@ -733,6 +736,8 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         c->coarse_pool = e21 ? atoi(e21) != 0 : 1;
         const char* e26 = getenv("KR_COARSE_ONE_STRAND");
         c->coarse_one = e26 ? atoi(e26) != 0 : 1;
+        const char* e27 = getenv("KR_COARSE_ONE_PASS");
+        c->coarse_pass = e27 ? atoi(e27) != 0 : 1;
         const char* e22 = getenv("KR_PLACE_MIN_BYTES");
         if (e22) c->place_min_bytes = (size_t)std::max(0ll, atoll(e22));
         const char* e18 = getenv("KR_COARSE_TCAP");
@@ -980,6 +985,10 @@ int kr_set_option(kr_ctx* c, int option, int64_t value) {
     case KR_OPT_COARSE_ONE_STRAND:
         if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_COARSE_ONE_STRAND: 0 or 1");
         c->coarse_one = (int)value;
+        return KR_OK;
+    case KR_OPT_COARSE_ONE_PASS:
+        if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_COARSE_ONE_PASS: 0 or 1");
+        c->coarse_pass = (int)value;
         return KR_OK;
     case KR_OPT_JOIN2:
         if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_JOIN2: 0 or 1");

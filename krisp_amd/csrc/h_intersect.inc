@@ -159,15 +159,16 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
             HIPCHK(c, hipMemsetAsync(cnt, 0, CS_CLS * 4, st));
             hipLaunchKernelGGL(k_strand_count, dim3(cgrid), dim3(CS_T), 0, st, (const kr_cand*)c->candB.p, nC, S, cnt);
             hipLaunchKernelGGL(k_strand_tables, dim3(1), dim3(CS_CLS), 0, st, (const u32*)cnt, ca, c->co_tcap, cls, cursor, ust, rows,
-                               c->mbox + 56);
+                               c->mbox + 56, (u32)c->coarse_pass);
             hipLaunchKernelGGL(k_strand_fill, dim3(cgrid), dim3(CS_T), 0, st, (const kr_cand*)c->candB.p, nC, S, cursor, ents);
             hipLaunchKernelGGL(k_coarse_probe<1>, dim3(grid), dim3(CO_T), 0, st, ca, (const u32*)cls, (const u32*)ust, (const u32*)rows,
-                               (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel, (const CoEnt*)ents, S);
+                               (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel, (const CoEnt*)ents, S,
+                               (u32)c->coarse_pass);
         } else {
             hipLaunchKernelGGL(k_coarse_tables, dim3(1), dim3(256), 0, st, (const kr_cand*)c->candB.p, nC, ca, c->co_tcap, cb, ust, rows);
             hipLaunchKernelGGL(k_coarse_probe<0>, dim3(grid), dim3(CO_T), 0, st, ca, (const u32*)cb, (const u32*)ust, (const u32*)rows,
                                (const kr_cand*)c->candB.p, (u32*)c->co_state.p, c->co_tcap, g.pmask, g.LRrel, (const CoEnt*)nullptr,
-                               CoStrand{});
+                               CoStrand{}, 0u);
         }
     }
     for (Genome* G : cg)
@@ -188,6 +189,7 @@ static int64_t intersect_coarse(kr_ctx* c, const int* ids, int n, const uint8_t*
             c->one_last[q] = ((volatile u32*)c->mbox)[56 + q];
             c->one_rounds[q] += c->one_last[q];
         }
+        c->one_last_passes = ((volatile u32*)c->mbox)[58];
     }
     for (size_t j = 0; j < cg.size(); j++)
         if (((volatile u32*)c->mbox)[32 + j] > hitcap) {

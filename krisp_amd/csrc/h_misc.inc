@@ -290,7 +290,8 @@ int kr_debug_coarse_pool(kr_ctx* c, double* out8) {
 }
 
 // KR_OPT_COARSE_ONE_STRAND (h_core.inc: one_strand_form; k_coarse.inc): out[0] partitions that wrote one strand, [1] intersections
-// that probed one-strand genomes, [2] / [3] the forward / reverse rounds of all of them, [4] / [5] of the latest, [6] the option
+// that probed one-strand genomes, [2] / [3] the forward / reverse rounds of all of them, [4] / [5] of the latest, [6] the option,
+// [7] the passes of the latest call (KR_OPT_COARSE_ONE_PASS, co_pass.inc)
 int kr_debug_coarse_strand(kr_ctx* c, int64_t* o) {
     if (!c || !o) return KR_ERR_PARAM;
     o[0] = c->one_partitions;
@@ -300,7 +301,7 @@ int kr_debug_coarse_strand(kr_ctx* c, int64_t* o) {
     o[4] = c->one_last[0];
     o[5] = c->one_last[1];
     o[6] = c->coarse_one;
-    o[7] = 0;
+    o[7] = c->one_last_passes;
     return KR_OK;
 }
 

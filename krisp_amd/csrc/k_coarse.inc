@@ -8,11 +8,11 @@
 // kr_collect will ask of this genome.  Exact: a slot's 19-bit tag only gates the look at the candidate's full prefix.
 
 #include "co_units.inc"        // CO_CHUNK, the numbering of the work units and its decode (shared with a host check)
+#include "co_pass.inc"         // co_hash, CO_BM_LOG and the prefilter's bits, the 16-bit slots and the passes of the one-strand form
 
 #define CO_T 1024               // threads of k_coarse_probe: two workgroups per CU (8 waves per SIMD, <= 64 VGPRs, 2 x 75 KB LDS)
 #define CO_SLOT_LOG 13
 #define CO_SLOTS (1u << CO_SLOT_LOG)    // LDS slots: idx << 19 | tag, CO_EMPTY = free
-#define CO_BM_LOG 17            // bits of the prefilter in front of the table: 2^17
 #define CO_QCAP 2048            // keys of one unit that passed the prefilter (more: the unit is looked up in place)
 #define CO_TCAP 6144            // candidates one table takes (three quarters of the slots; idx << 19 | tag never equals CO_EMPTY);
                                 // a top byte with more of them is streamed once per CO_TCAP candidates ("rounds")
@@ -36,10 +36,7 @@ struct CoarseArgs {
 
 // state word of a candidate: bits 0..3 the bases its column shows in coarse ingroup genomes, 4..7 in coarse outgroup
 // genomes, bit 8 + j: coarse genome j holds the prefix
-__device__ __forceinline__ u32 co_hash(u64 pre) {
-    const u32 y = (u32)pre * 0x9E3779B1u;
-    return ((u32)(pre >> 32) ^ y) * 0x85EBCA6Bu;
-}
+// (co_hash: co_pass.inc)
 
 // cb[t] = first candidate whose prefix has a top byte >= t (t = 0 .. 256); rows[t] = the buckets of top byte t in every
 // genome; ust[t] = units in front of top byte t (co_units.inc).  Also clears the genomes' hit counts.
@@ -120,12 +117,12 @@ __global__ __launch_bounds__(CS_T) void k_strand_count(const kr_cand* __restrict
 }
 
 // cls[t] = entries in front of class t (cls[CS_CLS] = 2 n), cursor[] = the same, for k_strand_fill; rows[d] = the buckets of
-// digit d in every genome; ust[d] = units in front of digit d: co_byte_units over (forward rounds + reverse rounds) * tcap
-// candidates -- a decoded round below the forward rounds is a forward round.  Also clears the genomes' hit counts.
-__device__ __forceinline__ u32 co_rounds(u32 nc, u32 tcap) { return nc / tcap + (nc % tcap ? 1u : 0u); }
+// digit d in every genome; ust[d] = units in front of digit d: co_byte_units over passes * tcap candidates -- what
+// co_units.inc decodes as a unit's round is its PASS (co_pass.inc: forward round p beside reverse round p, or with
+// one_pass = 0 one round after the other).  Also clears the genomes' hit counts.
 __global__ __launch_bounds__(CS_CLS) void k_strand_tables(const u32* __restrict__ cnt, CoarseArgs A, u32 tcap, u32* __restrict__ cls,
                                                           u32* __restrict__ cursor, u32* __restrict__ ust, u32* rows,
-                                                          u32* __restrict__ host_rounds) {
+                                                          u32* __restrict__ host_rounds, u32 one_pass) {
     __shared__ u32 waves[17];
     const u32 t = threadIdx.x;
     u32 total;
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(CS_CLS) void k_strand_tables(const u32* __restrict_
     cursor[t] = ex;
     if (t == 0) cls[CS_CLS] = total;
     if (t < 4 * A.n) A.hits[t >> 2][t & 3u] = 0;
-    u32 units = 0, rf = 0, rr = 0;
+    u32 units = 0, rf = 0, rr = 0, np = 0;
     if (t < 256) {
         u32* row = rows + t * CO_ROW;
         for (u32 j = 0; j < A.n; j++) {
@@ -143,17 +140,20 @@ __global__ __launch_bounds__(CS_CLS) void k_strand_tables(const u32* __restrict_
         }
         rf = co_rounds(cnt[2 * t], tcap);
         rr = co_rounds(cnt[2 * t + 1], tcap);
-        units = co_byte_units((rf + rr) * tcap, tcap, row, A.n);
-        if (co_row_chunks(row, A.n) == 0) rf = rr = 0;       // (a digit without keys: no round is run)
+        np = co_pass_count(cnt[2 * t], cnt[2 * t + 1], tcap, one_pass);
+        units = co_byte_units(np * tcap, tcap, row, A.n);
+        if (co_row_chunks(row, A.n) == 0) rf = rr = np = 0;  // (a digit without keys: no round is run)
     }
     const u32 ux = block_excl_scan(units, waves, total);
     if (t < 256) ust[t] = ux;
     if (t == 0) ust[256] = total;
-    // the forward and the reverse rounds of the call, for the host's counters (kr_debug_coarse_strand)
+    // the forward and the reverse rounds of the call and its passes, for the host's counters (kr_debug_coarse_strand)
     (void)block_excl_scan(rf, waves, total);
     if (t == 0) host_rounds[0] = total;
     (void)block_excl_scan(rr, waves, total);
     if (t == 0) host_rounds[1] = total;
+    (void)block_excl_scan(np, waves, total);
+    if (t == 0) host_rounds[2] = total;
 }
 
 // the entries into their classes: a workgroup counts its candidates' classes in LDS, takes its room in each class with one
@@ -193,40 +193,84 @@ __global__ __launch_bounds__(CS_T) void k_strand_fill(const kr_cand* __restrict_
     }
 }
 
-// One key against the table of the round (linear probing from the hash's top bits; a slot's tag gates the look at the
-// candidate's full prefix): a key under a candidate's prefix joins the unit's hits in LDS (the excess of a unit with more
-// than CO_HB of them goes straight to the list) and ORs presence + diagnostic base into the candidate's state word
-// OS (one-strand form): slot -> entry c0 + idx of the round's slice, whose pattern is compared and whose candidate takes the
-// bits; in a reverse round (`rev`) the hit is the window's REVERSE record: its key goes to the list, its base to the state
-template <int OS>
-__device__ __forceinline__ void co_lookup(u64 key, u64 pmask, int LR, const u32* slots, u32 c0, const kr_cand* __restrict__ cands,
-                                          u32* __restrict__ state, u32 orbits, u32 side_shift, u64* s_hit, u32* s_nhit,
-                                          u32* __restrict__ hits, u64* __restrict__ hitkeys, u32 hitcap,
-                                          const CoEnt* __restrict__ ents, bool rev, const CoStrand& S) {
+// One key against the table at hand (linear probing from the hash's top bits; a slot's tag gates the look at the
+// candidate's full prefix).  A hit -- where it goes: the unit's genome -- joins the unit's hits in LDS (the excess of a
+// unit with more than CO_HB of them goes straight to the list) and ORs presence + diagnostic base into the candidate's
+// state word
+struct CoHitSink {
+    u32* __restrict__ state;
+    u32 orbits, side_shift;
+    u64* s_hit;
+    u32* s_nhit;
+    u32* __restrict__ hits;
+    u64* __restrict__ hitkeys;
+    u32 hitcap;
+    int LR;
+};
+__device__ __forceinline__ void co_hit(const CoHitSink& K, u64 key, u32 ci) {
+    const u32 at0 = atomicAdd(K.s_nhit, 1u);
+    if (at0 < CO_HB) K.s_hit[at0] = key;
+    else {
+        const u32 pos = atomicAdd(K.hits, 1u);
+        if (pos < K.hitcap) K.hitkeys[pos] = key;
+    }
+    const u32 bb = (u32)(key >> (62 - 2 * K.LR)) & 3u;
+    atomicOr(&K.state[ci], K.orbits | (1u << (K.side_shift + bb)));
+}
+
+// the two-strand form: a key lies under one candidate at most
+__device__ __forceinline__ void co_lookup(u64 key, u64 pmask, const u32* slots, u32 c0, const kr_cand* __restrict__ cands,
+                                          const CoHitSink& K) {
     const u64 pre = key & pmask;
     const u32 h = co_hash(pre);
     const u32 tag = h & 0x7FFFFu;
     u32 s = h >> (32 - CO_SLOT_LOG);
     for (u32 w = slots[s]; w != CO_EMPTY; w = slots[s]) {
         if ((w & 0x7FFFFu) == tag) {
-            u32 ci = c0 + (w >> 19);
-            if ((OS ? ents[ci].pat : cands[ci].prefix) == pre) {
-                if (OS) {
-                    ci = ents[ci].ci;
-                    if (rev) key = cs_rev_key(S, key);
-                }
-                const u32 at0 = atomicAdd(s_nhit, 1u);
-                if (at0 < CO_HB) s_hit[at0] = key;
-                else {
-                    const u32 pos = atomicAdd(hits, 1u);
-                    if (pos < hitcap) hitkeys[pos] = key;
-                }
-                const u32 bb = (u32)(key >> (62 - 2 * LR)) & 3u;
-                atomicOr(&state[ci], orbits | (1u << (side_shift + bb)));
+            const u32 ci = c0 + (w >> 19);
+            if (cands[ci].prefix == pre) {
+                co_hit(K, key, ci);
                 return;
             }
         }
         s = (s + 1) & (CO_SLOTS - 1);
+    }
+}
+
+// the one-strand form (co_pass.inc): the table holds the pass's forward and reverse entries by the hash of pattern & M, in
+// 16-bit slots.  The walk goes on to the first empty slot: entries with equal pattern & M are neighbours, and a key may lie
+// under one forward AND one reverse entry.  A forward entry is compared with key & pmask and lists the key; a reverse entry
+// is compared with key & mask_rc and the hit is the window's REVERSE record: its key goes to the list, its base to the state
+__device__ __forceinline__ void co_lookup16(u64 key, u64 fm, u64 pmask, const uint16_t* slots, const CoPass& P,
+                                            const CoEnt* __restrict__ ents, const CoStrand& S, const CoHitSink& K) {
+    const u32 h = co_hash(key & fm);
+    const u32 tag = co_slot16_tag(h);
+    u32 s = co_slot16_home(h);
+    for (u32 w = slots[s]; w != CO_SLOT16_EMPTY; w = slots[s]) {
+        if (co_slot16_tagof(w) == tag) {
+            const u32 i = co_slot16_idx(w);
+            const bool fw = i < P.nf;
+            const CoEnt en = ents[fw ? P.c0f + i : P.c0r + (i - P.nf)];
+            if (en.pat == (key & (fw ? pmask : S.mask_rc))) co_hit(K, fw ? key : cs_rev_key(S, key), en.ci);
+        }
+        s = (s + 1) & ((1u << CO_SLOT16_LOG) - 1u);
+    }
+}
+
+// an entry into the 16-bit table: a CAS on the 32-bit word that holds the free slot
+__device__ __forceinline__ void co_insert16(u32* slots, u32 h, u32 idx) {
+    const u32 val = co_slot16(idx, co_slot16_tag(h));
+    u32 s = co_slot16_home(h);
+    for (;;) {
+        u32* w = slots + (s >> 1);
+        const u32 sh = (s & 1u) * 16u;
+        const u32 old = *(volatile u32*)w;
+        if (((old >> sh) & 0xFFFFu) != CO_SLOT16_EMPTY) {
+            s = (s + 1) & ((1u << CO_SLOT16_LOG) - 1u);
+            continue;
+        }
+        // (lost against a neighbour's insert into either half of the word: the same slot is looked at again)
+        if (atomicCAS(w, old, (old & ~(0xFFFFu << sh)) | (val << sh)) == old) return;
     }
 }
 
@@ -254,19 +298,22 @@ __device__ __forceinline__ void co_load(u32x4 (&v)[CO_UNROLL], const u64* __rest
 // issued before phase 1 of this one, so 64 KB per workgroup are in flight while it computes.  A new top byte starts cold:
 // its row and its table are fetched first anyway.
 //
-// Phase 1 (per iteration) only tests a bit of a 2^17-bit prefilter in LDS (set by the candidates' hashes: 3-7 % of the
-// keys pass) and queues what passes: a ballot per wave and key slot, one LDS atomic by one lane, a lane's place from the
-// lanes below it.  Phase 2 (per UNIT: its barriers and its dependent global reads would drain the prefetch) looks the
+// Phase 1 (per iteration) only tests the two bits of a key's hash in a 2^17-bit prefilter in LDS (a blocked Bloom filter
+// set by the hashes of the table's entries, co_pass.inc: 2-4 % of the keys pass) and queues what passes, all key slots of
+// the iteration as one batch: every read, one wait, a ballot per key slot, ONE LDS atomic by one lane for the wave, a
+// lane's place from the passing lanes of the earlier slots and the lanes below it.  Phase 2 (per UNIT: its barriers and its dependent global reads would drain the prefetch) looks the
 // queued keys up, a thread per key, densely; a unit that overran the queue is read again and looked up in place.  A unit's hits gather
 // in LDS and take their room in the genome's list with ONE atomic per unit.
 //
-// OS: the one-strand form -- cb = the class bounds (k_strand_tables), a round = one reading of one class: its slice of the
-// entry array and its mask (both wave-uniform) stand where cands + c0 and pmask stand in the two-strand form.
+// OS: the one-strand form -- cb = the class bounds (k_strand_tables); what the unit numbering calls a round is a PASS
+// (co_pass.inc): the forward round p and the reverse round p of the digit in one table of 16-bit slots (one_pass = 0: one
+// round after the other, the same kernel).  A key is tested ONCE, under M, the bits both readings share; phase 2 asks a
+// queued key both ways (co_lookup16).
 template <int OS>
 __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u32* __restrict__ cb, const u32* __restrict__ ust,
                                                        const u32* __restrict__ rows, const kr_cand* __restrict__ cands,
                                                        u32* __restrict__ state, u32 tcap, u64 pmask0, int LR,
-                                                       const CoEnt* __restrict__ ents, CoStrand S) {
+                                                       const CoEnt* __restrict__ ents, CoStrand S, u32 one_pass) {
     __shared__ u32 slots[CO_SLOTS];
     __shared__ u32 bitmap[1u << (CO_BM_LOG - 5)];
     __shared__ u32 s_ust[257];
@@ -283,15 +330,25 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
     if (u0 >= u1) return;
     const u32 lane = threadIdx.x & 63u;
     // the unit at hand and its genome (all wave-uniform)
-    u32 u = u0, t = 0, ust_t = 0, ust_t1 = 0, k0 = 0, k1 = 0, p0 = 0, c0 = 0;
+    u32 u = u0, t = 0, ust_t = 0, ust_t1 = 0, k0 = 0, k1 = 0, p0 = 0;
     u32 cur_t = ~0u, cur_r = ~0u;
     const u64* __restrict__ kp = nullptr;
-    u32* __restrict__ hits = nullptr;
-    u64* __restrict__ hitkeys = nullptr;
-    u32 hitcap = 0, orbits = 0, side_shift = 0;
+    u32 g_cur = 0;                                       // (its hit list, presence bit and side are read at the unit's end)
     bool cold = true;                                    // no load of the iteration at hand has been issued
-    u64 pmask = pmask0;                                  // the mask of the round at hand (OS: pmask or mask_rc)
-    bool rev = false;                                    // OS: the round at hand is a reverse round
+    // the mask under which a key meets the prefilter and the table: OS: M, the bits both readings share (co_pass.inc)
+    const u64 fm = OS ? co_pass_mask(pmask0, S.mask_rc) : pmask0;
+    // the slice of the table of (top byte t, pass r): OS: the pass's entries; else cands + c0f.  Asked where the table is
+    // built and again at every unit's end: a few scalar loads there, no registers held across the key stream
+    auto slice = [&](u32 r) {
+        CoPass P = {};
+        if (OS) P = co_pass_decode(CO_RFL(cb[2 * t]), CO_RFL(cb[2 * t + 1]), CO_RFL(cb[2 * t + 2]), tcap, r, one_pass);
+        else {
+            const u32 cb1 = CO_RFL(cb[t + 1]);
+            P.c0f = CO_RFL(cb[t]) + r * tcap;
+            P.nf = cb1 - P.c0f > tcap ? tcap : cb1 - P.c0f;
+        }
+        return P;
+    };
 
     // unit `un` of top byte t becomes the unit at hand; its round's table is built unless it stands
     auto adopt = [&](const CoUnit& un) {
@@ -300,11 +357,7 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
         k1 = un.k1;
         p0 = k0 & ~1u;
         kp = A.keys[g];
-        hits = A.hits[g];
-        hitkeys = (u64*)(hits + 4);
-        hitcap = A.hitcap[g];
-        orbits = 1u << A.bit[g];
-        side_shift = A.side[g];
+        g_cur = g;
         if (t != cur_t || r != cur_r) {
             cur_t = t;
             cur_r = r;
@@ -312,26 +365,21 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
             for (u32 i = threadIdx.x; i < CO_SLOTS; i += CO_T) slots[i] = CO_EMPTY;
             for (u32 i = threadIdx.x; i < (1u << (CO_BM_LOG - 5)); i += CO_T) bitmap[i] = 0;
             __syncthreads();
-            u32 cb0 = cb[OS ? 2 * t : t], cb1 = cb[OS ? 2 * t + 1 : t + 1], rr = r;
+            const CoPass P = slice(r);
             if (OS) {
-                const u32 rf = CO_RFL(co_rounds(cb1 - cb0, tcap));
-                rev = r >= rf;
-                if (rev) {
-                    rr = r - rf;
-                    cb0 = cb1;
-                    cb1 = cb[2 * t + 2];
+                for (u32 i = threadIdx.x; i < P.nf + P.nr; i += CO_T) {
+                    const u32 h = co_hash(ents[i < P.nf ? P.c0f + i : P.c0r + (i - P.nf)].pat & fm);
+                    co_insert16(slots, h, i);
+                    atomicOr(&bitmap[co_bloom_word(h)], co_bloom_bits(h));
                 }
-                const u64 m = rev ? S.mask_rc : pmask0;
-                pmask = ((u64)CO_RFL((u32)(m >> 32)) << 32) | CO_RFL((u32)m);
-            }
-            c0 = cb0 + rr * tcap;
-            const u32 c1 = cb1 - c0 > tcap ? c0 + tcap : cb1;
-            for (u32 i = c0 + threadIdx.x; i < c1; i += CO_T) {
-                const u32 h = co_hash(OS ? ents[i].pat : cands[i].prefix);
-                const u32 word = ((i - c0) << 19) | (h & 0x7FFFFu);
-                u32 s = h >> (32 - CO_SLOT_LOG);
-                while (atomicCAS(&slots[s], CO_EMPTY, word) != CO_EMPTY) s = (s + 1) & (CO_SLOTS - 1);
-                atomicOr(&bitmap[h >> (37 - CO_BM_LOG)], 1u << ((h >> (32 - CO_BM_LOG)) & 31u));
+            } else {
+                for (u32 i = threadIdx.x; i < P.nf; i += CO_T) {
+                    const u32 h = co_hash(cands[P.c0f + i].prefix);
+                    const u32 word = (i << 19) | (h & 0x7FFFFu);
+                    u32 s = h >> (32 - CO_SLOT_LOG);
+                    while (atomicCAS(&slots[s], CO_EMPTY, word) != CO_EMPTY) s = (s + 1) & (CO_SLOTS - 1);
+                    atomicOr(&bitmap[co_bloom_word(h)], co_bloom_bits(h));
+                }
             }
             __syncthreads();
         }
@@ -381,34 +429,55 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
         // phase 1
         const int hi = (int)(k1 - p0) - 2 * (int)threadIdx.x;       // this thread's key slots below `hi` lie in front of k1
         const bool front = p0 < k0 && threadIdx.x == 0;            // ... and its first one in front of k0 (an odd k0: key a0)
+        // all key slots of the iteration as one batch: every hash, every prefilter read, ONE wait; then the ballots
+        // (wave-uniform: they live in scalar registers) and ONE atomic by lane 0 for the wave's room in the queue
+        u32 hs[2 * CO_UNROLL], bw[2 * CO_UNROLL];
 #pragma unroll
-        for (int q = 0; q < CO_UNROLL; q++) {
+        for (int j = 0; j < 2 * CO_UNROLL; j++) {
+            const u32x4& v = V[j >> 1];
+            const u64 key = (j & 1) ? ((u64)v.w << 32 | v.z) : ((u64)v.y << 32 | v.x);
+            // (no branch around the use of a loaded key: the counted waits must be met on every path)
+            hs[j] = co_hash(key & fm);
+            bw[j] = bitmap[co_bloom_word(hs[j])];
+        }
+        u64 bal[2 * CO_UNROLL];
+        u32 total = 0;
 #pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const u64 key = e ? ((u64)V[q].w << 32 | V[q].z) : ((u64)V[q].y << 32 | V[q].x);
-                const u32 h = co_hash(key & pmask);
-                const u32 bw = bitmap[h >> (37 - CO_BM_LOG)];
-                // (no branch around the use of a loaded key: the counted waits must be met on every path)
-                const u32 inr = (u32)(2 * q * (int)CO_T + e < hi) & (u32)!(q == 0 && e == 0 && front);
-                const bool mine = ((bw >> ((h >> (32 - CO_BM_LOG)) & 31u)) & inr) != 0;
-                const u64 bal = __builtin_amdgcn_ballot_w64(mine);
-                if (bal) {                               // (wave-uniform; all 64 lanes are here)
-                    u32 qb = 0;
-                    if (lane == 0) qb = atomicAdd(&s_qn, (u32)__popcll(bal));
-                    qb = CO_RFL(qb);
-                    const u32 qa = qb + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
-                    if (mine && qa < CO_QCAP) s_q[qa] = key;         // (a key that finds the queue full: see below)
-                }
+        for (int j = 0; j < 2 * CO_UNROLL; j++) {
+            const bool inr = ((j >> 1) * 2 * (int)CO_T + (j & 1) < hi) & !(j == 0 && front);
+            const u32 bits = co_bloom_bits(hs[j]);
+            bal[j] = __builtin_amdgcn_ballot_w64(((bw[j] & bits) == bits) & inr);
+            total += (u32)__popcll(bal[j]);
+        }
+        if (total) {                                     // (wave-uniform; all 64 lanes are here)
+            u32 qb = 0;
+            if (lane == 0) qb = atomicAdd(&s_qn, total);
+            qb = CO_RFL(qb);                             // + the passing lanes of the earlier slots + those below this lane
+#pragma unroll
+            for (int j = 0; j < 2 * CO_UNROLL; j++) {
+                const u32x4& v = V[j >> 1];
+                const u64 key = (j & 1) ? ((u64)v.w << 32 | v.z) : ((u64)v.y << 32 | v.x);
+                const u32 qa = qb + __builtin_amdgcn_mbcnt_hi((u32)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal[j], 0u));
+                // (the slot's ballot is its lanes' predicate again: nothing is computed, and no second mask is kept)
+                if (__builtin_amdgcn_inverse_ballot_w64(bal[j]) && qa < CO_QCAP) s_q[qa] = key;     // (a key that finds the queue full: see below)
+                qb += (u32)__popcll(bal[j]);
             }
         }
         if (!last) { p0 += CO_ITER; return false; }
         // phase 2: the unit's queue
         __syncthreads();
+        u32* __restrict__ hits = A.hits[g_cur];
+        u64* __restrict__ hitkeys = (u64*)(hits + 4);
+        const u32 hitcap = A.hitcap[g_cur];
+        const CoHitSink K = {state, 1u << A.bit[g_cur], A.side[g_cur], s_hit, &s_nhit, hits, hitkeys, hitcap, LR};
+        const CoPass P = slice(cur_r);
+        auto lookup = [&](u64 key) {
+            if (OS) co_lookup16(key, fm, pmask0, (const uint16_t*)slots, P, ents, S, K);
+            else co_lookup(key, pmask0, slots, P.c0f, cands, K);
+        };
         if (s_qn <= CO_QCAP) {
             const u32 qn = s_qn;
-            for (u32 i = threadIdx.x; i < qn; i += CO_T)
-                co_lookup<OS>(s_q[i], pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap,
-                              ents, rev, S);
+            for (u32 i = threadIdx.x; i < qn; i += CO_T) lookup(s_q[i]);
         } else {
             // more keys passed the prefilter than the queue holds, and some were dropped (nothing of the unit has been
             // looked up yet): the queue is discarded and the unit's keys are read again and looked up in place -- exact
@@ -419,10 +488,8 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
 #pragma unroll
                 for (int e = 0; e < 2; e++) {
                     const u64 key = e ? ((u64)w.w << 32 | w.z) : ((u64)w.y << 32 | w.x);
-                    const u32 h = co_hash(key & pmask);
-                    if (p + e >= k0 && p + e < k1 && ((bitmap[h >> (37 - CO_BM_LOG)] >> ((h >> (32 - CO_BM_LOG)) & 31u)) & 1u))
-                        co_lookup<OS>(key, pmask, LR, slots, c0, cands, state, orbits, side_shift, s_hit, &s_nhit, hits, hitkeys, hitcap,
-                                      ents, rev, S);
+                    const u32 h = co_hash(key & fm), bits = co_bloom_bits(h);
+                    if (p + e >= k0 && p + e < k1 && (bitmap[co_bloom_word(h)] & bits) == bits) lookup(key);
                 }
             }
         }
@@ -442,7 +509,7 @@ __global__ __launch_bounds__(CO_T, 8) void k_coarse_probe(CoarseArgs A, const u3
         }
         __syncthreads();                                 // (queue and hit buffer are free, their counts zero)
         if (++u >= u1) return true;
-        if (ahead) adopt(un);
+        if (ahead) adopt(uniform(co_unit_decode(u - ust_t, s_bnd, G)));   // (decoded again: `un` is not held across the unit)
         else {
             new_byte();
             cold = true;
