@@ -853,6 +853,9 @@ enum { KR_OPT_SLICE_BASES = 1,       /* -1 automatic; 0..4: sort every genome in
        KR_OPT_COARSE_ONE_PASS = 15,  /* 1 (default; KR_COARSE_ONE_PASS in the environment): the probe of one-strand genomes streams a bucket
                                         past the forward AND the reverse candidates of its digit in one pass, each key tested once for
                                         both readings; 0: one reading after the other (the same kernel, the same results) */
+       KR_OPT_JOIN2_DENSE = 16,      /* 1 (default; KR_JOIN2_DENSE in the environment): k_join2 keeps each key's screen slot in a register and
+                                        queues the live keys per wave, so the exact join runs with full lanes; 0: every key slot joins its
+                                        own live keys, the slot computed again (the same kernel source, the same results) */
        KR_OPT_WIDE_ORDERED = 6 };    /* wide path: 0 (default) flanks of >= 20 bases are numbered through minimizer buckets (look-ups
                                         of neighbouring windows share memory sectors): the same groups and hits, but `cand` no longer
                                         ascends with (left, right); 1: order-preserving ranks, groups in the reference's order */

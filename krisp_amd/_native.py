@@ -59,6 +59,7 @@ OPT_COARSE_POOL = 12
 OPT_JOIN2 = 13
 OPT_COARSE_ONE_STRAND = 14
 OPT_COARSE_ONE_PASS = 15
+OPT_JOIN2_DENSE = 16
 ERR_KEY, ERR_HOST = -5, -6
 STRANDS_BOTH, STRANDS_FORWARD, STRANDS_CANONICAL = 0, 1, 2
 STAGES = ["pack", "hist8", "reduce8", "scatter1", "hist2", "scan2", "scatter2", "chunks", "localsort",

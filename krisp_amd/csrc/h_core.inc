@@ -129,7 +129,8 @@ struct kr_ctx {
     DevBuf isovf;                   // k_intersect3: oversized items
     int join2 = 1;                  // KR_OPT_JOIN2 / KR_JOIN2 env (A/B, tests): 1 = two genomes, one of each side, one diagnostic column, filter on take k_join2; 0 = k_intersect3t as every other call
     u32 j2_grid = 0;                // KR_JOIN2_GRID env (tests: a few workgroups walk many items; 0 = the occupancy x the CUs)
-    int j2_occ[9] = {0};            // resident k_join2 workgroups per CU by threads / 64 (occupancy query, cached)
+    int join2_dense = 1;            // KR_OPT_JOIN2_DENSE / KR_JOIN2_DENSE env (A/B, tests): 1 = k_join2<true>: slots kept, live keys queued per wave and joined with full lanes; 0 = k_join2<false>
+    int j2_occ[2][9] = {{0}};       // resident k_join2<dense> workgroups per CU by threads / 64 (occupancy query, cached)
     int64_t j2_launches = 0, j2_full = 0;    // launches that took k_join2; items it handed on because their live keys found no room
     bool j2_full_counted = false;   // (the redo of a call counts its handed-on items once)
     int64_t isect_ovf_items = 0, isect_refall = 0;
@@ -748,6 +749,8 @@ kr_ctx* kr_create(int device, size_t hbm_budget_bytes) {
         if (e20) c->co_grid = (u32)std::max(0, std::min(65536, atoi(e20)));
         const char* e24 = getenv("KR_JOIN2");
         c->join2 = e24 ? atoi(e24) != 0 : 1;
+        const char* e28 = getenv("KR_JOIN2_DENSE");
+        c->join2_dense = e28 ? atoi(e28) != 0 : 1;
         const char* e25 = getenv("KR_JOIN2_GRID");
         if (e25) c->j2_grid = (u32)std::max(0, std::min(65536, atoi(e25)));
         const char* e23 = getenv("KR_SCAN_GRID");
@@ -993,6 +996,10 @@ int kr_set_option(kr_ctx* c, int option, int64_t value) {
     case KR_OPT_JOIN2:
         if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_JOIN2: 0 or 1");
         c->join2 = (int)value;
+        return KR_OK;
+    case KR_OPT_JOIN2_DENSE:
+        if (value != 0 && value != 1) return fail(c, KR_ERR_PARAM, "KR_OPT_JOIN2_DENSE: 0 or 1");
+        c->join2_dense = (int)value;
         return KR_OK;
     case KR_OPT_ABLATE:
 #ifdef KR_ABLATE

@@ -430,8 +430,9 @@ static int64_t intersect_once(kr_ctx* c, const int* ids, int n, const uint8_t* i
             // (k_join2.inc) -- it never looks at the order inside a bucket, of either genome
             const bool join2 = c->join2 && n == 2 && (ingroup_bits == 1u || ingroup_bits == 2u) && a.apply_filter == 1 &&
                                g.D == 1 && tagk && ip.p0 >= 2 && c->isect_fmt == 0 && c->isect_kernel == 0 && c->fuse_anchor != 0;
-            const Isect3Kernel kern = join2 ? k_join2 : isect3_kernel(ua, tagk, st32, fmt);
-            int& occ = join2 ? c->j2_occ[T / 64] : c->i3_occ[ua ? 2 : (tagk ? 1 : 0)][st32 ? 3 : fmt][T / 64];
+            const bool dense2 = c->join2_dense != 0;
+            const Isect3Kernel kern = join2 ? (dense2 ? k_join2<true> : k_join2<false>) : isect3_kernel(ua, tagk, st32, fmt);
+            int& occ = join2 ? c->j2_occ[dense2 ? 1 : 0][T / 64] : c->i3_occ[ua ? 2 : (tagk ? 1 : 0)][st32 ? 3 : fmt][T / 64];
             if (occ == 0) {
                 int per = 0;
                 const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, (int)T, 0);

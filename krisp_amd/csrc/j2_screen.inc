@@ -47,3 +47,9 @@ __host__ __device__ inline bool j2_live(uint32_t a, uint32_t b) {
     return (a & 15u) != 0 && (b & 15u) != 0 && (u & (u - 1)) != 0;
 }
 __host__ __device__ inline bool j2_live_byte(uint32_t byte) { return j2_live(byte & 15u, byte >> 4); }
+// the same rule as one comparison: the smallest of a, b and (a | b) without its lowest bit is not zero
+__host__ __device__ inline bool j2_live_byte_min(uint32_t byte) {
+    const uint32_t a = byte & 15u, b = (byte >> 4) & 15u, u = a | b, two = u & (u - 1u);
+    const uint32_t m = a < b ? a : b;
+    return (m < two ? m : two) != 0;
+}

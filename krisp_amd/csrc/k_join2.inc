@@ -17,14 +17,36 @@
 // reads what the same CU read microseconds before.  A live anchor key that finds no room within J2_PROBES slots flags
 // its item: it is listed in a.ovf like an oversized one (and counted in a.ovf[I3_OVF_CAP + 2]), the host's redo path
 // answers it.  Neither genome's order inside a bucket is looked at.
+//
+// k_join2<true> (KR_OPT_JOIN2_DENSE, the default): about one key in ten is live, so a key slot's own `if (live) insert` ran
+// for about six lanes of a wave, eight times per item, and every key's slot was computed a second time behind the barrier.
+// Here the four screen slots of a batch stay in registers from the visit that sets the bits to the test (the anchor's across
+// the other genome's visit), and behind barrier (2) / (3) a wave appends its live keys to a queue of its own (j2_queue.inc:
+// ballot, lanes below, one 8-byte entry of two shifts; the fill is a scalar) and joins them 64 at a time with every lane
+// busy, the rest before the barrier that follows.  The queues are lkey[], which nobody else touches between barriers (1)
+// and (4).  The table fills in another order; what it holds behind barrier (4) is the same.  k_join2<false> is the kernel
+// without this.
 // ----------------------------------------------------------------------------
 #include "j2_screen.inc"
+#include "j2_queue.inc"
 
 #ifndef J2_OCC
 #define J2_OCC 6            // waves per SIMD the kernel is compiled for
 #endif
 #define J2_FULL_WORD (I3_OVF_CAP + 2)
 
+static_assert(J2Q_CAP * (I3_MAXT / 64) <= J2_TAB, "the waves' queues lie in lkey[]");
+
+// a wave's queue between its own writes and its own reads of other lanes' entries: the compiler keeps the order, the LDS
+// counter has run out (the LDS serves one wave's instructions in order; the wait makes that independent of it)
+__device__ __forceinline__ void j2q_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool DENSE>
 __global__ __launch_bounds__(I3_MAXT, J2_OCC) void k_join2(Isect3Args a, Geom g) {
     __shared__ __attribute__((aligned(16))) u32 scr[J2_SCREEN / 4];
     __shared__ __attribute__((aligned(16))) unsigned long long tkey[J2_TAB];
@@ -81,6 +103,9 @@ __global__ __launch_bounds__(I3_MAXT, J2_OCC) void k_join2(Isect3Args a, Geom g)
     u32 voff = 0;
     I3Regs X, Y, KA;
     KA.q[0] = KA.q[1] = u32x4{0, 0, 0, 0};
+    u32 slotA[4] = {0, 0, 0, 0};              // DENSE: the screen slots of KA's keys
+    unsigned long long* const myq = lkey + J2Q_CAP * (tid >> 6);       // DENSE: this wave's queue
+    const unsigned char* const scrb = reinterpret_cast<const unsigned char*>(scr);      // (byte slot of the screen = j2_byte of its word)
     i3_issue(X, a, keyp, cur, T);
 
     auto ikey_of = [&](u32 lo, u32 hi) { return j2_item_key(((u64)hi << 32) | lo, p0, wbits); };
@@ -109,6 +134,43 @@ __global__ __launch_bounds__(I3_MAXT, J2_OCC) void k_join2(Isect3Args a, Geom g)
             if (old == want || old == 0ull) break;
             h = (h + 1) & (J2_TAB - 1);
         }
+    };
+    // DENSE: one key slot's live keys onto the wave's queue
+    // (the ballot of each comparison is the comparison's own mask; the ballot of their conjunction is built from a lane value)
+    auto q_push = [&](u32& fill, bool valid, bool lv, u32 lo, u32 hi) {
+        const bool live = valid & lv;
+        const u64 m = __builtin_amdgcn_ballot_w64(valid) & __builtin_amdgcn_ballot_w64(lv);
+        const u32 below = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));      // = j2q_below(m, lane)
+        if (live) myq[j2q_place(fill, below)] = j2q_entry(lo, hi, p0);
+        fill = i3_uni(j2q_fill_after(fill, m));
+    };
+    // DENSE: the n entries on top of the queue, one per lane, into the table (ANCHOR) or past it
+    auto q_join = [&](u32& fill, u32 n, bool anchor) {
+        j2q_order();
+        if (lane < n) {
+            const u64 en = myq[j2q_first(fill, n) + lane];
+            const u64 ik = j2q_key(en, wbits);
+            if (anchor) insert(ik, prA | (sdA << j2q_base(en)));
+            else probe(ik, prB | (sdB << j2q_base(en)));
+        }
+        j2q_order();
+        fill = i3_uni(j2q_first(fill, n));
+    };
+    // DENSE: the live keys of a batch (screen slots sl[]) queued and joined; nothing is left in the queue
+    auto q_batch = [&](const I3Regs& K, const u32 (&sl)[4], u32 count, bool anchor) {
+        const u32 tid = opaque_tid();
+        u32 by[4];
+        // (read for every lane: a lane past `count` holds the slot of whatever its load left, inside the screen for any input
+        // -- j2_slot keeps J2_SCREEN_LOG bits --, and `valid` keeps it out of the queue)
+#pragma unroll
+        for (int e = 0; e < 4; e++) by[e] = scrb[sl[e]];
+        u32 fill = 0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            q_push(fill, I3_POS(e) < count, j2_live_byte_min(by[e]), I3_LO(K, e), I3_HI(K, e));
+            if (j2q_drains(fill)) q_join(fill, J2Q_DRAIN, anchor);
+        }
+        if (fill) q_join(fill, fill, anchor);
     };
     auto list_item = [&](u32 it, bool full) {
         const u32 idx = atomicAdd(&a.ovf[0], 1u);
@@ -163,11 +225,15 @@ __global__ __launch_bounds__(I3_MAXT, J2_OCC) void k_join2(Isect3Args a, Geom g)
                 if (tid == 0) list_item(st.it, false);
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (I3_POS(e) < cnt) {
+                for (int e = 0; e < 4; e++) {
+                    if (DENSE) {
+                        slotA[e] = j2_slot(ikey_of(I3_LO(R, e), I3_HI(R, e)));
+                        if (I3_POS(e) < cnt) atomicOr(&scr[slotA[e] >> 2], j2_bit(slotA[e], base_of(I3_LO(R, e)), false));
+                    } else if (I3_POS(e) < cnt) {
                         const u32 slot = j2_slot(ikey_of(I3_LO(R, e), I3_HI(R, e)));
                         atomicOr(&scr[slot >> 2], j2_bit(slot, base_of(I3_LO(R, e)), false));
                     }
+                }
                 KA = R;
             }
             if (tid < 2 * (u32)a.n) {
@@ -183,35 +249,48 @@ __global__ __launch_bounds__(I3_MAXT, J2_OCC) void k_join2(Isect3Args a, Geom g)
                 if (tid == 0) ctl[0] = 0;           // (everybody has read the item before's count: barrier (1) lies between)
                 item_firstb = 0;
             }
+            u32 slotB[4];                           // DENSE: the screen slots of R's keys, for the bits and for the test
+            if (DENSE) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) slotB[e] = j2_slot(ikey_of(I3_LO(R, e), I3_HI(R, e)));
+            }
             if (pass == 0) {
 #pragma unroll
                 for (int e = 0; e < 4; e++)
                     if (I3_POS(e) < left) {
-                        const u32 slot = j2_slot(ikey_of(I3_LO(R, e), I3_HI(R, e)));
+                        const u32 slot = DENSE ? slotB[e] : j2_slot(ikey_of(I3_LO(R, e), I3_HI(R, e)));
                         atomicOr(&scr[slot >> 2], j2_bit(slot, base_of(I3_LO(R, e)), true));
                     }
                 if (last_of_pass) {
                     __syncthreads();                                                // (2) the screen is complete
+                    if (DENSE) {
+                        q_batch(KA, slotA, cnt, true);
+                    } else {
 #pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        if (I3_POS(e) < cnt) {
-                            const u64 ik = ikey_of(I3_LO(KA, e), I3_HI(KA, e));
-                            const u32 slot = j2_slot(ik);
-                            if (j2_live_byte(j2_byte(scr[slot >> 2], slot))) insert(ik, prA | (sdA << base_of(I3_LO(KA, e))));
-                        }
+                        for (int e = 0; e < 4; e++)
+                            if (I3_POS(e) < cnt) {
+                                const u64 ik = ikey_of(I3_LO(KA, e), I3_HI(KA, e));
+                                const u32 slot = j2_slot(ik);
+                                if (j2_live_byte(j2_byte(scr[slot >> 2], slot))) insert(ik, prA | (sdA << base_of(I3_LO(KA, e))));
+                            }
+                    }
                     __syncthreads();                                                // (3) the live anchor keys are in the table
                     item_full = i3_uni(ctl[1]);
                 }
             }
             // (one batch: set and tested in one visit; more: tested on the second walk, behind barrier (3))
             if ((nx.it != st.it || pass == 1) && !item_full) {
+                if (DENSE) {
+                    q_batch(R, slotB, left, false);
+                } else {
 #pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (I3_POS(e) < left) {
-                        const u64 ik = ikey_of(I3_LO(R, e), I3_HI(R, e));
-                        const u32 slot = j2_slot(ik);
-                        if (j2_live_byte(j2_byte(scr[slot >> 2], slot))) probe(ik, prB | (sdB << base_of(I3_LO(R, e))));
-                    }
+                    for (int e = 0; e < 4; e++)
+                        if (I3_POS(e) < left) {
+                            const u64 ik = ikey_of(I3_LO(R, e), I3_HI(R, e));
+                            const u32 slot = j2_slot(ik);
+                            if (j2_live_byte(j2_byte(scr[slot >> 2], slot))) probe(ik, prB | (sdB << base_of(I3_LO(R, e))));
+                        }
+                }
             }
             if (nx.it != st.it) {
                 // ===== last batch of the item: the survivors, listed, ranked among themselves, written ascending
